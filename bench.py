@@ -24,6 +24,15 @@ into the replay buffer (RCCL over xGMI) — C3's one exchange, timed beside the 
 
 value = expansions created on all ranks in the K timed steps / max over ranks of the wall
 time of those K steps (barrier + device sync on both sides).
+
+A plain run sets up (pool, burn-in), warms up, times the K steps and prints the result line.
+`--full` adds everything else the line can carry: the CPU baselines, the per-phase and
+walk-only roofline figures, the other launch schedules, the Philox, network and chess modes,
+the tower alone and the Engine API (`cpu_baseline`, `extra`).
+
+`--dump-outputs DIR` writes what the timed launch computed as DIR/<name>.npy (dump_outputs):
+each game slot's moves — the column played, the result and the position after it — indexed by
+the move's number since the burn-in's end, which does not depend on the games' pace.
 """
 from __future__ import annotations
 
@@ -582,8 +591,97 @@ def burn_in(sp, max_steps: int = 200, check_every: int = 8) -> int:
     return steps
 
 
+DUMP_BYTES = 60 << 20        # --dump-outputs writes at most this much (32 bytes per move)
+DUMP_MOVE_BYTES = 4 + 4 + 3 * 8
+
+
+class MoveLog:
+    """The per-step outputs of the self-play launches (C4SelfPlay.run / run_pooled: results,
+    moves, positions after the move) of the game slots `slots`, copied to the host launch
+    after launch, in the order the launches ran."""
+
+    def __init__(self, slots: torch.Tensor):
+        self.slots = slots
+        self.parts = []
+
+    def add(self, sp):
+        """The launch that just ran on pool `sp` (call after its device sync)."""
+        s = self.slots
+        self.parts.append((sp._run_results[:, s].cpu().numpy(), sp._run_moves[:, s].cpu().numpy(),
+                           sp._run_states[:, s].cpu().numpy()))
+
+    def played(self):
+        """Moves finished so far, per slot."""
+        import numpy as np
+        n = np.zeros(self.slots.numel(), np.int64)
+        for res, _, _ in self.parts:
+            n += ((res != _native.ZC_SLOT_SKIP) & (res != _native.ZC_SLOT_IDLE)).sum(0)
+        return n
+
+
+def dump_slots(games: int, moves: int, seed: int, dev) -> torch.Tensor:
+    """The game slots --dump-outputs writes: all of them while `moves` moves of each fit
+    DUMP_BYTES, else a fixed sample (seeded by --seed alone), in slot order."""
+    import numpy as np
+    n = max(1, min(games, DUMP_BYTES // (DUMP_MOVE_BYTES * max(moves, 1))))
+    idx = np.arange(games) if n == games else np.sort(np.random.default_rng(seed).choice(games, n, replace=False))
+    return torch.as_tensor(idx, dtype=torch.int64, device=dev)
+
+
+def dump_outputs(sp, log: MoveLog, moves: int, out_dir: str, rank: int = 0) -> dict:
+    """Writes what the warm-up and the timed launch computed for the logged slots, as
+    <out_dir>/<name>.npy ([n slots] x [`moves` = W + K moves] each):
+
+      moves.npy    float32  the column played
+      results.npy  float32  the game's result after the move (ZC_C4_ONGOING = 2 while it runs)
+      states.npy   float64  the position after the move: stones X, stones O (bit masks < 2^49,
+                            exact in float64), turn
+      game_ids.npy float32  the slots' global game ids
+
+    Row j of a slot is its j-th move since the burn-in's end, whichever launch played it: the
+    pooled schedule hands the moves out by the games' pace, so how far each slot gets inside
+    the window differs from run to run, but its j-th move does not (the searches and the
+    per-game MT19937 streams are exact).  Slots the window left short of `moves` moves are
+    played on by an untimed lockstep launch of the same kernel (C4SelfPlay.run), and moves
+    past `moves` are left out, so two runs with the same arguments write the same files."""
+    import numpy as np
+    short = moves - int(log.played().min())
+    if short > 0:
+        sp.run(short)
+        torch.cuda.synchronize(sp.dev)
+        log.add(sp)
+    n = log.slots.numel()
+    mv = np.full((n, moves), -1, np.float32)
+    res = np.full((n, moves), -1, np.float32)
+    st = np.zeros((n, moves, 3), np.float64)
+    base = np.zeros(n, np.int64)
+    for r, m, s in log.parts:
+        valid = (r != _native.ZC_SLOT_SKIP) & (r != _native.ZC_SLOT_IDLE)
+        cnt = valid.sum(0)
+        if not np.array_equal(cnt, np.cumprod(valid, 0).sum(0)):
+            raise RuntimeError("a launch's moves of a slot are not its first rows")
+        k, j = np.nonzero(valid)
+        pos = base[j] + k
+        keep = pos < moves
+        k, j, pos = k[keep], j[keep], pos[keep]
+        mv[j, pos] = m[k, j]
+        res[j, pos] = r[k, j]
+        st[j, pos] = s[k, j]
+        base += cnt
+    if (mv < 0).any():
+        raise RuntimeError("a logged slot has fewer moves than the dump holds")
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if rank == 0 else f".rank{rank}"
+    files = {"moves": mv, "results": res, "states": st,
+             "game_ids": (log.slots.cpu().numpy() + sp.first_id).astype(np.float32)}
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), a)
+    return {"dir": out_dir, "slots": n, "moves_per_slot": moves, "completed_untimed_moves": max(short, 0),
+            "bytes": int(sum(a.nbytes for a in files.values()))}
+
+
 def run_steps(sp, steps: int, warmup: int, world: int = 1, launch: str = "pooled", carry: bool = True,
-              drain: bool = True) -> dict:
+              drain: bool = True, log: MoveLog | None = None) -> dict:
     """W untimed moves, then K timed steps (K x G moves) bracketed by barrier + device sync,
     as ONE self-play launch followed by its trajectory recording; HIP events around it on its
     stream.  launch "pooled" (the default, C4SelfPlay.run_pooled): the G games share a budget
@@ -607,6 +705,8 @@ def run_steps(sp, steps: int, warmup: int, world: int = 1, launch: str = "pooled
         else:
             sp.run(warmup)
     torch.cuda.synchronize(dev)
+    if log is not None and warmup:
+        log.add(sp)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -628,9 +728,13 @@ def run_steps(sp, steps: int, warmup: int, world: int = 1, launch: str = "pooled
                & (res != _native.ZC_SLOT_SKIP)).sum().item())
     moves = int(((res != _native.ZC_SLOT_IDLE) & (res != _native.ZC_SLOT_SKIP)).sum().item())
     tot = [int(x) for x in st[:, [0, 1, 2]].sum(0).tolist()]
+    if log is not None:
+        log.add(sp)
     if carry and drain:   # untimed: finish the moves left in flight (the pool's later users search it)
         sp.drain()
         torch.cuda.synchronize(dev)
+        if log is not None:
+            log.add(sp)
     return {"dt": dt, "launch_ms": ev[0].elapsed_time(ev[2]), "launch_record_ms": ev[0].elapsed_time(ev[1]), "expansions": tot[0], "depth_sum": tot[1],
             "finished": fin, "leaves": tot[2], "moves": moves}
 
@@ -726,11 +830,18 @@ def run_rank(args, rank: int, world: int, local: int):
     from zeroclone_amd.selfplay import C4SelfPlay
     G, S, B = args.games, args.sims, args.batch
     torch.cuda.set_stream(torch.cuda.Stream(dev))   # every launch and the timing events on one stream
-    sp = C4SelfPlay(G, S, c=args.c, batch_size=B, seed=args.seed, rank=rank, device=local, record=True)
+    # room for the games that can finish between two takes of the trajectory pool (the warm-up
+    # and the timed steps; a game has at least 7 moves): the default 8 G up to ~50 steps
+    games_cap = max(8 * G, 1024, (args.steps + args.warmup) * G // 7 + 2 * G)
+    sp = C4SelfPlay(G, S, c=args.c, batch_size=B, seed=args.seed, rank=rank, device=local, record=True,
+                    games_cap=games_cap)
     burn = burn_in(sp) if args.burn_in else 0
-    snap = pool_snapshot(sp) if (world == 1 and not args.no_cpu_baseline) else None
-    r = run_steps(sp, args.steps, args.warmup, world, launch=args.launch, carry=not args.no_carry)
+    full = args.full and world == 1
+    snap = pool_snapshot(sp) if (full and not args.no_cpu_baseline) else None
+    log = MoveLog(dump_slots(G, args.steps + args.warmup, args.seed, dev)) if args.dump_outputs else None
+    r = run_steps(sp, args.steps, args.warmup, world, launch=args.launch, carry=not args.no_carry, log=log)
     gather = gather_trajectories(sp, world)
+    dumped = dump_outputs(sp, log, args.steps + args.warmup, args.dump_outputs, rank) if log is not None else None
     counts, dt_max, kms = reduce_over_ranks([r["expansions"], r["depth_sum"], r["finished"], r["leaves"]], r["dt"],
                                             r["launch_ms"], dev)
     expansions, depth_sum, finished, leaves = counts
@@ -787,7 +898,9 @@ def run_rank(args, rank: int, world: int, local: int):
                       "selfplay_launch_ms": round(r["launch_ms"], 3),
                       "trajectory_allgather": gather},
         }
-        if world == 1:
+        if dumped is not None:
+            out["extra"]["dump_outputs"] = dumped
+        if full:
             out["extra"]["phases"] = phases(sp, args, bytes_launch, avg_kernel_s)
             other = "free" if args.launch == "pooled" else "pooled"
             # the other schedule's own steady state: its warmup first (a pooled window leaves
@@ -812,7 +925,7 @@ def run_rank(args, rank: int, world: int, local: int):
                         "own; games behind the launch's average pace run at raised wave priority (pace balancing, "
                         "DESIGN round 6); the headline `value` is the pooled schedule (the games share K x G moves; "
                         "each game's moves are its lockstep moves)"}
-        if world == 1 and args.net_steps > 0:
+        if full and args.net_steps > 0:
             out["extra"]["c2_philox"] = philox_mode(sp, args)
             out["extra"]["c2_value_net"] = net_mode(sp, G, S, B, args.c, args.net_steps, dev)
             out["extra"]["c2_puct"] = c4_puct_mode(sp, G, S, B, args.net_steps, dev)
@@ -830,7 +943,7 @@ def run_rank(args, rank: int, world: int, local: int):
             crude_pool.close()
             out["extra"]["net_tower"] = tower_mode(dev)
             out["extra"]["c1_engine"] = c1_mode(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(S, B, args.c, snap, args.steps)
             if args.net_steps > 0:
                 out["extra"]["c4_chess"]["crude"]["cpu_baseline"] = cpu_baseline_chess(
@@ -1080,10 +1193,17 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-burn-in", dest="burn_in", action="store_false",
                     help="time from the lockstep opening instead of steady-state self-play")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baselines, the phase and walk figures, the other launch "
+                         "schedules and the Philox / network / chess / tower / Engine modes (cpu_baseline, extra; "
+                         "N=1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the moves the warm-up and the timed steps computed (column, result, position "
+                         "after it, by game slot and move number) as DIR/<name>.npy; see dump_outputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--net-steps", type=int, default=5,
-                    help="timed steady-state moves of the network / chess modes reported under extra "
-                         "(0 = skip; N=1 only)")
+                    help="with --full: timed steady-state moves of the network / chess modes reported under "
+                         "extra (0 = skip; N=1 only)")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="torch.distributed backend of the N-rank run (nccl = RCCL over xGMI)")
     ap.add_argument("--share-device", action="store_true",

@@ -25,7 +25,7 @@ for st in "$@"; do
     sel)    run pytest_sel 1100 python -u -m pytest ${PYSEL} -x -v --timeout 400 --timeout-method thread -p no:cacheprovider; rc=$?
             if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi ;;
     smoke)  run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench)  run bench 900 python bench.py || exit $? ;;
+    bench)  run bench 900 python bench.py --full || exit $? ;;
     benchq) run benchq 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --net-steps 0 || exit $? ;;
     prof)   run prof 900 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv \
                 -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --net-steps 0 || exit $? ;;
