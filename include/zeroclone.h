@@ -658,6 +658,61 @@ int zc_traj_record_steps_async(int32_t n, const zc_traj_buffers *buf, void *d_st
                                int32_t *d_results, int32_t steps, const int32_t *d_reached, void *d_scratch,
                                int64_t scratch_bytes, void *hip_stream);
 
+/* ---- root visit counts as policy targets (pi(a) = N(a) / sum N) ----------------------
+ * A sparse record per searched position, kept beside a zc_traj_buffers pool (which it does
+ * not change).  One uint32 entry per root move with Na > 0: move id | count << 16 (Connect4:
+ * the column; chess: the packed uint16 move), in the root's move-list order (the index order
+ * of d_out_root_na).  A count above 65535 is stored as 65535 and flagged.  Both levels are
+ * CSR; the caller owns every buffer (device memory):
+ *   d_slot_pi    [n][slot_cap] uint32        the entries of the slot's current game
+ *   d_slot_off   [n][max_len + 1] int32      history position i owns [off[i], off[i+1]); off[0] = 0
+ *   d_slot_base  [n] int64                   scratch: the pool place of a game being committed
+ *   d_pool_pi    [pi_pool_cap] uint32        finished games' entries, game after game
+ *   d_pool_first [pool_cap] int64            per pooled position (indexed like d_labels): its
+ *   d_pool_count [pool_cap] int32            first entry in d_pool_pi and their number
+ *   d_pctl       [4] int64                   ZC_TRAJ_PI_* below
+ * max_len and pool_cap are the zc_traj_buffers' the calls are given. */
+typedef struct zc_traj_policy_buffers {
+    int32_t slot_cap, reserved;
+    int64_t pi_pool_cap;
+    uint32_t *d_slot_pi;
+    int32_t *d_slot_off;
+    int64_t *d_slot_base;
+    uint32_t *d_pool_pi;
+    int64_t *d_pool_first;
+    int32_t *d_pool_count;
+    int64_t *d_pctl;
+} zc_traj_policy_buffers;
+#define ZC_TRAJ_PI_ENTRIES 0   /* pool entries reserved                                       */
+#define ZC_TRAJ_PI_OVERFLOW 1  /* bit 0: a slot's history full (slot_cap); bit 1: the entry pool
+                                * full (the game's entries dropped); bit 2: a count saturated */
+/* After the search and before the play and record kernels of a step: for every slot with a
+ * live game (d_slot[g][1] >= 0) the non-zero (move, Na) pairs of row g of d_root_na
+ * [n][stride] become the entries of history position d_slot[g][0] - 1, the position the
+ * search ran from.  d_root_moves [n][stride] uint16 gives the move ids (chess: the roots'
+ * zc_chess_legal_moves_async lists, stride ZC_CHESS_MAX_MOVES); NULL = the index is the id
+ * (Connect4, stride 7).  One wave per slot.  Entries a slot's history cannot take are not
+ * written and set ZC_TRAJ_PI_OVERFLOW bit 0. */
+int zc_traj_policy_append_async(int32_t n, const zc_traj_buffers *buf, const zc_traj_policy_buffers *pol,
+                                const int32_t *d_root_na, const uint16_t *d_root_moves, int32_t stride,
+                                void *hip_stream);
+/* After zc_traj_record_async of the same step: every game that call placed in the pool gets
+ * its entries reserved in d_pool_pi (a prefix sum over the slots, so the layout is
+ * deterministic), copied as one block, and d_pool_first / d_pool_count written for each of
+ * its pooled positions (the game's last position was never searched: count 0).  A game
+ * the entry pool cannot take sets bit 1 and gets first = count = 0 throughout. */
+int zc_traj_policy_commit_async(int32_t n, const zc_traj_buffers *buf, const zc_traj_policy_buffers *pol,
+                                void *hip_stream);
+/* Sparse records to dense training targets: d_out [n_rows][width], ZC_F32 or ZC_F16; row r
+ * holds count / sum (one IEEE single-precision division; fp16: that float rounded to nearest)
+ * of the entries d_entries[d_first[r] .. + d_count[r]) and zeros elsewhere (all zeros for a
+ * row without entries).  width 7: index = move id (ids >= 7 are ignored); width 4096: index =
+ * (id & 63) * 64 + ((id >> 6) & 63) = from * 64 + to, the order of zc_chess_puct_backup's
+ * logits (d_out 16-byte aligned).  Other widths: ZC_EINVAL.  One wave per row. */
+int zc_traj_policy_dense_async(int32_t n_rows, const int64_t *d_first, const int32_t *d_count,
+                               const uint32_t *d_entries, int32_t width, int32_t dtype, void *d_out,
+                               void *hip_stream);
+
 /* ---- any game backend: SURVEY §8(b)'s fallback (gen_search.hip) ----------------------
  * mcts.get_move (mcts.cpp:102-160) for a backend the device knows nothing about: the caller
  * keeps the game states and move objects (backend.get_legal_moves / play_move, the policy

@@ -61,6 +61,17 @@ class TrajBuffers(ctypes.Structure):
                 ("d_ctl", ctypes.c_void_p), ("d_init", ctypes.c_void_p)]
 
 
+class TrajPolicyBuffers(ctypes.Structure):
+    """zc_traj_policy_buffers (include/zeroclone.h): the sparse root-visit-count record kept beside a
+    trajectory pool."""
+    _fields_ = [("slot_cap", ctypes.c_int32), ("reserved", ctypes.c_int32), ("pi_pool_cap", ctypes.c_int64),
+                ("d_slot_pi", ctypes.c_void_p), ("d_slot_off", ctypes.c_void_p), ("d_slot_base", ctypes.c_void_p),
+                ("d_pool_pi", ctypes.c_void_p), ("d_pool_first", ctypes.c_void_p), ("d_pool_count", ctypes.c_void_p),
+                ("d_pctl", ctypes.c_void_p)]
+
+
+ZC_TRAJ_PI_ENTRIES, ZC_TRAJ_PI_OVERFLOW = 0, 1
+ZC_TRAJ_PI_MAX_COUNT = 65535   # a policy entry's count field: 16 bits
 ZC_TRAJ_POSITIONS, ZC_TRAJ_GAMES, ZC_TRAJ_NEXT, ZC_TRAJ_QUOTA, ZC_TRAJ_FINISHED, ZC_TRAJ_OVERFLOW = range(6)
 ZC_SLOT_IDLE = 3
 ZC_SLOT_SKIP = 4
@@ -262,6 +273,12 @@ SIGNATURES = [
                                                ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
     ("zc_traj_record_async", ctypes.c_int, [ctypes.c_int32, P(TrajBuffers), ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_traj_policy_append_async", ctypes.c_int, [ctypes.c_int32, P(TrajBuffers), P(TrajPolicyBuffers),
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    ("zc_traj_policy_commit_async", ctypes.c_int, [ctypes.c_int32, P(TrajBuffers), P(TrajPolicyBuffers),
+                                                   ctypes.c_void_p]),
+    ("zc_traj_policy_dense_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     ("zc_chess_from_fen", ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
     ("zc_chess_init", ctypes.c_int, [ctypes.c_void_p]),
     ("zc_c4_from_rows", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, P(C4State)]),

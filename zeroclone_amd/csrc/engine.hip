@@ -923,6 +923,57 @@ int zc_traj_record_async(int32_t n, const zc_traj_buffers *buf, void *d_states, 
     return ZC_OK;
 }
 
+namespace {
+int check_traj_policy(const zc_traj_policy_buffers *pol) {
+    if (!pol) return fail(ZC_EINVAL, "bad argument");
+    const zc_traj_policy_buffers &q = *pol;
+    if (q.slot_cap < 0 || q.pi_pool_cap < 0)
+        return fail(ZC_EINVAL, "bad policy buffer shape (slot_cap %d, pi_pool_cap %lld)", q.slot_cap,
+                    (long long)q.pi_pool_cap);
+    if (!q.d_slot_pi || !q.d_slot_off || !q.d_slot_base || !q.d_pool_pi || !q.d_pool_first || !q.d_pool_count ||
+        !q.d_pctl)
+        return fail(ZC_EINVAL, "null policy buffer");
+    return ZC_OK;
+}
+}  // namespace
+
+int zc_traj_policy_append_async(int32_t n, const zc_traj_buffers *buf, const zc_traj_policy_buffers *pol,
+                                const int32_t *d_root_na, const uint16_t *d_root_moves, int32_t stride,
+                                void *hip_stream) {
+    if (int r = check_traj(n, buf, nullptr)) return r;
+    if (int r = check_traj_policy(pol)) return r;
+    if (stride < 1 || stride > 65536) return fail(ZC_EINVAL, "stride must be in [1, 65536] (got %d)", stride);
+    if (n && !d_root_na) return fail(ZC_EINVAL, "bad argument");
+    if (!n) return ZC_OK;
+    zc::launch_traj_policy_append(n, *buf, *pol, d_root_na, d_root_moves, stride, (hipStream_t)hip_stream);
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+
+int zc_traj_policy_commit_async(int32_t n, const zc_traj_buffers *buf, const zc_traj_policy_buffers *pol,
+                                void *hip_stream) {
+    if (int r = check_traj(n, buf, nullptr)) return r;
+    if (int r = check_traj_policy(pol)) return r;
+    if (!n) return ZC_OK;
+    zc::launch_traj_policy_commit(n, *buf, *pol, (hipStream_t)hip_stream);
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+
+int zc_traj_policy_dense_async(int32_t n_rows, const int64_t *d_first, const int32_t *d_count,
+                               const uint32_t *d_entries, int32_t width, int32_t dtype, void *d_out,
+                               void *hip_stream) {
+    if (width != 7 && width != 4096) return fail(ZC_EINVAL, "width must be 7 or 4096 (got %d)", width);
+    if (dtype != ZC_F32 && dtype != ZC_F16) return fail(ZC_EINVAL, "dtype must be ZC_F32 or ZC_F16");
+    if (n_rows < 0 || (n_rows && (!d_first || !d_count || !d_out))) return fail(ZC_EINVAL, "bad argument");
+    if (width == 4096 && ((uintptr_t)d_out & 15)) return fail(ZC_EINVAL, "d_out must be 16-byte aligned");
+    if (!n_rows) return ZC_OK;
+    zc::launch_traj_policy_dense(n_rows, d_first, d_count, d_entries, width, dtype == ZC_F16, d_out,
+                                 (hipStream_t)hip_stream);
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+
 int zc_chess_planes_async(zc_engine *eng, int32_t n, const zc_chess_state *d_states, void *d_planes,
                           int32_t planes_dtype, void *hip_stream) {
     if (planes_dtype != ZC_F32 && planes_dtype != ZC_F16) return fail(ZC_EINVAL, "planes_dtype must be ZC_F32 or ZC_F16");

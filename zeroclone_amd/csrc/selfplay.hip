@@ -16,6 +16,8 @@
 // opaque byte records (zc_c4_state: 24 B, zc_chess_state: 72 B), copied 8 bytes at a time.
 #include "zc_internal.h"
 
+#include <hip/hip_fp16.h>
+
 namespace zc {
 namespace {
 
@@ -411,7 +413,194 @@ __global__ __launch_bounds__(kSlotWaves * 64) void traj_steps_copy_kernel(int n,
     }
 }
 
+// ---------------------------------------------------------------- root visit counts
+// The policy targets of the searched positions (pi(a) = N(a) / sum N), sparse: one uint32
+// (move id | count << 16) per root move with Na > 0, in the root's move-list order.  Slot
+// history and pool are both CSR (zc_traj_policy_buffers).
+constexpr int kPiSlotFull = 1, kPiPoolFull = 2, kPiSaturated = 4;
+
+// Append — one wave per slot, after the search and before the play: the non-zero counts of the
+// slot's row, compacted by ballot + prefix popcount, become the entries of history position
+// slot[0] - 1; the running offset is off[pos] -> off[pos + 1].
+__global__ __launch_bounds__(kSlotWaves * 64) void traj_policy_append_kernel(int n, zc_traj_buffers b,
+                                                                             zc_traj_policy_buffers q,
+                                                                             const int32_t *na, const uint16_t *mv,
+                                                                             int stride) {
+    const int lane = (int)(threadIdx.x & 63);
+    const int g = (int)(blockIdx.x * kSlotWaves + (threadIdx.x >> 6));
+    if (g >= n) return;
+    const int32_t *slot = b.d_slot + 4 * (size_t)g;
+    if (slot[1] < 0) return;
+    const int pos = slot[0] - 1;
+    if (pos < 0 || pos >= b.max_len) return;  // never: slot[0] is in [1, max_len]
+    int32_t *off = q.d_slot_off + (size_t)g * (b.max_len + 1);
+    uint32_t *dst = q.d_slot_pi + (size_t)g * q.slot_cap;
+    const int base = pos ? off[pos] : 0;
+    int run = 0, ov = 0;
+    for (int c0 = 0; c0 < stride; c0 += 64) {
+        const int j = c0 + lane;
+        const int cnt = j < stride ? na[(size_t)g * stride + j] : 0;
+        const unsigned long long have = __ballot(cnt > 0);
+        if (cnt > 0) {
+            const long long at = (long long)base + run + __popcll(have & ((1ull << lane) - 1));
+            if (cnt > 65535) ov |= kPiSaturated;
+            const uint32_t id = mv ? (uint32_t)mv[(size_t)g * stride + j] : (uint32_t)j;
+            if (at < q.slot_cap) dst[at] = id | ((uint32_t)min(cnt, 65535) << 16);
+            else ov |= kPiSlotFull;
+        }
+        run += __popcll(have);
+    }
+    ov = (__ballot(ov & kPiSlotFull) ? kPiSlotFull : 0) | (__ballot(ov & kPiSaturated) ? kPiSaturated : 0);
+    if (lane == 0) {
+        off[pos + 1] = (int32_t)min((long long)base + run, (long long)q.slot_cap);
+        if (ov) atomicOr((unsigned long long *)(q.d_pctl + ZC_TRAJ_PI_OVERFLOW), (unsigned long long)ov);
+    }
+}
+
+// Commit pass 1 — one workgroup walks the slots 1024 at a time (as traj_record_kernel, which
+// ran just before and left each pooled game's length in slot[3] and its place in slot[2]):
+// the pooled games' entries get their places in the entry pool in slot order.
+__global__ __launch_bounds__(kRecThreads) void traj_policy_reserve_kernel(int n, zc_traj_buffers b,
+                                                                          zc_traj_policy_buffers q) {
+    long long ent_base = q.d_pctl[ZC_TRAJ_PI_ENTRIES];
+    int overflow = 0;
+    __syncthreads();
+    for (int c0 = 0; c0 < n; c0 += kRecThreads) {
+        const int g = c0 + (int)threadIdx.x;
+        int len = 0;
+        long long cnt = 0;
+        if (g < n) {
+            const int32_t *slot = b.d_slot + 4 * (size_t)g;
+            int32_t *off = q.d_slot_off + (size_t)g * (b.max_len + 1);
+            len = min(slot[3] & 0x7FFFFFFF, b.max_len);
+            if (len > 0) cnt = off[len - 1];  // positions 0 .. len-2 were searched
+            if (slot[0] == 1) off[0] = 0;     // restarted: its history starts over
+        }
+        int x = 0, tx;
+        long long y = cnt, ty;
+        block_scan2(x, y, tx, ty);
+        if (g < n) {
+            long long at = -1;
+            if (len > 0) {
+                if (ent_base + y + cnt > q.pi_pool_cap) overflow = 1;  // dropped: first = count = 0
+                else at = ent_base + y;
+            }
+            q.d_slot_base[g] = at;
+        }
+        ent_base += ty;
+    }
+    const int ov = __syncthreads_or(overflow);
+    if (threadIdx.x == 0) {
+        q.d_pctl[ZC_TRAJ_PI_ENTRIES] = ent_base;
+        if (ov) q.d_pctl[ZC_TRAJ_PI_OVERFLOW] |= kPiPoolFull;
+    }
+}
+
+// Commit pass 2 — one wave per slot: first / count of each pooled position, then the game's
+// entries as one contiguous block.
+__global__ __launch_bounds__(kSlotWaves * 64) void traj_policy_copy_kernel(int n, zc_traj_buffers b,
+                                                                           zc_traj_policy_buffers q) {
+    const int lane = (int)(threadIdx.x & 63);
+    const int g = (int)(blockIdx.x * kSlotWaves + (threadIdx.x >> 6));
+    if (g >= n) return;
+    const int32_t *slot = b.d_slot + 4 * (size_t)g;
+    const int len = min(slot[3] & 0x7FFFFFFF, b.max_len);
+    if (len <= 0) return;
+    const long long P = slot[2], at = q.d_slot_base[g];
+    const int32_t *off = q.d_slot_off + (size_t)g * (b.max_len + 1);
+    for (int i = lane; i < len; i += 64) {
+        if (P + i >= b.pool_cap) break;  // never: pass 1 of the record placed the game inside
+        const int o0 = i ? off[i] : 0;
+        q.d_pool_first[P + i] = at < 0 ? 0 : at + o0;
+        q.d_pool_count[P + i] = (at < 0 || i + 1 >= len) ? 0 : off[i + 1] - o0;
+    }
+    if (at < 0) return;
+    const int total = min(off[len - 1], q.slot_cap);
+    const uint32_t *src = q.d_slot_pi + (size_t)g * q.slot_cap;
+    for (int e = lane; e < total; e += 64) q.d_pool_pi[at + e] = src[e];
+}
+
+// Dense targets, width 7 — one wave per row, lane = column: count / sum of the row's entries.
+template <typename T>
+__global__ __launch_bounds__(256) void traj_policy_dense7_kernel(int n_rows, const int64_t *first,
+                                                                 const int32_t *count, const uint32_t *ent, T *out) {
+    const int lane = (int)(threadIdx.x & 63);
+    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n_rows) return;
+    const int c = count[r];
+    const uint32_t *e = ent + first[r];
+    int sum = 0, mine = 0;
+    for (int k = 0; k < c; ++k) {
+        const uint32_t v = e[k];
+        sum += (int)(v >> 16);
+        if ((int)(v & 0xFFFF) == lane) mine = (int)(v >> 16);
+    }
+    if (lane < 7) {
+        const float p = mine ? __fdiv_rn((float)mine, (float)sum) : 0.0f;
+        if constexpr (sizeof(T) == 2) out[r * 7 + lane] = __float2half_rn(p);
+        else out[r * 7 + lane] = p;
+    }
+}
+
+// Dense targets, width 4096 — a pure HBM-write kernel: one wave per row zero-fills its 16 KB
+// (fp16: 8 KB) with 16-byte stores, 1 KB per wave instruction, waits for them, then scatters
+// the (at most 256) non-zero cells at from * 64 + to.
+template <typename T>
+__global__ __launch_bounds__(256) void traj_policy_dense4096_kernel(int n_rows, const int64_t *first,
+                                                                    const int32_t *count, const uint32_t *ent, T *out) {
+    const int lane = (int)(threadIdx.x & 63);
+    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n_rows) return;
+    T *row = out + r * 4096;
+    float4 *row16 = (float4 *)row;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    constexpr int kChunks = 4096 * (int)sizeof(T) / 16;
+#pragma unroll
+    for (int k = 0; k < kChunks / 64; ++k) row16[k * 64 + lane] = z;
+    const int c = count[r];
+    if (c <= 0) return;
+    const uint32_t *e = ent + first[r];
+    int sum = 0;
+    for (int k = lane; k < c; k += 64) sum += (int)(e[k] >> 16);
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    // the zeros have landed before a cell is written again (same wave, other lanes)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_waitcnt(0);
+    const float fs = (float)sum;
+    for (int k = lane; k < c; k += 64) {
+        const uint32_t v = e[k];
+        const int idx = (int)(v & 63) * 64 + (int)((v >> 6) & 63);
+        const float p = (v >> 16) ? __fdiv_rn((float)(v >> 16), fs) : 0.0f;
+        if constexpr (sizeof(T) == 2) row[idx] = __float2half_rn(p);
+        else row[idx] = p;
+    }
+}
+
 }  // namespace
+
+void launch_traj_policy_append(int n, const zc_traj_buffers &b, const zc_traj_policy_buffers &q, const int32_t *na,
+                               const uint16_t *mv, int stride, hipStream_t s) {
+    const dim3 slots((unsigned)((n + kSlotWaves - 1) / kSlotWaves)), wb(kSlotWaves * 64);
+    hipLaunchKernelGGL(traj_policy_append_kernel, slots, wb, 0, s, n, b, q, na, mv, stride);
+}
+
+void launch_traj_policy_commit(int n, const zc_traj_buffers &b, const zc_traj_policy_buffers &q, hipStream_t s) {
+    const dim3 slots((unsigned)((n + kSlotWaves - 1) / kSlotWaves)), wb(kSlotWaves * 64);
+    hipLaunchKernelGGL(traj_policy_reserve_kernel, dim3(1), dim3(kRecThreads), 0, s, n, b, q);
+    hipLaunchKernelGGL(traj_policy_copy_kernel, slots, wb, 0, s, n, b, q);
+}
+
+void launch_traj_policy_dense(int n_rows, const int64_t *first, const int32_t *count, const uint32_t *ent, int width,
+                              bool half, void *out, hipStream_t s) {
+    const dim3 grid((unsigned)((n_rows + 3) / 4)), wb(256);
+    if (width == 7) {
+        if (half) hipLaunchKernelGGL(traj_policy_dense7_kernel<__half>, grid, wb, 0, s, n_rows, first, count, ent, (__half *)out);
+        else hipLaunchKernelGGL(traj_policy_dense7_kernel<float>, grid, wb, 0, s, n_rows, first, count, ent, (float *)out);
+    } else {
+        if (half) hipLaunchKernelGGL(traj_policy_dense4096_kernel<__half>, grid, wb, 0, s, n_rows, first, count, ent, (__half *)out);
+        else hipLaunchKernelGGL(traj_policy_dense4096_kernel<float>, grid, wb, 0, s, n_rows, first, count, ent, (float *)out);
+    }
+}
 
 size_t traj_steps_scratch_bytes(int n, int K) { return steps_scratch_layout(n, K, nullptr, nullptr); }
 

@@ -390,6 +390,11 @@ void launch_traj_record(int n, const zc_traj_buffers &b, void *states, const int
 size_t traj_steps_scratch_bytes(int n, int K);
 void launch_traj_record_steps(int n, int K, const zc_traj_buffers &b, const void *states, const int16_t *moves,
                               const int32_t *results, const int32_t *reached, void *scratch, hipStream_t s);
+void launch_traj_policy_append(int n, const zc_traj_buffers &b, const zc_traj_policy_buffers &q, const int32_t *na,
+                               const uint16_t *mv, int stride, hipStream_t s);
+void launch_traj_policy_commit(int n, const zc_traj_buffers &b, const zc_traj_policy_buffers &q, hipStream_t s);
+void launch_traj_policy_dense(int n_rows, const int64_t *first, const int32_t *count, const uint32_t *ent, int width,
+                              bool half, void *out, hipStream_t s);
 void launch_uct_debug(int n, const double *logn, const int32_t *na, const double *q, double c, double *out,
                       hipStream_t s);
 

@@ -71,28 +71,73 @@ class TrajBatch:
     labels [n] int32                  Engine.get_dataset label of each position
     moves  [n] int16                  move played from it (-1 at a game's last position)
     games  [k, 5] int64               game number, slot, result, first row, positions
+
+    With the root visit counts recorded (`Trajectories(policy_width=...)`; None otherwise):
+    pi_off [n + 1] int64              row i owns the entries pi[pi_off[i]:pi_off[i + 1]]
+    pi     [total] int32              move id | visit count << 16 (the uint32 entries), one per
+                                      root move with Na > 0 in the root's move-list order; none
+                                      at a game's last position (never searched)
     """
     rows: torch.Tensor
     labels: torch.Tensor
     moves: torch.Tensor
     games: torch.Tensor
+    pi_off: torch.Tensor | None = None
+    pi: torch.Tensor | None = None
 
     def results(self) -> list[int]:
         return [int(r) for r in self.games[:, 2].cpu().tolist()]
+
+    def policy_targets(self, width: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """Dense policy targets [n, width] (zc_traj_policy_dense_async): N(a) / sum N per row,
+        zeros elsewhere (a game's last position: all zeros).  width 7: index = column;
+        width 4096: index = from * 64 + to, the order of the chess PUCT network's logits."""
+        if self.pi is None:
+            raise ValueError("no visit counts were recorded (record_policy=True / Trajectories(policy_width=...))")
+        if dtype not in (torch.float32, torch.float16):
+            raise ValueError("dtype must be torch.float32 or torch.float16")
+        n = self.rows.shape[0]
+        out = torch.empty((n, int(width)), dtype=dtype, device=self.rows.device)
+        count = (self.pi_off[1:] - self.pi_off[:-1]).to(torch.int32)
+        _native.check(_native.lib().zc_traj_policy_dense_async(
+            n, ctypes.c_void_p(self.pi_off.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+            ctypes.c_void_p(self.pi.data_ptr()), int(width),
+            _native.ZC_F16 if dtype == torch.float16 else _native.ZC_F32, ctypes.c_void_p(out.data_ptr()),
+            ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)))
+        return out
 
 
 class Trajectories:
     """Per-slot game histories and the pool of finished games, all in HBM (zc_traj_record_async).
 
     `max_len` positions per game (Connect4: 43), room for `games_cap` finished games and
-    `pool_cap` positions until the next `take()`."""
+    `pool_cap` positions until the next `take()`.
+
+    `policy_width` (7: Connect4, 4096: chess) also records every search's root visit counts,
+    sparse (zc_traj_policy_*): `record_policy()` after the search, the commit inside
+    `record()`.  `pi_slot_cap` entries per slot's game (default: every move of every position
+    visited) and `pi_pool_cap` pooled entries until the next `take()`."""
+
+    PI_STRIDE = {7: 7, 4096: _native.CHESS_MAX_MOVES}   # policy_width -> moves per root (d_out_root_na's row)
 
     def __init__(self, n_slots: int, init_row: torch.Tensor, max_len: int, games_cap: int, pool_cap: int,
-                 device: torch.device):
+                 device: torch.device, policy_width: int | None = None, pi_slot_cap: int | None = None,
+                 pi_pool_cap: int | None = None):
         init = init_row.reshape(-1).contiguous().view(torch.uint8)
         if init.numel() % 8:
             raise ValueError("row size must be a multiple of 8 bytes")
+        if policy_width is not None and policy_width not in self.PI_STRIDE:
+            raise ValueError(f"policy_width must be 7 or 4096 (got {policy_width})")
         self.n, self.W, self.max_len, self.dev = n_slots, init.numel() // 8, max_len, device
+        self.policy_width = policy_width
+        if policy_width is not None:
+            self.pi_stride = self.PI_STRIDE[policy_width]
+            self.pi_slot_cap = int(pi_slot_cap) if pi_slot_cap is not None else (max_len - 1) * self.pi_stride
+            self.pi_pool_cap = int(pi_pool_cap) if pi_pool_cap is not None else pool_cap * min(self.pi_stride, 32)
+            self.slot_pi = torch.zeros((n_slots, self.pi_slot_cap), dtype=torch.int32, device=device)
+            self.slot_off = torch.zeros((n_slots, max_len + 1), dtype=torch.int32, device=device)
+            self.slot_base = torch.zeros(n_slots, dtype=torch.int64, device=device)
+            self.pctl = torch.zeros(4, dtype=torch.int64, device=device)
         self.init = init.view(torch.int64).to(device).clone()
         self.hist = torch.zeros((n_slots, max_len, self.W), dtype=torch.int64, device=device)
         self.hmoves = torch.zeros((n_slots, max_len), dtype=torch.int16, device=device)
@@ -120,30 +165,62 @@ class Trajectories:
                      ("d_ctl", self.ctl), ("d_init", self.init)):
             setattr(b, f, t.data_ptr())
         self._buf = b
+        if self.policy_width is not None:
+            self._alloc_pi(self.pi_pool_cap)
 
-    def _grow_pool(self, games_cap: int, pool_cap: int):
-        """A larger pool holding the positions and game records reserved so far."""
+    def _alloc_pi(self, pi_pool_cap: int):
+        """The pooled policy entries and each pooled position's (first, count); the per-slot
+        history keeps its buffers."""
+        self.pi_pool_cap = int(pi_pool_cap)
+        self.pool_pi = torch.zeros(self.pi_pool_cap, dtype=torch.int32, device=self.dev)
+        self.pool_first = torch.zeros(self.pool_cap, dtype=torch.int64, device=self.dev)
+        self.pool_count = torch.zeros(self.pool_cap, dtype=torch.int32, device=self.dev)
+        q = _native.TrajPolicyBuffers()
+        q.slot_cap, q.pi_pool_cap = self.pi_slot_cap, self.pi_pool_cap
+        for f, t in (("d_slot_pi", self.slot_pi), ("d_slot_off", self.slot_off), ("d_slot_base", self.slot_base),
+                     ("d_pool_pi", self.pool_pi), ("d_pool_first", self.pool_first),
+                     ("d_pool_count", self.pool_count), ("d_pctl", self.pctl)):
+            setattr(q, f, t.data_ptr())
+        self._pol = q
+
+    def _grow_pool(self, games_cap: int, pool_cap: int, pi_pool_cap: int | None = None):
+        """A larger pool holding the positions and game records (and policy entries) reserved so far."""
         ctl = self.ctl.cpu().tolist()
         npos, ngames = int(ctl[_native.ZC_TRAJ_POSITIONS]), int(ctl[_native.ZC_TRAJ_GAMES])
         old = (self.pool, self.labels, self.pool_moves, self.games)
+        if self.policy_width is not None:
+            nent = min(int(self.pctl[_native.ZC_TRAJ_PI_ENTRIES]), self.pi_pool_cap)
+            old_pi = (self.pool_pi, self.pool_first, self.pool_count)
+            self.pi_pool_cap = max(self.pi_pool_cap, int(pi_pool_cap or 0))
         self._alloc_pool(games_cap, pool_cap)
         self.pool[:npos] = old[0][:npos]
         self.labels[:npos] = old[1][:npos]
         self.pool_moves[:npos] = old[2][:npos]
         self.games[:ngames] = old[3][:ngames]
+        if self.policy_width is not None:
+            self.pool_pi[:nent] = old_pi[0][:nent]
+            self.pool_first[:npos] = old_pi[1][:npos]
+            self.pool_count[:npos] = old_pi[2][:npos]
 
     def ensure_room(self):
         """Grow the pool (on demand, keeping its contents) so that the next step cannot
         overflow it: a slot's game that finishes at that step has at most its current
         history length + 1 positions, so the worst case is known before the step — far less
-        than quota x max_len.  One small device read; simulate_games calls it per step."""
+        than quota x max_len.  One small device read; simulate_games calls it per step.
+        The policy entries likewise: the live slots' current entry fill plus one row of moves each."""
         act = self.slot[:, 1] >= 0
-        need = torch.stack([(self.slot[:, 0].to(torch.int64) + 1)[act].sum(), act.sum().to(torch.int64)])
-        ctl = self.ctl[[_native.ZC_TRAJ_POSITIONS, _native.ZC_TRAJ_GAMES]]
-        npos, ngames = (int(x) for x in (ctl + need).tolist())
-        if npos > self.pool_cap or ngames > self.games_cap:
-            self._grow_pool(max(ngames, self.games_cap, 2 * self.games_cap if ngames > self.games_cap else 0),
-                            max(npos, self.pool_cap, 2 * self.pool_cap if npos > self.pool_cap else 0))
+        need = [(self.slot[:, 0].to(torch.int64) + 1)[act].sum(), act.sum().to(torch.int64)]
+        ctl = [self.ctl[_native.ZC_TRAJ_POSITIONS], self.ctl[_native.ZC_TRAJ_GAMES]]
+        if self.policy_width is not None:
+            fill = self.slot_off.gather(1, (self.slot[:, :1].to(torch.int64) - 1).clamp(0, self.max_len))[:, 0]
+            need.append((fill.to(torch.int64) + self.pi_stride)[act].sum())
+            ctl.append(self.pctl[_native.ZC_TRAJ_PI_ENTRIES])
+        npos, ngames, *nent = (int(x) for x in (torch.stack(ctl) + torch.stack(need)).tolist())
+        nent = nent[0] if nent else 0
+        if npos > self.pool_cap or ngames > self.games_cap or (nent and nent > self.pi_pool_cap):
+            grow = lambda need, cap: max(need, cap, 2 * cap if need > cap else 0)  # noqa: E731
+            self._grow_pool(grow(ngames, self.games_cap), grow(npos, self.pool_cap),
+                            grow(nent, self.pi_pool_cap) if nent else None)
 
     def start(self, quota: int | None, games_cap: int | None = None):
         """Slot g plays game g (g < quota) or idles; the pool is emptied.  quota None = no
@@ -164,6 +241,9 @@ class Trajectories:
         self.ctl.zero_()
         self.ctl[_native.ZC_TRAJ_NEXT] = min(q, self.n)
         self.ctl[_native.ZC_TRAJ_QUOTA] = q
+        if self.policy_width is not None:
+            self.slot_off.zero_()
+            self.pctl.zero_()
 
     def record(self, d_states: int, moves: torch.Tensor, results: torch.Tensor, flags: torch.Tensor | None = None,
                rep: torch.Tensor | None = None, stream: int = 0):
@@ -171,6 +251,26 @@ class Trajectories:
             self.n, ctypes.byref(self._buf), ctypes.c_void_p(d_states), ctypes.c_void_p(moves.data_ptr()),
             ctypes.c_void_p(results.data_ptr()), ctypes.c_void_p(flags.data_ptr() if flags is not None else None),
             ctypes.c_void_p(rep.data_ptr() if rep is not None else None), ctypes.c_void_p(stream or None)))
+        if self.policy_width is not None:   # the finished games' visit counts follow them into the pool
+            _native.check(_native.lib().zc_traj_policy_commit_async(
+                self.n, ctypes.byref(self._buf), ctypes.byref(self._pol), ctypes.c_void_p(stream or None)))
+
+    def record_policy(self, na: torch.Tensor, root_moves: torch.Tensor | None = None, stream: int = 0):
+        """After a step's search, before its play and record(): the root visit counts
+        na [n, stride] int32 (d_out_root_na) of the positions searched; chess passes the roots'
+        legal-move lists [n, stride] (zc_chess_legal_moves_async), Connect4 nothing (index =
+        column)."""
+        if self.policy_width is None:
+            raise ValueError("this pool records no visit counts (policy_width=None)")
+        if tuple(na.shape) != (self.n, self.pi_stride) or na.dtype != torch.int32 or not na.is_contiguous():
+            raise ValueError(f"na must be a contiguous int32 [{self.n}, {self.pi_stride}] tensor")
+        if root_moves is not None and (tuple(root_moves.shape) != tuple(na.shape) or root_moves.element_size() != 2
+                                       or not root_moves.is_contiguous()):
+            raise ValueError("root_moves must be a contiguous 16-bit tensor of na's shape")
+        _native.check(_native.lib().zc_traj_policy_append_async(
+            self.n, ctypes.byref(self._buf), ctypes.byref(self._pol), ctypes.c_void_p(na.data_ptr()),
+            ctypes.c_void_p(root_moves.data_ptr() if root_moves is not None else None), self.pi_stride,
+            ctypes.c_void_p(stream or None)))
 
     def record_steps(self, d_states: int, moves: torch.Tensor, results: torch.Tensor, steps: int,
                      reached: torch.Tensor | None = None, stream: int = 0):
@@ -179,6 +279,8 @@ class Trajectories:
         k < *reached are read.  Needs the unlimited quota."""
         if self.quota != _UNLIMITED:
             raise ValueError("multi-step recording needs the unlimited quota (start(None))")
+        if self.policy_width is not None:
+            raise ValueError("the multi-step launches export no per-move visit counts: record the policy with step()")
         need = ctypes.c_int64(0)
         _native.check(_native.lib().zc_traj_steps_scratch_bytes(self.n, int(steps), ctypes.byref(need)))
         if getattr(self, "_scratch", None) is None or self._scratch.numel() < need.value:
@@ -193,7 +295,7 @@ class Trajectories:
         """Games finished since start() (one device read); raises at once if the pool has
         overflowed (a game was dropped), rather than at take()."""
         fin, ov = (int(x) for x in self.ctl[[_native.ZC_TRAJ_FINISHED, _native.ZC_TRAJ_OVERFLOW]].tolist())
-        if ov:
+        if ov or (self.policy_width is not None and int(self.pctl[_native.ZC_TRAJ_PI_OVERFLOW])):
             self.take()   # raises with the overflow's cause
         return fin
 
@@ -207,6 +309,16 @@ class Trajectories:
                                + ("a game longer than max_len " if ctl[_native.ZC_TRAJ_OVERFLOW] & 2 else "")
                                + ("the quota ran out inside a multi-step record" if ctl[_native.ZC_TRAJ_OVERFLOW] & 4
                                   else ""))
+        if self.policy_width is not None:
+            pov = int(self.pctl[_native.ZC_TRAJ_PI_OVERFLOW])
+            if pov:
+                raise RuntimeError("policy record overflow: "
+                                   + (f"a game's visit counts exceeded pi_slot_cap ({self.pi_slot_cap} entries) "
+                                      if pov & 1 else "")
+                                   + (f"entry pool full (take() more often or raise pi_pool_cap, {self.pi_pool_cap}) "
+                                      if pov & 2 else "")
+                                   + (f"a visit count above {_native.ZC_TRAJ_PI_MAX_COUNT} saturated"
+                                      if pov & 4 else ""))
         k, n = int(ctl[_native.ZC_TRAJ_GAMES]), int(ctl[_native.ZC_TRAJ_POSITIONS])
         g = self.games[:k]
         order = torch.argsort(g[:, 0])
@@ -216,6 +328,13 @@ class Trajectories:
         idx = torch.repeat_interleave(g[:, 2] - starts, lens, output_size=n) + torch.arange(n, device=self.dev)
         games = torch.stack([g[:, 0], g[:, 1] >> 32, (g[:, 1] & 0xFFFFFFFF) - 1, starts, lens], dim=1)
         out = TrajBatch(self.pool[idx].clone(), self.labels[idx].clone(), self.pool_moves[idx].clone(), games)
+        if self.policy_width is not None:   # the entries re-based to the batch's row order
+            cnt = self.pool_count[idx].to(torch.int64)
+            out.pi_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.dev), torch.cumsum(cnt, 0)])
+            total = int(out.pi_off[-1])
+            src = torch.repeat_interleave(self.pool_first[idx] - out.pi_off[:-1], cnt, output_size=total)
+            out.pi = self.pool_pi[src + torch.arange(total, device=self.dev)]
+            self.pctl[_native.ZC_TRAJ_PI_ENTRIES] = 0
         self.ctl[_native.ZC_TRAJ_POSITIONS] = 0
         self.ctl[_native.ZC_TRAJ_GAMES] = 0
         return out
@@ -235,6 +354,30 @@ def _room(traj, stream: int | None = None):
         return
     with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=traj.dev)):
         traj.ensure_room()
+
+
+def _check_record_policy(record_policy: bool, sims: int, record: bool = True):
+    """A policy entry's count field is 16 bits, and the entries ride on the trajectories."""
+    if not record_policy:
+        return
+    if sims > _native.ZC_TRAJ_PI_MAX_COUNT:
+        raise ValueError(f"record_policy stores visit counts in 16 bits: sims {sims} > {_native.ZC_TRAJ_PI_MAX_COUNT}")
+    if not record:
+        raise ValueError("record_policy needs the trajectory recorder (record=True)")
+
+
+_NO_FUSED_POLICY = ("the fused multi-step launches export no per-move visit counts: with record_policy=True "
+                    "play with step()")
+
+
+def _adopt_policy(t: "Trajectories", o: "Trajectories"):
+    """adopt(): the games in progress bring their recorded visit counts along."""
+    if t.policy_width is None:
+        return
+    if o.policy_width != t.policy_width or o.pi_slot_cap != t.pi_slot_cap:
+        raise ValueError("adopt() with record_policy needs a pool recording the policy with the same pi_slot_cap")
+    t.slot_pi.copy_(o.slot_pi)
+    t.slot_off.copy_(o.slot_off)
 
 
 def _warm(search, fn, sims: int):
@@ -264,7 +407,12 @@ class C4SelfPlay:
 
     def __init__(self, games: int, sims: int, c: float = 1.4, batch_size: int = 32, seed: int = 0,
                  rank: int = 0, device: int = 0, record: bool = True, games_cap: int | None = None,
-                 net=None, puct_net=None, temperature: float = 1.0, puct_seed: int = 1, streams: int = 1):
+                 net=None, puct_net=None, temperature: float = 1.0, puct_seed: int = 1, streams: int = 1,
+                 record_policy: bool = False, pi_slot_cap: int | None = None, pi_pool_cap: int | None = None):
+        """record_policy: every step()'s root visit counts go with the positions into the
+        trajectories (TrajBatch.pi / policy_targets(7)), in every search mode."""
+        _check_record_policy(record_policy, sims, record)
+        self.record_policy = bool(record_policy)
         self.G, self.sims, self.c, self.bs = games, sims, c, batch_size
         self.dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.eng = _native.NativeEngine(max_games=games, max_sims=sims, max_batch=batch_size,
@@ -282,7 +430,8 @@ class C4SelfPlay:
         if record:
             cap = games_cap or max(8 * games, 1024)
             self.traj = Trajectories(games, torch.zeros(24, dtype=torch.uint8), self.MAX_LEN, cap,
-                                     cap * self.MAX_LEN, self.dev)
+                                     cap * self.MAX_LEN, self.dev, policy_width=7 if record_policy else None,
+                                     pi_slot_cap=pi_slot_cap, pi_pool_cap=pi_pool_cap)
         self.totals = torch.zeros(2, dtype=torch.int64, device=self.dev)   # expansions, depth sum since reset
         self.carry_pending = False   # run_pooled(carry=True) left moves in flight (drain() finishes them)
         self.vs = self.value_fn = self.ps = self.net_fn = None
@@ -327,6 +476,8 @@ class C4SelfPlay:
         as `moves` calls of step().  Needs the unlimited quota (start(None)): with a quota the
         refill depends on other slots' finishes, which step() decides once per step.
         Returns the per-step results [moves, G]; self.stats sums the moves' counters."""
+        if self.record_policy:
+            raise ValueError(_NO_FUSED_POLICY)
         if self.traj is not None and self.traj.quota != _UNLIMITED:
             raise ValueError("run() plays without a game quota; use step() under simulate_games' quota")
         if self.vs is not None or self.ps is not None:
@@ -361,6 +512,8 @@ class C4SelfPlay:
         stop at their next flush and carry over — the next run()/run_pooled() resumes them
         first; drain() finishes them; step() and the lockstep searches refuse until then.
         Returns the per-step results [moves_cap, G]; self.stats sums the launch's counters."""
+        if self.record_policy:
+            raise ValueError(_NO_FUSED_POLICY)
         if self.traj is not None and self.traj.quota != _UNLIMITED:
             raise ValueError("run_pooled() plays without a game quota; use step() under simulate_games' quota")
         if self.vs is not None or self.ps is not None:
@@ -399,14 +552,17 @@ class C4SelfPlay:
         s = stream if stream is not None else torch.cuda.current_stream(self.dev).cuda_stream
         if self.ps is not None or self.vs is not None:
             if self.ps is not None:
-                mv, _, st = self.ps.enqueue(self.roots, self.sims, self.net_fn, temperature=self.temperature)
+                mv, na, st = self.ps.enqueue(self.roots, self.sims, self.net_fn, temperature=self.temperature)
             else:
-                mv, _, st = self.vs.enqueue(self.roots, self.sims, self.c, self.value_fn)
+                mv, na, st = self.vs.enqueue(self.roots, self.sims, self.c, self.value_fn)
             self.moves.copy_(mv)
             self.stats.copy_(st)
         else:
+            na = self.na
             self.eng.c4_search_async(self.roots.data_ptr(), self.G, self.sims, self.c, self.bs,
                                      self.moves.data_ptr(), self.na.data_ptr(), self.stats.data_ptr(), stream=s)
+        if self.record_policy:   # the visit counts of the positions searched, before they are played
+            self.traj.record_policy(na, stream=s)
         self.totals += self.stats[:, :2].sum(0)
         return self.results
 
@@ -423,6 +579,7 @@ class C4SelfPlay:
             t.hmoves.copy_(o.hmoves)
             t.slot.copy_(o.slot)
             t.ctl[_native.ZC_TRAJ_NEXT] = o.ctl[_native.ZC_TRAJ_NEXT]
+            _adopt_policy(t, o)
 
     def capture_step(self):
         """One whole step (search with its network, play, record) as a HIP graph; each
@@ -448,7 +605,13 @@ class C4SelfPlay:
         self.eng.c4_play_async(self.roots.data_ptr(), self.G, self.moves.data_ptr(), self.results.data_ptr(),
                                reset=not self.record, stream=s)
         if self.record:
-            self.moves16.copy_(self.moves)
+            # on the step's own stream: the copy reads the search's moves and feeds the record
+            # kernel, both enqueued on s (torch's current stream would race with a side stream)
+            if s == torch.cuda.current_stream(self.dev).cuda_stream:
+                self.moves16.copy_(self.moves)
+            else:
+                with torch.cuda.stream(torch.cuda.ExternalStream(s, device=self.dev)):
+                    self.moves16.copy_(self.moves)
             self.traj.record(self.roots.data_ptr(), self.moves16, self.results, stream=s)
         return self.results
 
@@ -510,7 +673,12 @@ class ChessSelfPlay:
                  rank: int = 0, device: int = 0, policy: int = _native.ZC_POLICY_IMMEDIATE_VALUE,
                  freedom: float = 3.0, net=None, init_fen: str | None = None, games_cap: int | None = None,
                  hist_cap: int = 1024, puct_net=None, temperature: float = 1.0, puct_seed: int = 1,
-                 puct_streams: int = 1, streams: int = 1):
+                 puct_streams: int = 1, streams: int = 1, record_policy: bool = False,
+                 pi_slot_cap: int | None = None, pi_pool_cap: int | None = None):
+        """record_policy: every step()'s root visit counts go with the positions into the
+        trajectories (TrajBatch.pi / policy_targets(4096)), in every search mode."""
+        _check_record_policy(record_policy, sims)
+        self.record_policy = bool(record_policy)
         self.G, self.sims, self.c, self.bs = games, sims, c, batch_size
         self.policy, self.freedom = int(policy), float(freedom)
         self.dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
@@ -557,7 +725,14 @@ class ChessSelfPlay:
         self._pb = b
         max_len = 2 * self.hist_cap + 1
         cap = games_cap or max(8 * games, 1024)
-        self.traj = Trajectories(games, self.init_row[0], max_len, cap, cap * 160, self.dev)
+        if record_policy and pi_slot_cap is None:   # a position has at most min(sims, 256) visited moves
+            pi_slot_cap = (max_len - 1) * min(sims, _native.CHESS_MAX_MOVES)
+        self.traj = Trajectories(games, self.init_row[0], max_len, cap, cap * 160, self.dev,
+                                 policy_width=4096 if record_policy else None, pi_slot_cap=pi_slot_cap,
+                                 pi_pool_cap=pi_pool_cap)
+        if record_policy:
+            self.root_moves = torch.zeros((games, _native.CHESS_MAX_MOVES), dtype=torch.int16, device=self.dev)
+            self.root_counts = torch.zeros(games, dtype=torch.int32, device=self.dev)
 
     def start(self, quota: int | None = None):
         self.roots.copy_(self.init_row.expand_as(self.roots))
@@ -573,17 +748,21 @@ class ChessSelfPlay:
         _room(self.traj, stream)
         s = self._stream(stream)
         if self.ps is not None:
-            mv, _, st = self.ps.enqueue(self.roots, self.sims, self.net_fn, temperature=self.temperature)
+            mv, na, st = self.ps.enqueue(self.roots, self.sims, self.net_fn, temperature=self.temperature)
         elif self.vs is not None:
-            mv, _, st = self.vs.enqueue(self.roots, self.sims, self.c, self.value_fn)
+            mv, na, st = self.vs.enqueue(self.roots, self.sims, self.c, self.value_fn)
         else:
             self.eng.chess_search_async(0, self.G, self.roots.data_ptr(), self.sims, self.c, self.bs, self.policy,
                                         self.freedom, self.moves.data_ptr(), self.na.data_ptr(),
                                         self.stats.data_ptr(), s)
-            mv, st = self.moves, self.stats
+            mv, na, st = self.moves, self.na, self.stats
         if mv is not self.moves:
             self.moves.copy_(mv)
             self.stats.copy_(st)
+        if self.record_policy:   # the roots' move lists name the visit counts' moves, before the play
+            self.eng.chess_legal_moves_async(self.G, self.roots.data_ptr(), self.root_moves.data_ptr(),
+                                             self.root_counts.data_ptr(), s)
+            self.traj.record_policy(na, self.root_moves, stream=s)
         _native.check(_native.lib().zc_chess_play_step_async(
             self.G, ctypes.byref(self._pb), ctypes.c_void_p(self.moves.data_ptr()),
             ctypes.c_void_p(self.stats.data_ptr()), ctypes.c_void_p(self.post.data_ptr()),
@@ -605,6 +784,7 @@ class ChessSelfPlay:
         t.hmoves.copy_(o.hmoves)
         t.slot.copy_(o.slot)
         t.ctl[_native.ZC_TRAJ_NEXT] = o.ctl[_native.ZC_TRAJ_NEXT]
+        _adopt_policy(t, o)
 
     def capture_step(self):
         """One whole step (search with its network, play, record) as a HIP graph; each
@@ -644,6 +824,8 @@ class ChessSelfPlay:
         return self._launch(moves_cap, budget, stream, kernel_done)
 
     def _launch(self, moves, budget, stream, kernel_done):
+        if self.record_policy:
+            raise ValueError(_NO_FUSED_POLICY)
         if self.vs is not None or self.ps is not None:
             raise ValueError("run()/run_pooled() fuse the crude-score search; network modes step()")
         if self.traj.quota != _UNLIMITED:
