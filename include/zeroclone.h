@@ -520,6 +520,23 @@ int zc_c4_puct_backup_ex(zc_engine *eng, int32_t first_game, int32_t n_games, in
                          const void *d_logits, int32_t logits_dtype, int32_t rows_per_game, void *hip_stream);
 int zc_c4_puct_end(zc_engine *eng, int32_t first_game, int32_t n_games, float temperature, int32_t *d_out_move,
                    int32_t *d_out_root_na, float *d_out_root_prior, zc_game_stats *d_out_stats, void *hip_stream);
+/* Tree reuse.  zc_c4_puct_begin that keeps, per game, the subtree of d_roots[i] when the game's
+ * previous finished search (run to zc_c4_puct_end with status 0, not forgotten since) holds
+ * that position one or two plies below its root: the first such node in slot order, children
+ * before grandchildren, evaluated and not terminal.  The kept nodes are renumbered in creation
+ * order (the new root is node 0) with their N, W and P bit for bit; Dirichlet noise is mixed
+ * into the kept root's priors as into a fresh root's.  Flush 0 of a reused search has no leaf
+ * (counts = 0), so it adds sims - 1 visits below the root's kept ones and reports
+ * leaves = sims - 1.  The same position again, no such node, or kept + sims - 1 > max_sims + 1
+ * nodes: the game starts afresh, exactly as under zc_c4_puct_begin (never a capacity error).
+ * d_kept[i] (may be NULL) = nodes kept, 0 = started afresh. */
+int zc_c4_puct_begin_reuse(zc_engine *eng, int32_t first_game, int32_t n_games, const zc_c4_state *d_roots,
+                           int32_t sims, double c_puct, int32_t batch_size, float dirichlet_alpha,
+                           float dirichlet_eps, uint64_t seed, int32_t *d_search_no, int32_t *d_kept,
+                           void *hip_stream);
+/* Stream-ordered: the games' kept trees are dropped; their next search starts afresh
+ * (new network weights, restarted games). */
+int zc_c4_puct_forget(zc_engine *eng, int32_t first_game, int32_t n_games, void *hip_stream);
 /* Test hook: game `game`'s Connect4 PUCT tree as raw 192-byte node records (stones X/O, move
  * order word, turn, #moves, evaluated, won, parent, parent slot, depth, children[8], N[8],
  * P[8] float, W[8] double); *out_count = nodes.  Synchronises the device. */

@@ -17,6 +17,9 @@
 //           takes W += 1 - r with r = the leaf value, alternating in sign (N already
 //           counted); a terminal leaf's value is -1 (the side to move has lost) or 0;
 //   root    flush 0 evaluates the root alone.
+//   reuse   (opt-in, zc_c4_puct_begin_reuse) the subtree of the position now at the root, one
+//           or two plies below the last search's root, is compacted in place into the next
+//           tree; such a search has no flush-0 leaf and adds sims - 1 visits.
 //
 // Node = one 192-byte record, slot k (a move, in the node's move-list order) in lane k:
 // everything a selection step reads is one coalesced load per field.  One wave per game.
@@ -31,7 +34,9 @@ namespace {
 
 static_assert(sizeof(C4PNode) == 192, "C4PNode is 192 bytes");
 
-enum : int { pNodes = 0, pStatus = 1, pNb = 2, pExp = 3, pDepth = 4 };
+// pDone: the game's last search ran to end with status 0 (its tree may be re-rooted);
+// pReused: the search in progress started from a kept subtree (flush 0 has no leaf)
+enum : int { pNodes = 0, pStatus = 1, pNb = 2, pExp = 3, pDepth = 4, pDone = 5, pReused = 6 };
 
 __device__ __forceinline__ C4PNode *pnodes(const C4PuctParams &p, int g) { return p.nodes + (size_t)g * p.M; }
 
@@ -94,7 +99,178 @@ __global__ __launch_bounds__(64) void c4_puct_begin_kernel(C4PuctParams p) {
         ctl[pNb] = 0;
         ctl[pExp] = 0;
         ctl[pDepth] = 0;
+        ctl[pDone] = 0;
+        ctl[pReused] = 0;
     }
+}
+
+// ---- tree reuse: the subtree of the position now at the root becomes the next tree ----
+// Node ids are in creation order (a parent's id is below its child's), so one ascending pass
+// over the ids decides which nodes descend from the new root and numbers them, a second one
+// moves the records down in place (new id <= old id, and a chunk's stores land only on
+// records that this or an earlier chunk has already loaded), and a third renumbers the moved
+// records' parent and child links.
+
+// The node holding (s0, s1, turn) one ply below the old root, else two plies below it; the
+// first in slot order (slot of the child, then slot of the grandchild), or -1.
+__device__ int reroot_find(const C4PNode *T, int n, uint64_t s0, uint64_t s1, int turn) {
+    const uint32_t lane = lane_id();
+    const int nm0 = uni((int)T[0].nmoves);
+    auto holds = [&](int id) {
+        return id > 0 && id < n && T[id].s0 == s0 && T[id].s1 == s1 && (int)T[id].turn == turn;
+    };
+    const int c1 = (int)lane < min(nm0, kSlots) ? (int)T[0].child[lane] : 0xFFFF;
+    uint64_t hit = __ballot(holds(c1));
+    if (hit) return __builtin_amdgcn_readlane(c1, __builtin_ctzll(hit));
+    const int c = __shfl(c1, (int)(lane >> 3));  // lane = child slot * 8 + grandchild slot
+    int c2 = 0xFFFF;
+    if (c > 0 && c < n && (int)(lane & 7u) < (int)T[c].nmoves) c2 = (int)T[c].child[lane & 7u];
+    hit = __ballot(holds(c2));
+    if (hit) return __shfl(c2, __builtin_ctzll(hit));
+    return -1;
+}
+
+// Pass 1: remap[i] = the new id of node i of r's subtree, 0xFFFF for any other node i >= r
+// (ids below r are never kept and never looked up).  Returns the number of nodes kept.
+__device__ int reroot_number(const C4PNode *T, uint16_t *remap, int n, int r) {
+    const uint32_t lane = lane_id();
+    int cnt = 0;
+    for (int base = r; base < n; base += 64) {
+        const int i = base + (int)lane;
+        const bool valid = i < n;
+        const int par = valid ? (int)T[i].parent : 0xFFFF;
+        // a parent in an earlier chunk: its entry is final
+        bool k = valid && (i == r || (par >= r && par < base && remap[par] != 0xFFFF));
+        const bool inpar = valid && par >= base && par < i;
+        const int pl = inpar ? par - base : 0;  // the parent's lane
+        uint64_t b = __ballot(k);
+        for (;;) {  // parents in this chunk: at most one round per level of the tree
+            k = k || (inpar && ((b >> pl) & 1ull));
+            const uint64_t nb = __ballot(k);
+            if (nb == b) break;
+            b = nb;
+        }
+        const int id = cnt + __popcll(b & ((1ull << lane) - 1ull));
+        if (valid) remap[i] = k ? (uint16_t)id : (uint16_t)0xFFFF;
+        cnt += __popcll(b);
+        wave_mem_order();
+        __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next chunk's lanes read these entries
+    }
+    return cnt;
+}
+
+// Pass 2: the kept records move to their new ids, 64 ids a chunk as 12 x 64 16-byte pieces.
+__device__ void reroot_move(C4PNode *T, const uint16_t *remap, int n, int r) {
+    const uint32_t lane = lane_id();
+    constexpr int kPieces = (int)sizeof(C4PNode) / 16;
+    for (int base = r; base < n; base += 64) {
+        const int rows = min(64, n - base);
+        const uint4 *src = reinterpret_cast<const uint4 *>(T + base);
+        uint4 v[kPieces];
+        uint32_t dst[kPieces];
+#pragma unroll
+        for (int it = 0; it < kPieces; ++it) {
+            const int q = it * 64 + (int)lane, rec = q / kPieces;
+            const bool valid = rec < rows;
+            v[it] = valid ? src[q] : make_uint4(0, 0, 0, 0);
+            dst[it] = valid ? (uint32_t)remap[base + rec] : 0xFFFFu;
+        }
+        // every load of the chunk has returned before any of its stores is issued
+        wave_mem_order();
+        __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int it = 0; it < kPieces; ++it)
+            if (dst[it] != 0xFFFFu) reinterpret_cast<uint4 *>(T + dst[it])[(it * 64 + (int)lane) % kPieces] = v[it];
+        wave_mem_order();
+    }
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// Pass 3: the moved records' links, one node a lane: parent and children through the table
+// (they still hold old ids, all >= r: a kept node's parent and children are kept), depth
+// counted from the new root.  Piece 1 of a record holds parent / pact / depth, piece 2 its
+// eight children; the nine table reads of a node are independent loads.
+__device__ void reroot_link(C4PNode *T, const uint16_t *remap, int kept, int n, int r, int rdepth) {
+    for (int id = (int)lane_id(); id < kept; id += 64) {
+        uint4 *rec = reinterpret_cast<uint4 *>(T + id);
+        const uint32_t link = rec[1].z;
+        const uint4 ch = rec[2];
+        const uint32_t old[9] = {ch.x & 0xFFFFu, ch.x >> 16, ch.y & 0xFFFFu, ch.y >> 16, ch.z & 0xFFFFu,
+                                 ch.z >> 16,     ch.w & 0xFFFFu, ch.w >> 16, link & 0xFFFFu};
+        uint32_t now[9];
+#pragma unroll
+        for (int h = 0; h < 9; ++h) {
+            const bool in = old[h] >= (uint32_t)r && old[h] < (uint32_t)n;
+            const uint32_t m = remap[in ? old[h] : (uint32_t)r];  // always a valid entry: no branch around the load
+            now[h] = in ? m : 0xFFFFu;
+        }
+        rec[2] = make_uint4(now[0] | (now[1] << 16), now[2] | (now[3] << 16), now[4] | (now[5] << 16),
+                            now[6] | (now[7] << 16));
+        const uint32_t pact = (link >> 16) & 0xFFu, dep = link >> 24;
+        reinterpret_cast<uint32_t *>(rec + 1)[2] =
+            id == 0 ? 0x00FFFFFFu : now[8] | (pact << 16) | ((dep - (uint32_t)rdepth) << 24);
+    }
+    wave_mem_order();
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+__global__ __launch_bounds__(64) void c4_puct_reroot_kernel(C4PuctParams p) {
+    const int gl = blockIdx.x;
+    if (gl >= p.n_games) return;
+    const int g = p.first_game + gl;
+    const zc_c4_state root = p.roots[gl];
+    const uint64_t s0 = uni64(root.stones[0]), s1 = uni64(root.stones[1]);
+    const int turn = uni(root.turn);
+    int32_t *ctl = p.ctl + (size_t)g * kCtlWords;
+    C4PNode *T = pnodes(p, g);
+    uint16_t *remap = p.remap + (size_t)g * p.M;
+    const uint32_t lane = lane_id();
+    int status = 0, kept = 0;
+    if (!valid_state(s0, s1, turn)) {
+        status = ZC_STATUS_BAD_STATE;
+    } else {
+        const int n = uni(ctl[pNodes]);
+        int r = -1;
+        if (uni(ctl[pDone]) == 1 && n >= 2 && n <= p.M) r = uni(reroot_find(T, n, s0, s1, turn));
+        if (r > 0 && (!uni((int)T[r].evaluated) || uni((int)T[r].nmoves) == 0)) r = -1;
+        if (r > 0) {
+            kept = reroot_number(T, remap, n, r);
+            if (kept + p.sims - 1 > p.M) kept = 0;  // no room for this search's nodes: start afresh
+        }
+        if (kept) {
+            const int rdepth = uni((int)T[r].depth);
+            reroot_move(T, remap, n, r);
+            reroot_link(T, remap, kept, n, r, rdepth);
+            if (p.dir_eps > 0.0f) {  // the fresh path's root noise (backup kernel), on the kept priors
+                const uint2 key = make_uint2((uint32_t)p.seed, (uint32_t)(p.seed >> 32));
+                const bool valid = (int)lane < uni((int)T[0].nmoves);
+                float pr = valid ? T[0].pr[lane] : 0.0f;
+                const float gm = valid ? gamma_draw(p.dir_alpha, key, (uint32_t)g, lane, search_number(p, gl)) : 0.0f;
+                const float gs = wave_sum_f(gm);
+                pr = (1.0f - p.dir_eps) * pr + p.dir_eps * (gs > 0.0f ? gm / gs : 0.0f);
+                if (valid) T[0].pr[lane] = pr;
+            }
+        } else {
+            pnode_init(T, s0, s1, turn, 0xFFFF, 0xFF, 0);
+            wave_mem_order();
+            if (uni((int)T->nmoves) == 0) status = ZC_STATUS_NO_MOVES;
+        }
+    }
+    if (lane == 0) {
+        ctl[pNodes] = kept ? kept : 1;
+        ctl[pStatus] = status;
+        ctl[pNb] = 0;
+        ctl[pExp] = 0;
+        ctl[pDepth] = 0;
+        ctl[pDone] = 0;
+        ctl[pReused] = kept ? 1 : 0;
+        if (p.out_kept) p.out_kept[gl] = kept;
+    }
+}
+
+__global__ void c4_puct_forget_kernel(C4PuctParams p) {
+    const int gl = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gl < p.n_games) p.ctl[(size_t)(p.first_game + gl) * kCtlWords + pDone] = 0;
 }
 
 // One PUCT walk + expansion; returns the leaf and its depth, the edges of its path in lanes
@@ -172,6 +348,7 @@ __global__ __launch_bounds__(64) void c4_puct_select_kernel(C4PuctParams p) {
     const uint32_t lane = lane_id();
     int status = uni(ctl[pStatus]);
     int nb = status ? 0 : pflush_leaves(p, p.flush);
+    if (p.flush == 0 && uni(ctl[pReused])) nb = 0;  // a kept root is evaluated already
     int nnodes = uni(ctl[pNodes]);
     uint32_t *paths = p.paths + (size_t)g * p.max_batch * kMaxDepth;
     uint32_t *meta = p.meta + (size_t)g * p.max_batch;
@@ -285,7 +462,7 @@ __global__ __launch_bounds__(64) void c4_puct_end_kernel(C4PuctParams p) {
     if (gl >= p.n_games) return;
     const int g = p.first_game + gl;
     const C4PNode *R = pnodes(p, g);
-    const int32_t *ctl = p.ctl + (size_t)g * kCtlWords;
+    int32_t *ctl = p.ctl + (size_t)g * kCtlWords;
     const uint32_t lane = lane_id();
     const uint32_t k = lane & 7u;
     const int status = uni(ctl[pStatus]);
@@ -329,8 +506,9 @@ __global__ __launch_bounds__(64) void c4_puct_end_kernel(C4PuctParams p) {
         st.status = status;
         st.expansions = ctl[pExp];
         st.depth_sum = ctl[pDepth];
-        st.leaves = p.sims;
+        st.leaves = ctl[pReused] ? p.sims - 1 : p.sims;
         p.out_stats[gl] = st;
+        ctl[pDone] = status == 0 ? 1 : 0;
     }
 }
 
@@ -338,6 +516,12 @@ __global__ __launch_bounds__(64) void c4_puct_end_kernel(C4PuctParams p) {
 
 void launch_c4_puct_begin(const C4PuctParams &p, hipStream_t s) {
     hipLaunchKernelGGL(c4_puct_begin_kernel, dim3(p.n_games), dim3(64), 0, s, p);
+}
+void launch_c4_puct_reroot(const C4PuctParams &p, hipStream_t s) {
+    hipLaunchKernelGGL(c4_puct_reroot_kernel, dim3(p.n_games), dim3(64), 0, s, p);
+}
+void launch_c4_puct_forget(const C4PuctParams &p, hipStream_t s) {
+    hipLaunchKernelGGL(c4_puct_forget_kernel, dim3((p.n_games + 63) / 64), dim3(64), 0, s, p);
 }
 void launch_c4_puct_select(const C4PuctParams &p, hipStream_t s) {
     hipLaunchKernelGGL(c4_puct_select_kernel, dim3(p.n_games), dim3(64), 0, s, p);

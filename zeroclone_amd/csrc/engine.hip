@@ -361,7 +361,7 @@ int zc_engine_destroy(zc_engine *eng) {
         free_arena(eng);
         free_chess(eng->ca);
         free_gen(eng);
-        void *c4p[] = {eng->c4p_nodes, eng->c4p_ctl, eng->c4p_paths, eng->c4p_meta};
+        void *c4p[] = {eng->c4p_nodes, eng->c4p_ctl, eng->c4p_paths, eng->c4p_meta, eng->c4p_remap};
         for (void *q : c4p)
             if (q) (void)hipFree(q);
         give_stream(eng->cfg.device, eng->stream);
@@ -1540,13 +1540,11 @@ int check_qx(zc_engine *e, int32_t first, int32_t n, int32_t flush, bool need_fl
     if (need_flush && (flush < 0 || flush >= nflush)) return fail(ZC_EINVAL, "flush %d outside [0, %d)", flush, nflush);
     return ZC_OK;
 }
-}  // namespace
-
-extern "C" {
-
-int zc_c4_puct_begin(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state *d_roots, int32_t sims,
-                     double c_puct, int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no,
-                     void *hip_stream) {
+// zc_c4_puct_begin / zc_c4_puct_begin_reuse: the same validation and search parameters; the
+// reuse form launches the re-root kernel in place of the begin kernel.
+int c4p_begin(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state *d_roots, int32_t sims, double c_puct,
+              int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no, bool reuse, int32_t *d_kept,
+              void *hip_stream) {
     if (!eng || (n && !d_roots)) return fail(ZC_EINVAL, "null argument");
     if (int r = check_search(eng, first, n, sims, c_puct, bs)) return r;
     if (sims < 2) return fail(ZC_EINVAL, "PUCT search needs sims >= 2 (flush 0 evaluates the root)");
@@ -1554,6 +1552,8 @@ int zc_c4_puct_begin(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state
     std::lock_guard<std::mutex> lk(eng->mu);
     ZC_HIP(hipSetDevice(eng->cfg.device));
     if (int r = ensure_c4p(eng)) return r;
+    if (reuse && !eng->c4p_remap)
+        if (int r = dalloc(eng, &eng->c4p_remap, (size_t)eng->cfg.max_games * (size_t)eng->M)) return r;
     eng->qx_first = first;
     eng->qx_n = n;
     eng->qx_sims = sims;
@@ -1567,7 +1567,45 @@ int zc_c4_puct_begin(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state
     if (!n) return ZC_OK;
     zc::C4PuctParams p = c4p_params(eng, first, n);
     p.roots = d_roots;
-    zc::launch_c4_puct_begin(p, (hipStream_t)hip_stream);
+    if (reuse) {
+        p.remap = eng->c4p_remap;
+        p.out_kept = d_kept;
+        zc::launch_c4_puct_reroot(p, (hipStream_t)hip_stream);
+    } else {
+        zc::launch_c4_puct_begin(p, (hipStream_t)hip_stream);
+    }
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int zc_c4_puct_begin(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state *d_roots, int32_t sims,
+                     double c_puct, int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no,
+                     void *hip_stream) {
+    return c4p_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, false, nullptr,
+                     hip_stream);
+}
+
+int zc_c4_puct_begin_reuse(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state *d_roots, int32_t sims,
+                           double c_puct, int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no,
+                           int32_t *d_kept, void *hip_stream) {
+    return c4p_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, true, d_kept,
+                     hip_stream);
+}
+
+int zc_c4_puct_forget(zc_engine *eng, int32_t first, int32_t n, void *hip_stream) {
+    if (!eng) return fail(ZC_EINVAL, "null argument");
+    if (int r = check_games(eng, first, n)) return r;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    if (!n || !eng->c4p_nodes) return ZC_OK;  // no tree yet: nothing is kept
+    ZC_HIP(hipSetDevice(eng->cfg.device));
+    zc::C4PuctParams p{};
+    p.first_game = first;
+    p.n_games = n;
+    p.ctl = eng->c4p_ctl;
+    zc::launch_c4_puct_forget(p, (hipStream_t)hip_stream);
     ZC_HIP(hipGetLastError());
     return ZC_OK;
 }

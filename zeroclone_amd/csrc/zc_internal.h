@@ -262,8 +262,12 @@ struct C4PuctParams {
     int32_t *out_na;          // [n][7] visits per column
     float *out_prior;         // [n][7] root priors per column (optional)
     zc_game_stats *out_stats;
+    uint16_t *remap;          // re-root: [G][M] new id of each kept node (scratch)
+    int32_t *out_kept;        // re-root: [n] nodes kept, 0 = started afresh (optional)
 };
 void launch_c4_puct_begin(const C4PuctParams &p, hipStream_t s);
+void launch_c4_puct_reroot(const C4PuctParams &p, hipStream_t s);
+void launch_c4_puct_forget(const C4PuctParams &p, hipStream_t s);
 void launch_c4_puct_select(const C4PuctParams &p, hipStream_t s);
 void launch_c4_puct_backup(const C4PuctParams &p, hipStream_t s);
 void launch_c4_puct_end(const C4PuctParams &p, hipStream_t s);
@@ -421,6 +425,7 @@ struct zc_engine {
     zc::C4PNode *c4p_nodes = nullptr;
     int32_t *c4p_ctl = nullptr;
     uint32_t *c4p_paths = nullptr, *c4p_meta = nullptr;
+    uint16_t *c4p_remap = nullptr;  // [G][M], allocated on the first zc_c4_puct_begin_reuse
     int qx_first = 0, qx_n = 0, qx_sims = 0, qx_bs = 0;
     double qx_c = 0;
     float qx_alpha = 0, qx_eps = 0;

@@ -408,14 +408,28 @@ class C4SelfPlay:
     def __init__(self, games: int, sims: int, c: float = 1.4, batch_size: int = 32, seed: int = 0,
                  rank: int = 0, device: int = 0, record: bool = True, games_cap: int | None = None,
                  net=None, puct_net=None, temperature: float = 1.0, puct_seed: int = 1, streams: int = 1,
-                 record_policy: bool = False, pi_slot_cap: int | None = None, pi_pool_cap: int | None = None):
+                 record_policy: bool = False, pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
+                 reuse_tree: bool = False, tree_nodes: int | None = None):
         """record_policy: every step()'s root visit counts go with the positions into the
-        trajectories (TrajBatch.pi / policy_targets(7)), in every search mode."""
+        trajectories (TrajBatch.pi / policy_targets(7)), in every search mode.
+        reuse_tree (PUCT mode): each search keeps the subtree of the move just played
+        (C4PuctSearch(reuse=True)) and adds sims - 1 visits to it; a tree holds up to
+        `tree_nodes` nodes (default min(2 * sims, 65534)), and a search whose kept nodes leave
+        no room for its own starts afresh.  start() and adopt() drop the kept trees."""
         _check_record_policy(record_policy, sims, record)
+        if reuse_tree:
+            if puct_net is None:
+                raise ValueError("reuse_tree keeps the PUCT search's tree: it needs puct_net")
+            # a kept root carries the visits of every earlier search of its game: at most 42 searches
+            if record_policy and 42 * sims > _native.ZC_TRAJ_PI_MAX_COUNT:
+                raise ValueError(f"record_policy stores visit counts in 16 bits: with reuse_tree a root can hold "
+                                 f"42 * sims = {42 * sims} > {_native.ZC_TRAJ_PI_MAX_COUNT} visits")
+        self.reuse_tree = bool(reuse_tree)
         self.record_policy = bool(record_policy)
         self.G, self.sims, self.c, self.bs = games, sims, c, batch_size
         self.dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        self.eng = _native.NativeEngine(max_games=games, max_sims=sims, max_batch=batch_size,
+        max_sims = (tree_nodes or min(2 * sims, 65534)) if reuse_tree else sims
+        self.eng = _native.NativeEngine(max_games=games, max_sims=max_sims, max_batch=batch_size,
                                         device=self.dev.index or 0)
         self.first_id = rank * games
         self.eng.seed(0, [seed + self.first_id + g for g in range(games)])
@@ -444,7 +458,7 @@ class C4SelfPlay:
                 self.value_fn = [NetValue(net.replica() if hasattr(net, "replica") else net) for _ in range(streams)]
         if puct_net is not None:
             from .valued import C4PuctSearch, PolicyNet
-            self.ps = C4PuctSearch(self.eng, games, batch_size, seed=puct_seed, leaves=False)
+            self.ps = C4PuctSearch(self.eng, games, batch_size, seed=puct_seed, leaves=False, reuse=self.reuse_tree)
             self.net_fn = PolicyNet(puct_net)
             if streams > 1:
                 self.net_fn = [PolicyNet(puct_net.replica()) for _ in range(streams)]
@@ -458,6 +472,8 @@ class C4SelfPlay:
             self.eng.c4_carry_discard(0, self.G, torch.cuda.current_stream(self.dev).cuda_stream)
             self.carry_pending = False
         self.roots.zero_()
+        if self.reuse_tree:
+            self.ps.forget()
         if self.traj is not None:
             self.traj.start(quota, games_cap=quota)
 
@@ -573,6 +589,8 @@ class C4SelfPlay:
         if self.carry_pending:   # its carried searches belong to the roots being replaced
             raise RuntimeError("moves carried over by run_pooled(carry=True) are in flight: drain() first")
         self.roots.copy_(other.roots)
+        if self.reuse_tree:
+            self.ps.forget()
         if self.traj is not None and other.traj is not None:
             t, o = self.traj, other.traj
             t.hist.copy_(o.hist)

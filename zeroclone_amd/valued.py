@@ -412,14 +412,20 @@ class C4PuctSearch:
 
     net_fn(leaves, planes, counts) -> (values fp64 [n*bs], logits [n*bs, 7] fp32/fp16, one per
     column) — e.g. `lambda l, p, c: net(p)` with nets.MfmaPolicyValueNetwork over
-    PolicyValueNetwork(in_planes=2, board=(6, 7), n_logits=7)."""
+    PolicyValueNetwork(in_planes=2, board=(6, 7), n_logits=7).
+
+    reuse=True: every search keeps, per game, the subtree of its root position when the game's
+    previous search holds it one or two plies below its root (zc_c4_puct_begin_reuse), and then
+    adds sims - 1 visits below the kept ones; `kept` [n] int32 = nodes kept (0: a fresh tree).
+    The engine needs max_sims above sims for anything to be kept; forget() drops the trees."""
 
     def __init__(self, eng: "_native.NativeEngine", n_games: int, batch_size: int = 32, c_puct: float = 1.5,
                  dirichlet_alpha: float = 0.3, dirichlet_eps: float = 0.25, seed: int = 0,
-                 planes_dtype: torch.dtype = torch.float16, leaves: bool = True):
+                 planes_dtype: torch.dtype = torch.float16, leaves: bool = True, reuse: bool = False):
         if batch_size > eng.max_batch:
             raise ValueError(f"batch_size {batch_size} > engine max_batch {eng.max_batch}")
         self.eng, self.n, self.bs = eng, n_games, batch_size
+        self.reuse = bool(reuse)
         self.c, self.alpha, self.eps, self.seed = c_puct, dirichlet_alpha, dirichlet_eps, seed
         self.dev = torch.device("cuda", eng.device)
         L = n_games * batch_size
@@ -435,13 +441,27 @@ class C4PuctSearch:
         # the tree arena exists before any graph capture
         z = torch.zeros((1, 3), dtype=torch.int64, device=self.dev)
         eng.c4_puct_begin(0, 0, z.data_ptr(), 2, c_puct, batch_size, dirichlet_alpha, dirichlet_eps, seed)
+        self.kept = None
+        if self.reuse:   # and so does the re-root's scratch
+            self.kept = torch.zeros(n_games, dtype=torch.int32, device=self.dev)
+            eng.c4_puct_begin_reuse(0, 0, z.data_ptr(), 2, c_puct, batch_size, dirichlet_alpha, dirichlet_eps, seed)
+            self.forget()   # trees of an earlier search object on this engine are not this one's
+
+    def forget(self, first_game: int = 0, n: int | None = None):
+        """Drop the kept trees of games [first_game, first_game + n) (default: this search's n
+        games), stream-ordered: their next search starts afresh."""
+        self.eng.c4_puct_forget(first_game, self.n if n is None else n, _stream(self.dev))
 
     def enqueue(self, roots: torch.Tensor, sims: int, net_fn, temperature: float = 0.0, first_game: int = 0):
         e, n = self.eng, self.n
         p = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
         nfl = _native.check(_native.lib().zc_chess_puct_flushes(int(sims), int(self.bs)))
-        e.c4_puct_begin(first_game, n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps, self.seed,
-                        self.search_no.data_ptr(), stream=_stream(self.dev))
+        if self.reuse:
+            e.c4_puct_begin_reuse(first_game, n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps,
+                                  self.seed, self.search_no.data_ptr(), self.kept.data_ptr(), stream=_stream(self.dev))
+        else:
+            e.c4_puct_begin(first_game, n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps, self.seed,
+                            self.search_no.data_ptr(), stream=_stream(self.dev))
         if isinstance(net_fn, (list, tuple)):   # split over streams, as ChessPuctSearch
             def select(first, m, f, lv, pv, cv, s):
                 e.c4_puct_select(first, m, f, lv.data_ptr() if lv is not None else 0, pv.data_ptr(),
