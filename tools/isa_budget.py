@@ -1,0 +1,253 @@
+#!/usr/bin/env python3
+"""Static instruction budget of the Connect4 rollout loop (CPU only: a cross-compile).
+
+    python tools/isa_budget.py [--asm FILE] [--label TEXT]
+
+Compiles zeroclone_amd/csrc/c4_search.hip to gfx950 assembly with build.py's flags (ZC_CFLAGS
+honoured; --asm FILE reads an assembly file made that way instead), finds the rollout loops of
+c4_selfplay_kernel<false> by the win test's ds_permute_b32 + v_permlane32_swap — one test in
+a loop over blocks inside the loop over leaves, or two when a rollout's first block stands in
+the leaf loop itself and the others in a loop of their own — and prints
+
+  * per basic block of the leaf loop: SALU / VALU / LDS / other instruction counts (other =
+    waits, nops, branches, priorities, vector memory), its loop depth and successors;
+  * the sums along three paths, each the cheapest that fits its description:
+      win       leaf prologue -> one block without a fill -> exit to the next leaf
+                (the exit is the cheapest way from the win test to the next leaf that does
+                not start another block: the win exit, which the board-full exit shares or ties)
+      absorbed  the same with one absorbed fill (the block passes two prefix sums)
+      continue  one block without a fill that goes on to another: from one win test round the
+                block loop to the next (told from the exit by its LDS read of the next legal
+                set's order words)
+    (no window advance and no empty view on any of them);
+  * next_free_vgpr and the private segment size of c4_selfplay_kernel<false> and
+    c4_search_kernel<false,false>.
+
+profiles/c4_rollout_isa_budget.txt keeps the output for the code before and after a change.
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+KERNEL = "c4_selfplay_kernelILb0EE"
+ALSO = ["c4_search_kernelILb0ELb0EE"]
+OTHER = ("s_waitcnt", "s_nop", "s_branch", "s_cbranch", "s_setprio", "s_sleep", "s_endpgm", "s_barrier",
+         "s_setpc", "s_sendmsg", "s_trap", "s_inst_prefetch", "s_code_end")
+
+
+def compile_asm(path):
+    from zeroclone_amd import build as zb
+    src = "c4_search.hip"
+    cmd = [zb.hipcc(), f"--offload-arch={zb.ARCH}", *zb.FLAGS, *zb.SOURCE_FLAGS.get(src, []),
+           *os.environ.get("ZC_CFLAGS", "").split(), "--cuda-device-only", "-S",
+           os.path.join(zb.CSRC, src), "-o", path]
+    subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+
+
+def kind(op):
+    if op.startswith(OTHER):
+        return "other"
+    if op.startswith("s_"):
+        return "salu"
+    if op.startswith("v_"):
+        return "valu"
+    if op.startswith("ds_"):
+        return "lds"
+    return "other"
+
+
+class Block:
+    def __init__(self, name):
+        self.name, self.ins, self.succ, self.falls = name, [], [], True
+        self.header_of = None   # depth, when this block heads a loop
+        self.loop = None        # innermost loop header this block is in (its own name for a header)
+        self.parents = {}       # header blocks only: depth -> enclosing header
+
+    def counts(self):
+        c = dict(salu=0, valu=0, lds=0, other=0)
+        for op, _ in self.ins:
+            c[kind(op)] += 1
+        return c
+
+    def n(self):
+        return len(self.ins)
+
+
+def parse_function(lines, key):
+    """Basic blocks of the function whose symbol contains `key`, in layout order."""
+    start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\S*" + re.escape(key) + r"\S*:", l))
+    fn = re.match(r"^(\S+):", lines[start]).group(1)
+    blocks, cur, fnum = [], Block("entry"), None
+    blocks.append(cur)
+    for l in lines[start + 1:]:
+        if l.startswith(".Lfunc_end"):
+            break
+        m = re.match(r"^\.L(BB(\d+)_\d+):(.*)", l) or re.match(r"^; %bb\.(\d+):(.*)", l)
+        if m:
+            if m.re.pattern.startswith(r"^\.L"):
+                name, fnum, rest = m.group(1), m.group(2), m.group(3)
+            else:
+                name, rest = f"BB{fnum if fnum is not None else '?'}_{m.group(1)}", m.group(2)
+            cur = Block(name)
+            blocks.append(cur)
+            h = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=(\d+)", rest)
+            if h:
+                cur.loop = h.group(1)
+            l = rest  # a loop header's comment starts on the label's line
+        s = l.strip()
+        if s.startswith(";"):
+            h = re.search(r"Parent Loop (BB\d+_\d+) Depth=(\d+)", s)
+            if h:
+                cur.parents[int(h.group(2))] = h.group(1)
+            h = re.search(r"This (?:Inner )?Loop Header: Depth=(\d+)", s)
+            if h:
+                cur.header_of = int(h.group(1))
+                cur.loop = cur.name
+            continue
+        if not s or s.startswith(".") or s.endswith(":"):
+            continue
+        op = s.split()[0]
+        cur.ins.append((op, s))
+        if op.startswith(("s_cbranch", "s_branch")):
+            t = s.split()[1]
+            cur.succ.append(t[2:] if t.startswith(".L") else t)
+        if op in ("s_branch", "s_endpgm"):
+            cur.falls = False
+    # "%bb.N" blocks seen before the first label get the function number now
+    for b in blocks:
+        if b.name.startswith("BB?_"):
+            b.name = f"BB{fnum}_" + b.name[4:]
+    for i, b in enumerate(blocks):
+        if b.falls and i + 1 < len(blocks):
+            b.succ.append(blocks[i + 1].name)
+    return fn, blocks
+
+
+def loop_chain(byname, b):
+    """Headers of the loops around block b, innermost first."""
+    out, h = [], b.loop
+    while h:
+        out.append(h)
+        hb = byname[h]
+        h = hb.parents.get(hb.header_of - 1)
+    return out
+
+
+def all_paths(byname, src, dst, allowed):
+    """Simple paths src .. dst (both included; a cycle when they are the same) through `allowed`."""
+    out, stack = [], [(src, [src])]
+    while stack:
+        node, path = stack.pop()
+        for s in byname[node].succ:
+            if s == dst:
+                out.append(path + [s])
+            elif s in allowed and s not in path:
+                stack.append((s, path + [s]))
+    return out
+
+
+def cost(byname, path):
+    return sum(byname[b].n() for b in path)
+
+
+def fmt_counts(byname, path):
+    c = dict(salu=0, valu=0, lds=0, other=0)
+    for b in path:
+        for k, v in byname[b].counts().items():
+            c[k] += v
+    return f"SALU {c['salu']:3d}  VALU {c['valu']:3d}  LDS {c['lds']:2d}  other {c['other']:2d}  total {sum(c.values()):3d}"
+
+
+def has(byname, path, text):
+    return sum(text in s for b in path for _, s in byname[b].ins)
+
+
+def analyse(lines, out):
+    fn, blocks = parse_function(lines, KERNEL)
+    byname = {b.name: b for b in blocks}
+    depth = lambda b: byname[b.loop].header_of if b.loop else 0
+    tests = [b for b in blocks if any(op == "ds_permute_b32" for op, _ in b.ins)
+             and any(op.startswith("v_permlane32_swap") for op, _ in b.ins)]
+    # one win test: a loop over blocks inside the loop over leaves.  Two: a rollout's first
+    # block stands in the leaf loop itself, the others in a loop of their own.
+    P1 = min(tests, key=depth)
+    P2 = max(tests, key=depth)
+    if len(tests) == 1:
+        B, Lh = loop_chain(byname, P1)[:2]
+    else:
+        B, Lh = loop_chain(byname, P2)[0], loop_chain(byname, P1)[0]
+    in_leaf = [b for b in blocks if Lh in loop_chain(byname, b)]
+    print(f"kernel {fn}", file=out)
+    print(f"leaf loop {Lh}, block loop {B}, win test in " + " ".join(t.name for t in tests), file=out)
+    print(f"{'block':<12}{'depth':>5}{'SALU':>6}{'VALU':>6}{'LDS':>5}{'other':>6}{'total':>6}  successors", file=out)
+    for b in in_leaf:
+        c = b.counts()
+        print(f"{b.name:<12}{depth(b):>5}{c['salu']:>6}{c['valu']:>6}{c['lds']:>5}{c['other']:>6}{b.n():>6}  "
+              + " ".join(b.succ), file=out)
+
+    def best(paths, what):
+        if not paths:
+            raise SystemExit(f"isa_budget: no path for {what}")
+        return min(paths, key=lambda p: cost(byname, p))
+
+    # no path advances the window or meets an empty view (the temper's constant marks both)
+    calm = {b.name for b in in_leaf if not has(byname, [b.name], "0x9d2c5680")}
+    testnames = {t.name for t in tests}
+    # leaf header .. win test: the leaf's prologue and one block, by the prefix sums it passes
+    head = all_paths(byname, Lh, P1.name, calm - testnames)
+    nofill = best([p for p in head if has(byname, p, "row_bcast:31") == 1], "block without fill")
+    fill = best([p for p in head if has(byname, p, "row_bcast:31") == 2], "block with an absorbed fill")
+    # after the win test, to the next leaf: going on reads the next legal set's order words
+    # from LDS (and passes another win test), the exit reads nothing
+    quiet = {n for n in calm - testnames if not has(byname, [n], "ds_read")}
+    ex = best([p[1:-1] for p in all_paths(byname, P1.name, Lh, quiet)], "exit")
+    # a block that goes on: the cycle from one win test of the block loop to the next
+    in_loop = {n for n in calm if B in loop_chain(byname, byname[n])}
+    cyc = best([p[1:] for p in all_paths(byname, P2.name, P2.name, in_loop)
+                if has(byname, p[1:], "ds_read") and has(byname, p[1:], "row_bcast:31") == 1], "continue")
+    paths = [("win", nofill + ex), ("absorbed", fill + ex), ("continue", cyc)]
+    print(file=out)
+    for name, parts in (("leaf + block, no fill", nofill), ("leaf + block, absorbed fill", fill),
+                        ("exit to the next leaf", ex), ("block that goes on", cyc)):
+        print(f"part {name:<28}{cost(byname, parts):>4}  " + " ".join(parts), file=out)
+    print(file=out)
+    for name, p in paths:
+        print(f"path {name:<9} {fmt_counts(byname, p)}", file=out)
+    print(file=out)
+    text = "\n".join(lines)
+    res = {name: cost(byname, p) for name, p in paths}
+    for key in [KERNEL] + ALSO:
+        m = re.search(r"\.amdhsa_kernel (\S*" + re.escape(key) + r"\S*)\n(.*?)\.end_amdhsa_kernel", text, re.S)
+        body = m.group(2)
+        vg = re.search(r"\.amdhsa_next_free_vgpr (\d+)", body).group(1)
+        ps = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)
+        print(f"{key}: next_free_vgpr {vg}  private_segment_fixed_size {ps}", file=out)
+        res[key] = (int(vg), int(ps))
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--asm", help="analyse this assembly file instead of compiling")
+    ap.add_argument("--label", help="a heading printed first (e.g. the commit)")
+    a = ap.parse_args()
+    if a.asm:
+        lines = open(a.asm).read().splitlines()
+    else:
+        with tempfile.TemporaryDirectory() as d:
+            path = os.path.join(d, "c4_search.s")
+            compile_asm(path)
+            lines = open(path).read().splitlines()
+    if a.label:
+        print(f"== {a.label}")
+    analyse(lines, sys.stdout)
+
+
+if __name__ == "__main__":
+    main()

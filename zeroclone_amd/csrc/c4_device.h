@@ -253,14 +253,15 @@ __device__ __forceinline__ void rng_advance(Rng &r) {
 }
 
 // The 64 tempered words from the next unconsumed one on: lane l = word off + l of the
-// window (precondition: off < 64).
-template <class R>
-__device__ __forceinline__ uint32_t rng_view(const R &r) {
-    const uint32_t j = lane_id() + r.off;
-    const int idx = (int)(j << 2);  // ds_bpermute reads the lane from address bits 7:2 only
-    const uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute(idx, (int)r.wt);
-    const uint32_t b = (uint32_t)__builtin_amdgcn_ds_bpermute(idx, (int)r.wn);
-    return j < 64u ? a : b;
+// window (precondition: off < 64).  Word off + l sits in lane (off + l) % 64 of wt or of wn,
+// and every one of those 64 source lanes is read by exactly one lane: lane s by the word
+// s (of wt) when s >= off, by the word 64 + s (of wn) otherwise.  So the SOURCE lane picks
+// the window, and one lane permute gathers the view.
+__device__ __forceinline__ uint32_t rng_view(const Rng &r) {
+    const uint32_t lane = lane_id();
+    const uint32_t src = lane < r.off ? r.wn : r.wt;
+    // ds_bpermute reads the lane from address bits 7:2 only
+    return (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane + r.off) << 2), (int)src);
 }
 
 // rngpos after the search: {use0 + use(), use0 + grel}
@@ -292,10 +293,12 @@ struct LRng {
     uint32_t off;    // next word to consume = window start + off, off in [0, 128)
     int32_t hrel;    // words [.., use0 + hrel) were in the ring at the start (hrel >= 192 - off)
     // the two tempered windows stay in their registers: wa/wb hold x[W + lane] and
-    // x[W + 64 + lane] when ph == 0, the other way round when ph == 64 (an advance overwrites
-    // the older one in place and flips ph: no register rotation, so no loop-carried copies)
-    uint32_t wa, wb, ph;
-    __device__ __forceinline__ uint32_t cur() const { return ph ? wb : wa; }  // tempered x[W + lane]
+    // x[W + 64 + lane] when ph == 0, the other way round when ph is all ones (an advance
+    // overwrites the older one in place and flips ph: no register rotation, so no loop-carried
+    // copies).  ph is a wave mask, so that it selects between the two as it stands
+    uint32_t wa, wb;
+    uint64_t ph;
+    __device__ __forceinline__ uint32_t cur() const { return mask_sel(ph, wa, wb); }  // tempered x[W + lane]
     uint32_t wx;     // raw x[W + 128 + lane]
     uint32_t ia, ib, im;  // raw x[p-624], x[p-623], x[p-227] for p = W + 192 + lane (the next step)
     __device__ __forceinline__ int32_t use() const { return wrel + (int32_t)off; }
@@ -354,13 +357,12 @@ __device__ __forceinline__ void lrng_open(LRng &r, uint32_t *lds, const uint32_t
     lrng_prefetch(r);
 }
 
-// rng_view for the LDS stream: the window holding word off + l is wa or wb by ph
+// rng_view for the LDS stream: source lane s gives the second window when s < off, the
+// first otherwise, and which of wa / wb that is flips with ph
 __device__ __forceinline__ uint32_t rng_view(const LRng &r) {
-    const uint32_t j = lane_id() + r.off;
-    const int idx = (int)(j << 2);
-    const uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute(idx, (int)r.wa);
-    const uint32_t b = (uint32_t)__builtin_amdgcn_ds_bpermute(idx, (int)r.wb);
-    return (j ^ r.ph) < 64u ? a : b;
+    const uint32_t lane = lane_id();
+    const uint32_t src = mask_sel(__ballot(lane < r.off) ^ r.ph, r.wa, r.wb);
+    return (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane + r.off) << 2), (int)src);
 }
 
 // Move the windows on by 64 words (precondition: off >= 64); one recurrence step.
@@ -368,9 +370,10 @@ __device__ __forceinline__ void rng_advance(LRng &r) {
     r.wrel += kWin;
     r.off -= (uint32_t)kWin;
     const uint32_t t = temper(r.wx);  // the new second window replaces the old first one
-    if (r.ph) r.wb = t;
-    else r.wa = t;
-    r.ph ^= 64u;
+    const uint32_t na = mask_sel(r.ph, t, r.wa), nb = mask_sel(r.ph, r.wb, t);
+    r.wa = na;
+    r.wb = nb;
+    r.ph = ~r.ph;
     const int32_t p = r.wrel + 128 + (int32_t)lane_id();
     uint32_t x = mt_twist(r.ia, r.ib, r.im);
     if (r.wrel + 128 < r.hrel) {  // only inside the seeded block: words already in the ring
@@ -456,14 +459,21 @@ __device__ __forceinline__ uint32_t rng_below_pick(R &r, uint32_t n, const uint8
     }
 }
 
-// Per-search counters, accumulated in lane 0 of VGPRs (off the scalar unit, no SGPRs).
+// Per-search counters, accumulated in VGPRs (off the scalar unit, no SGPRs): add() counts a
+// uniform value in lane 0.  plies and blocks also take lane-parallel terms (a rollout's plies
+// in its leaf's lane), so their totals are the sums over the wave: total().
 struct Counters {
     int32_t expansions = 0, depth_sum = 0, plies = 0, blocks = 0;
     __device__ __forceinline__ void add(int32_t &c, int32_t v) { c += (lane_id() == 0) ? v : 0; }
+    __device__ __forceinline__ static int32_t total(int32_t c) {  // the same in every lane
+        for (int o = 32; o; o >>= 1) c += __shfl_xor(c, o);
+        return c;
+    }
 };
 
-// A pending leaf, kept in LDS between the phases of a flush.
-struct Leaf {
+// A pending leaf, kept in LDS between the phases of a flush (16-byte aligned: the rollout
+// reads both boards in one LDS access).
+struct alignas(16) Leaf {
     uint64_t p0, p1;  // stones of 'X' / 'O'
     uint32_t meta;    // node | depth << 16 | turn << 24 | legal mask << 25
     int32_t val;      // rollout value from the leaf's side to move

@@ -62,11 +62,24 @@ __device__ __forceinline__ void scan_or16x2(uint32_t &x, uint32_t &y) {
 }
 
 // Values that are the same in every lane but should live in VGPRs (worked on by the VALU):
-// the scalar unit is shared by the CU's four SIMDs and is the busier of the two here.
+// the scalar unit is shared by the CU's four SIMDs and is the busier of the two here.  The
+// empty asm is also where the compiler waits for a load of x, so it goes at x's first use,
+// not at the load.
 __device__ __forceinline__ uint64_t in_vgpr(uint64_t x) {
     __asm__("" : "+v"(x));
     return x;
 }
+// a <= b ? -1 : y, formed on the scalar unit as one value the compiler cannot take apart: a
+// loop exit tested as "win OR board full" is otherwise built from two 64-bit flag masks, ANDed
+// with exec and tested again at the loop's latch
+__device__ __forceinline__ int neg_if_le(uint32_t a, uint32_t b, int y) {
+    int r;
+    __asm__("s_cmp_le_u32 %1, %2\n\ts_cselect_b32 %0, -1, %3" : "=s"(r) : "s"(a), "s"(b), "s"(y) : "scc");
+    return r;
+}
+// v_writelane_b32: `old` with lane l replaced by the uniform x (the compiler's intrinsic, which
+// this clang gives no builtin for; it places the lane select and keeps the hazards)
+extern "C" __device__ int zc_writelane(int x, int l, int old) __asm("llvm.amdgcn.writelane.i32");
 // first set bit of a wave mask, 0xFFFFFFFF when empty (s_ff1_i32_b64)
 __device__ __forceinline__ uint32_t ff1(uint64_t m) {
     uint32_t r;
@@ -139,16 +152,25 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
     uint64_t t_ = ZC_RSTAMP && sub ? __builtin_amdgcn_s_memtime() : 0;
     const uint32_t lane = lane_id();
     const uint32_t lrow = lane >> 4;
-    const bool first_row = (lrow & 1u) == 0;                  // rows 0, 2: the block's first mover
+    // rows 1, 3 test the block's second mover (rows 0, 2 its first), as a wave mask: XORed with
+    // the side to move it says which lanes take p1 for their stones (`S1` below)
+    const uint64_t second_rows = __ballot((lrow & 1u) != 0);
     const uint32_t d1 = lrow < 2 ? 1u : 6u, d2 = lrow < 2 ? 7u : 8u;
     // lane 7a + b (< 49): the columns {a, b} (a == b: one column) whose fills a block may see
     const uint32_t pairbits = lane < 49u ? (1u << (lane / 7u)) | (1u << (lane % 7u)) : 0u;
     // per leaf, lane-parallel (lane = leaf of a group of 64): side to move / last mover stones,
     // 41 - stones (-2: has_four(last mover), the leaf is won), read out by readlane when the
     // leaf's turn comes
+    // whatever the caller left in flight in vector memory is waited for once, here: nothing
+    // below issues any (the HBM stream's window loads wait for themselves), and a wait at the
+    // top of every leaf would otherwise guard the registers the leaf loop reuses
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) alone
     for (int g = 0; g < nb; g += 64) {
       uint32_t lm_v = 0, ow_v = 0, hp_v = 0;
       int room_v = 0;
+      // the group's results, leaf jl in lane jl (one v_writelane each per leaf): the values go
+      // to the leaf records in one store after the group, the plies into the counter's lanes
+      int val_v = 0, q_v = 0;
       {
         const int jj = g + (int)lane;
         if (jj < nb) {
@@ -159,6 +181,9 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
             room_v = has_four(op_v) ? -2 : 41 - __popcll(x0 | x1);
             const uint64_t oc = x0 | x1;  // column heights, 4 bits per column
             for (int c = 0; c < 7; ++c) hp_v |= (uint32_t)__popcll((oc >> (7 * c)) & 0x3Full) << (4 * c);
+#ifndef ZC_DIAG_WASTE
+            cn.blocks += room_v >= 0 ? 1 : 0;  // a rollout's first block (the others: where it goes on)
+#endif
         }
       }
       const int jend = min(nb, g + 64);
@@ -166,22 +191,21 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
         RMARK(6);  // regions: 1 leaf setup, 2 view, 3 first segment, 4 absorbed fill, 5 win test, 6 block tail
         const int jl = j - g;
         const uint32_t lm = (uint32_t)__builtin_amdgcn_readlane((int)lm_v, jl);
-        // the leaf's boards straight from LDS into VGPRs (one uniform address per read: a
-        // broadcast), in flight while the first view is gathered
-        const uint32_t tnv = (lm >> 24) & 1u;
-        const uint64_t *const pp = &L[j].p0;
-        uint64_t me = in_vgpr(pp[tnv]);       // side to move
-        uint64_t op = in_vgpr(pp[tnv ^ 1u]);  // last mover
+        // the leaf's boards straight from LDS into VGPRs: one 16-byte read of (p0, p1) at a
+        // uniform address (a broadcast), waited for where the win test first uses them.  They
+        // stay p0 / p1 for the whole rollout; S1 = the lanes that test p1, the second mover's
+        // rows when p0 is to move, the first mover's otherwise
+        uint4 pw;
+        __builtin_memcpy(&pw, &L[j], sizeof pw);  // Leaf is 16-byte aligned
+        uint64_t x0 = ((uint64_t)pw.y << 32) | pw.x, x1 = ((uint64_t)pw.w << 32) | pw.z;
+        uint64_t S1 = (lm >> 24) & 1u ? ~second_rows : second_rows;
         uint32_t hp = (uint32_t)__builtin_amdgcn_readlane((int)hp_v, jl);  // column heights, carried across blocks
         const uint32_t low0 = (uint32_t)__builtin_amdgcn_readlane((int)ow_v, jl);
         const int room0 = __builtin_amdgcn_readlane(room_v, jl);
-        const bool won = room0 == -2;
-        int val = 0;
+        int val = (room0 + 1) >> 1;  // -2: has_four(last mover), -1; -1: check_draw, 0
         int q = 0;  // plies played in this rollout (room0 - room when it ends)
         RMARK(1);
-        if (won) {  // has_four(last mover)
-            val = -1;
-        } else if (room0 >= 0) {  // not check_draw
+        if (room0 >= 0) {  // neither
             int room = room0;
             int mask = (int)(lm >> 25);
             uint32_t ow = low0;
@@ -190,7 +214,15 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
             // order words of the legal set minus the columns of `pairbits`, for the fills
             // (read as soon as the legal set is known, well before a fill needs it)
             uint32_t owp = s_order[(uint32_t)mask & ~pairbits];
-            for (;;) {
+            // One block of plies.  What it leaves for the steps after it: ew, the block's first
+            // winning lane (0xFFFFFFFF: none), and l0, its last lane otherwise; the lane and ply it
+            // ended at; every lane's column, the prefix sums of the plies per column, the fills,
+            // each row's stones and the lane of an absorbed fill.  Returns < 0 when the rollout
+            // is over: the ply's mover completed four (ew <= l0), or check_draw: board full —
+            // one scalar test.
+            uint32_t ew, l0, lf, endlane, endply, col, sc;
+            uint64_t F, mine;
+            auto block = [&]() __attribute__((always_inline)) {
                 RMARK(6);
                 uint32_t wv, v;
                 uint64_t A;  // accepted words
@@ -209,52 +241,53 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
                         A = __ballot(v < n);
                     } while (A == 0ull);
                 }
-#ifndef ZC_DIAG_WASTE
-                cn.add(cn.blocks, 1);
-#endif
                 RMARK(2);
                 const uint32_t cap_r = min((uint32_t)room, 30u);  // last ply index the board allows
                 uint32_t qk = mbcnt(A);                            // this lane's ply in the block
-                uint32_t col = (ow >> (3 * v)) & 7u;  // its column (if accepted; v < 8 as n < 8)
+                col = (ow >> (3 * v)) & 7u;  // its column (if accepted; v < 8 as n < 8)
                 // the ply's row: the column's height (hp, 4 bits per column, carried from block
                 // to block) + earlier plies in the same column (4-bit per-column counters,
                 // prefix-summed).  A nibble only overflows into the next column's after its own
                 // column filled — beyond the block's end, in lanes never read.
                 uint32_t one = mask_sel0(A, 1u << (4 * col));
-                uint32_t sc = scan_add32(one);
+                sc = scan_add32(one);
                 uint32_t row = ((sc - one + hp) >> (4 * col)) & 15u;  // the column's height + earlier plies in it
                 uint32_t nacc = (uint32_t)__popcll(A);
                 // the fills, kept as a wave mask (a per-lane bool merged across the absorption
                 // would be materialised and compared again)
-                uint64_t F = __ballot(row == 5u);
+                F = __ballot(row == 5u);
                 // the block's end: its first fill, or the first ply past the cap / the view's last
                 // accepted word (masks ANDed on the scalar unit, one lane compare)
                 uint64_t E0 = A & (F | __ballot(qk >= min(cap_r, nacc - 1u)));
-                uint32_t l0 = (uint32_t)__builtin_ctzll(E0);
+                l0 = (uint32_t)__builtin_ctzll(E0);
                 // the fills with room for more plies after them: the block's end is one of these
                 // exactly when it is the first of them
                 const uint64_t G = A & F & __ballot(qk < cap_r);
                 // the first fill, with room for more plies: re-draw the words after it under
-                // the new legal set
+                // the new legal set.  lf = the lane of that fill when it is absorbed; when none
+                // is, ff1(G) lies past the block's end (G is part of E0) or is 0xFFFFFFFF, so "the
+                // absorbed fill was played" is endlane >= lf either way and lf, like the fill's
+                // column (col[lf], which the re-draw keeps), needs no merge across the absorption
+                lf = ff1(G);
+#ifdef ZC_DIAG_WASTE
+                const uint32_t l0f = l0;
+#endif
 #if !(ZC_RV & 1)
-                uint32_t lf = 64u;  // lane of the absorbed fill (64: none)
-                uint32_t cf = 0;
                 RMARK(3);
-                if (ff1(G) == l0) {  // a fill with room for more plies
-                    lf = l0;
-                    cf = (uint32_t)__builtin_amdgcn_readlane((int)col, (int)lf);
+                if (lf == l0) {  // a fill with room for more plies
+                    const uint32_t cf = (uint32_t)__builtin_amdgcn_readlane((int)col, (int)lf);
                     const uint32_t ow2 = (uint32_t)__builtin_amdgcn_readlane((int)owp, (int)(8u * cf));
                     const uint32_t n2 = (ow2 >> 24) & 15u;
                     const uint32_t v2 = wv >> __clz(n2);
-                    const uint64_t low = (2ull << lf) - 1ull;  // lanes 0..lf
-                    A = (A & low) | (__ballot(v2 < n2) & ~low);
+                    const uint64_t high = ~1ull << lf;  // the lanes after lf
+                    A = (A & ~high) | (__ballot(v2 < n2) & high);
                     qk = mbcnt(A);
-                    col = mask_sel(low, (ow2 >> (3 * v2)) & 7u, col);  // lanes after lf: the new order
+                    col = mask_sel(high, col, (ow2 >> (3 * v2)) & 7u);  // lanes after lf: the new order
                     one = mask_sel0(A, 1u << (4 * col));
                     sc = scan_add32(one);
                     row = ((sc - one + hp) >> (4 * col)) & 15u;
                     nacc = (uint32_t)__popcll(A);
-                    F = __ballot(row == 5u) & ~low;  // the absorbed fill no longer ends the block
+                    F = __ballot(row == 5u) & high;  // the absorbed fill no longer ends the block
                     E0 = A & (F | __ballot(qk >= min(cap_r, nacc - 1u)));
                     l0 = (uint32_t)__builtin_ctzll(E0);
                 }
@@ -272,8 +305,11 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
                 const uint64_t bit = 1ull << (pb & 63u);
                 uint32_t blo = (uint32_t)bit, bhi = (uint32_t)(bit >> 32);
                 scan_or16x2(blo, bhi);
-                const uint64_t mine = ((uint64_t)bhi << 32) | blo;  // this row's stones so far
-                const uint64_t bd = (first_row ? me : op) | mine;
+                mine = ((uint64_t)bhi << 32) | blo;  // this row's stones so far
+                x0 = in_vgpr(x0);
+                x1 = in_vgpr(x1);
+                const uint64_t bd = (((uint64_t)mask_sel(S1, (uint32_t)(x0 >> 32), (uint32_t)(x1 >> 32)) << 32) |
+                                     mask_sel(S1, (uint32_t)x0, (uint32_t)x1)) | mine;
                 const uint64_t m1 = bd & (bd >> d1), m2 = bd & (bd >> d2);
                 const uint64_t f4 = (m1 & (m1 >> (2 * d1))) | (m2 & (m2 >> (2 * d2)));
                 const uint64_t W = __ballot(f4 != 0ull);
@@ -281,8 +317,6 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
                 const uint32_t W32 = (uint32_t)W | (uint32_t)(W >> 32);
                 const uint64_t Ew = A & __ballot(((W32 >> (c & 31u)) & 1u) != 0u);
 #else
-                uint32_t lf = 64u;  // lane of the absorbed fill (64: none)
-                uint32_t cf = 0;
                 // compact EVERY accepted word's ply by parity: ply q < 32 to lane (q & 1)*16 + q/2
                 // (a forward lane permute; the other lanes, and plies >= 32, land in lanes 32..63),
                 // then copy lanes 0..31 up over lanes 32..63.  No ply past the block's last one (at
@@ -299,7 +333,10 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
                     uint32_t blo = (uint32_t)bit, bhi = (uint32_t)(bit >> 32);
                     scan_or16x2(blo, bhi);
                     mine_ = ((uint64_t)bhi << 32) | blo;  // this row's stones so far
-                    const uint64_t bd = (first_row ? me : op) | mine_;
+                    x0 = in_vgpr(x0);
+                    x1 = in_vgpr(x1);
+                    const uint64_t bd = (((uint64_t)mask_sel(S1, (uint32_t)(x0 >> 32), (uint32_t)(x1 >> 32)) << 32) |
+                                         mask_sel(S1, (uint32_t)x0, (uint32_t)x1)) | mine_;
                     const uint64_t m1 = bd & (bd >> d1), m2 = bd & (bd >> d2);
                     const uint64_t f4 = (m1 & (m1 >> (2 * d1))) | (m2 & (m2 >> (2 * d2)));
                     const uint64_t W = __ballot(f4 != 0ull);
@@ -313,64 +350,65 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
                 // block without the second test
                 uint64_t Ew1 = 0, mine1 = 0;
                 RMARK(3);
-                if (ff1(G) == l0) {  // a fill with room for more plies
-                    lf = l0;
-                    cf = (uint32_t)__builtin_amdgcn_readlane((int)col, (int)lf);
+                if (lf == l0) {  // a fill with room for more plies
+                    const uint32_t cf = (uint32_t)__builtin_amdgcn_readlane((int)col, (int)lf);
                     const uint32_t ow2 = (uint32_t)__builtin_amdgcn_readlane((int)owp, (int)(8u * cf));
                     const uint32_t n2 = (ow2 >> 24) & 15u;
                     const uint32_t v2 = wv >> __clz(n2);
-                    const uint64_t low = (2ull << lf) - 1ull;  // lanes 0..lf
-                    if (ZC_RV & 1) Ew1 = win_test(A, qk, col, row, mine1) & low;
-                    A = (A & low) | (__ballot(v2 < n2) & ~low);
+                    const uint64_t high = ~1ull << lf;  // the lanes after lf
+                    if (ZC_RV & 1) Ew1 = win_test(A, qk, col, row, mine1) & ~high;
+                    A = (A & ~high) | (__ballot(v2 < n2) & high);
                     qk = mbcnt(A);
-                    col = mask_sel(low, (ow2 >> (3 * v2)) & 7u, col);  // lanes after lf: the new order
+                    col = mask_sel(high, col, (ow2 >> (3 * v2)) & 7u);  // lanes after lf: the new order
                     one = mask_sel0(A, 1u << (4 * col));
                     sc = scan_add32(one);
                     row = ((sc - one + hp) >> (4 * col)) & 15u;
                     nacc = (uint32_t)__popcll(A);
-                    F = __ballot(row == 5u) & ~low;  // the absorbed fill no longer ends the block
+                    F = __ballot(row == 5u) & high;  // the absorbed fill no longer ends the block
                     E0 = A & (F | __ballot(qk >= min(cap_r, nacc - 1u)));
                     l0 = (uint32_t)__builtin_ctzll(E0);
                 }
                 RMARK(4);
-                uint64_t mine, Ew;
+                uint64_t Ew;
                 if ((ZC_RV & 1) && Ew1 != 0ull) {  // the win precedes the fill (l0 >= lf after the re-draw)
                     Ew = Ew1;
                     mine = mine1;
                 } else {
                     Ew = win_test(A, qk, col, row, mine);
                 }
+                // (the merge of the two tests' masks can end up in VGPRs, which ff1's scalar
+                // operand does not take)
+                if (ZC_RV & 1) Ew = uni64(Ew);
 #endif
-                const uint32_t ew = ff1(Ew);
-                const uint32_t endlane = min(ew, l0);
-                const bool win = ew <= l0;  // (ff1 of an empty mask is 0xFFFFFFFF)
-                const uint32_t endply = (uint32_t)__builtin_amdgcn_readlane((int)qk, (int)endlane);
+                ew = ff1(Ew);
+                endlane = min(ew, l0);
+                endply = (uint32_t)__builtin_amdgcn_readlane((int)qk, (int)endlane);
                 rng.off += endlane + 1u;  // words through the block's last ply are consumed
 #ifdef ZC_DIAG_WASTE
-                cn.add(cn.blocks, lf < 64u && endlane < lf ? 1 : 0);
-                cn.add(cn.plies, lf < 64u ? 1 : 0);
+                cn.add(cn.blocks, lf == l0f && endlane < lf ? 1 : 0);
+                cn.add(cn.plies, lf == l0f ? 1 : 0);
 #endif
                 room -= (int)endply + 1;
                 RMARK(5);
-                if (win) {  // the ply's mover completed four
-                    val = ((room0 - room) & 1) ? 1 : -1;  // an odd number of plies: the leaf's side won
-                    break;
-                }
-                if (room < 0) {  // check_draw: board full
-                    val = 0;
-                    break;
-                }
-                // the rollout goes on (most end in their first block, so this is off the common
-                // path): both sides' stones after ply endply — first mover through ply
-                // 2*(endply/2) (row 0, inclusive), second mover through the odd plies <= endply
-                // (row 1, inclusive scan at lane 15 + (endply+1)/2; none when endply = 0)
+                return neg_if_le(ew, l0, room);
+            };
+            // The rollout goes on: the state for its next block.  Both sides' stones after ply
+            // endply — first mover through ply 2*(endply/2) (row 0, inclusive), second mover
+            // through the odd plies <= endply (row 1, inclusive scan at lane 15 + (endply+1)/2;
+            // none when endply = 0)
+            auto go_on = [&]() __attribute__((always_inline)) {
+#ifndef ZC_DIAG_WASTE
+                cn.add(cn.blocks, 1);
+#endif
                 {
                     const uint64_t s2 = readlane64(mine, (int)((endply + 31u) >> 1));
-                    const uint64_t a2 = me | readlane64(mine, (int)(endply >> 1));
-                    const uint64_t b2 = op | (endply ? s2 : 0ull);
-                    const bool odd = endply & 1u;  // an even number of plies: the first mover is to move again
-                    me = odd ? a2 : b2;
-                    op = odd ? b2 : a2;
+                    const uint64_t a2 = readlane64(mine, (int)(endply >> 1));  // the first mover's new stones
+                    const uint64_t b2 = endply ? s2 : 0ull;                     // the second mover's
+                    const bool p1_first = S1 & 1ull;  // lane 0 tests the first mover: p1, if it takes p1
+                    x0 |= p1_first ? b2 : a2;
+                    x1 |= p1_first ? a2 : b2;
+                    // an odd number of plies: the other side is to move, and the rows trade boards
+                    S1 = endply & 1u ? S1 : ~S1;
                 }
                 hp += (uint32_t)__builtin_amdgcn_readlane((int)sc, (int)endlane);  // plies per column through endlane
                 // the legal set (and its CPython order) after the block's fills: the absorbed
@@ -378,8 +416,8 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
                 const bool fa = endlane >= lf;
                 const bool fe = (F >> endlane) & 1u;
                 {  // unconditional (selects), so the block loop carries one copy of its state
-                    const uint32_t ce = fe ? (uint32_t)__builtin_amdgcn_readlane((int)col, (int)endlane) : cf;
-                    const uint32_t ca = fa ? cf : ce;
+                    const uint32_t ca = (uint32_t)__builtin_amdgcn_readlane((int)col, (int)(fa ? lf : endlane));
+                    const uint32_t ce = fe ? (uint32_t)__builtin_amdgcn_readlane((int)col, (int)endlane) : ca;
                     const bool ff = fa | fe;
                     mask = ff ? mask & ~((1 << ca) | (1 << ce)) : mask;
                     const uint32_t ownew = (uint32_t)__builtin_amdgcn_readlane((int)owp, (int)((7u * ca + ce) & 63u));
@@ -388,14 +426,25 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
                 }
                 n = (ow >> 24) & 15u;
                 sh = (uint32_t)__builtin_clz(n);
+            };
+            // Most rollouts end in their first block, so that one stands alone, in line, and only
+            // the others enter the loop: every branch the compiler emits is structured, and a
+            // loop whose exit lies in mid-body carries its exit test as a flag mask to a latch of
+            // its own, on every rollout; the value is formed after the last block for the same reason
+            if (block() >= 0) {
+                do go_on();
+                while (block() >= 0);
             }
             q = room0 - room;
+            val = ew <= l0 ? ((q & 1) ? 1 : -1) : 0;  // a win after an odd number of plies: the leaf's side's
         }
-        L[j].val = val;  // uniform: every lane stores
-#ifndef ZC_DIAG_WASTE
-        cn.add(cn.plies, q);
-#endif
+        val_v = zc_writelane(val, jl, val_v);
+        q_v = zc_writelane(q, jl, q_v);
       }
+      if (g + (int)lane < jend) L[g + (int)lane].val = val_v;
+#ifndef ZC_DIAG_WASTE
+      cn.plies += q_v;  // lane-parallel (Counters)
+#endif
     }
 }
 
@@ -1419,6 +1468,7 @@ __device__ __forceinline__ void search_games(const SearchParams &p, uint8_t *s_d
     int na_col;
     const int col = best_column(t, na_col);
     if (lane < 7) p.out_na[(size_t)gl * 7 + lane] = na_col;
+    const int32_t plies = Counters::total(cn.plies), blocks = Counters::total(cn.blocks);
     if (lane == 0) {
         p.out_move[gl] = col;
         zc_game_stats st{};
@@ -1426,8 +1476,8 @@ __device__ __forceinline__ void search_games(const SearchParams &p, uint8_t *s_d
         st.expansions = cn.expansions;
         st.depth_sum = cn.depth_sum;
         st.leaves = p.sims;
-        st.rollout_plies = cn.plies;
-        st.rollout_blocks = cn.blocks;
+        st.rollout_plies = plies;
+        st.rollout_blocks = blocks;
         st.rng_words = rng.use();
         p.out_stats[gl] = st;
     }
@@ -1564,14 +1614,15 @@ __global__ __launch_bounds__(kSearchWaves * kBlock, 4) void c4_selfplay_kernel(S
         p.out_moves16[o] = -1;
         p.out_results[o] = ZC_SLOT_SKIP;
     }
+    const int32_t plies = Counters::total(cn.plies), blocks = Counters::total(cn.blocks);
     if (lane == 0) {
         zc_game_stats st{};
         st.status = status;
         st.expansions = cn.expansions;
         st.depth_sum = cn.depth_sum;
         st.leaves = leaves;
-        st.rollout_plies = cn.plies;
-        st.rollout_blocks = cn.blocks;
+        st.rollout_plies = plies;
+        st.rollout_blocks = blocks;
         st.rng_words = rng.use();
         st.reserved = finished;
         p.out_stats[gl] = st;
