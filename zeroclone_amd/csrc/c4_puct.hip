@@ -483,15 +483,19 @@ __global__ __launch_bounds__(64) void c4_puct_end_kernel(C4PuctParams p) {
             argmax8(bv, bi);
             best = uni(bi);
         } else {  // sample proportional to Na^(1/T): inverse CDF over the moves in order
+            const double inv_t = 1.0 / (double)p.temperature;
+            int32_t top = 0;
+            for (int j = 0; j < nm; ++j) top = max(top, uni(R->na[j]));
+            const int kb = count_bits(top);
             double tot = 0.0;
-            for (int j = 0; j < nm; ++j) tot += pow((double)uni(R->na[j]), 1.0 / (double)p.temperature);
+            for (int j = 0; j < nm; ++j) tot += temperature_weight(uni(R->na[j]), kb, inv_t);
             const uint4 r = philox(make_uint4((uint32_t)g, 0x5BE0CD19u, search_number(p, gl), 0),
                                    make_uint2((uint32_t)p.seed, (uint32_t)(p.seed >> 32)));
             const double target = (double)u01(r.x) * tot;
             double run = 0.0;
             best = nm - 1;
             for (int j = 0; j < nm; ++j) {
-                run += pow((double)uni(R->na[j]), 1.0 / (double)p.temperature);
+                run += temperature_weight(uni(R->na[j]), kb, inv_t);
                 if (run > target) {
                     best = j;
                     break;

@@ -465,10 +465,18 @@ __global__ __launch_bounds__(64) void puct_end_kernel(ChessParams p) {
             }
             best = uni(bi);
         } else {  // sample proportional to Na^(1/T): inverse CDF over the moves in order
+            const double inv_t = 1.0 / (double)p.temperature;
+            int32_t top = 0;
+            for (int b = 0; b < nm; b += 64) {
+                const int j = b + (int)lane;
+                if (j < nm) top = max(top, t.na[base + j]);
+            }
+            for (int o = 32; o > 0; o >>= 1) top = max(top, __shfl_xor(top, o));
+            const int kb = count_bits(uni(top));
             double tot = 0.0;
             for (int b = 0; b < nm; b += 64) {
                 const int j = b + (int)lane;
-                tot += j < nm ? pow((double)t.na[base + j], 1.0 / (double)p.temperature) : 0.0;
+                tot += j < nm ? temperature_weight(t.na[base + j], kb, inv_t) : 0.0;
             }
             tot = wave_sum_d(tot);
             const uint4 r = philox(make_uint4((uint32_t)g, 0x5BE0CD19u, search_number(p, gl), 0),
@@ -477,7 +485,7 @@ __global__ __launch_bounds__(64) void puct_end_kernel(ChessParams p) {
             double run = 0.0;
             best = nm - 1;
             for (int j = 0; j < nm; ++j) {  // serial scan in move order (<= 256 steps, once per move)
-                run += pow((double)uni(t.na[base + j]), 1.0 / (double)p.temperature);
+                run += temperature_weight(uni(t.na[base + j]), kb, inv_t);
                 if (run > target) {
                     best = j;
                     break;

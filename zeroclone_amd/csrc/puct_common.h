@@ -41,6 +41,15 @@ __device__ __forceinline__ uint32_t search_number(const Params &p, int gl) {
     return p.search_no ? (uint32_t)__builtin_amdgcn_readfirstlane(p.search_no[gl]) : 0u;
 }
 
+// Temperature weight of a root move with n visits: (n * 2^-k)^(1/T), k = the bit length of
+// the root's largest count.  The common factor 2^(-k/T) leaves the sampled distribution as
+// n^(1/T); the scaled base is below 1, so no temperature overflows (unscaled, 1210^100 does,
+// and a total of inf selects no move), and a power of two keeps integer 1/T exact.
+__device__ __forceinline__ int count_bits(int32_t max_count) { return max_count > 0 ? 32 - __clz(max_count) : 0; }
+__device__ __forceinline__ double temperature_weight(int32_t n, int k, double inv_t) {
+    return pow(ldexp((double)n, -k), inv_t);
+}
+
 __device__ __forceinline__ double wave_sum_d(double x) {
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
     return x;
