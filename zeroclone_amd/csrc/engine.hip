@@ -253,31 +253,69 @@ zc::SearchParams make_params(zc_engine *e, int32_t first, int32_t n, const zc_c4
 
 // ---------------------------------------------------------------- stepwise search
 namespace {
+using StepSearch = zc_engine::StepSearch;
+using PuctSearch = zc_engine::PuctSearch;
+
+// The four stepwise searches (zc_c4_ext_*, zc_chess_ext_*, zc_chess_puct_*, zc_c4_puct_*) share
+// one protocol, begin -> [select(f) -> backup(f)] * flushes -> end, every step over games
+// inside the begin call's range.
+int value_flushes(int sims, int bs) { return (sims + bs - 1) / bs; }
+int puct_flushes(int sims, int bs) { return 1 + (sims - 1 + bs - 1) / bs; }  // flush 0: the roots alone
+
+void set_step(StepSearch &s, int32_t first, int32_t n, int32_t sims, double c, int32_t bs, int flushes) {
+    s.first = first;
+    s.n = n;
+    s.sims = sims;
+    s.bs = bs;
+    s.flushes = flushes;
+    s.c = c;
+    s.active = true;
+}
+
+// A step of search `s` over games [first, first + n), and over flush `flush` where it has one.
+int check_step(const StepSearch &s, int32_t first, int32_t n, int32_t flush, bool need_flush) {
+    if (!s.active) return fail(ZC_EINVAL, "no %s search in progress (call %s_begin first)", s.what, s.what);
+    if (first < s.first || n < 0 || (int64_t)first + n > (int64_t)s.first + s.n)
+        return fail(ZC_EINVAL, "games [%d, %d) outside the %s search's range [%d, %d)", first, first + n, s.what,
+                    s.first, s.first + s.n);
+    if (need_flush && (flush < 0 || flush >= s.flushes))
+        return fail(ZC_EINVAL, "flush %d outside [0, %d)", flush, s.flushes);
+    return ZC_OK;
+}
+
+// A host-policy step (zc_*_hp_walk / zc_*_hp_expand) on one game's leaf `leaf` of flush `flush`.
+int check_hp(const StepSearch &s, int32_t game, int32_t flush, int32_t leaf) {
+    if (int r = check_step(s, game, 1, flush, true)) return r;
+    const int nb = std::min(s.bs, s.sims - flush * s.bs);
+    if (leaf < 0 || leaf >= nb) return fail(ZC_EINVAL, "leaf %d outside flush %d's [0, %d)", leaf, flush, nb);
+    return ZC_OK;
+}
+
+// The frame of a step over games [first, first + n) of `search` (a zc_engine member): the
+// arguments (`cond`: the buffers n > 0 needs), the lock, the range and the flush, the device.
+#define ZC_STEP_ENTRY(search, flush, need_flush, cond)                                          \
+    if (!eng || (n && !(cond))) return fail(ZC_EINVAL, "null argument");                        \
+    std::lock_guard<std::mutex> lk(eng->mu);                                                    \
+    if (int r = check_step(eng->search, first, n, flush, need_flush)) return r;                 \
+    if (!n) return ZC_OK;                                                                       \
+    ZC_HIP(hipSetDevice(eng->cfg.device));
+
+int check_planes_dtype(int32_t planes_dtype) {
+    if (planes_dtype != ZC_F32 && planes_dtype != ZC_F16) return fail(ZC_EINVAL, "planes_dtype must be ZC_F32 or ZC_F16");
+    return ZC_OK;
+}
+
 zc::ExtParams ext_params(zc_engine *e, int32_t first, int32_t n) {
     zc::ExtParams p{};
     p.first_game = first;
     p.n_games = n;
-    p.sims = e->ext_sims;
-    p.bs = e->ext_bs;
+    p.sims = e->c4_value.sims;
+    p.bs = e->c4_value.bs;
     p.M = e->M;
     p.max_batch = e->cfg.max_batch;
-    p.c = e->ext_c;
+    p.c = e->c4_value.c;
     p.a = e->a;
     return p;
-}
-
-int check_ext_range(const zc_engine *e, int32_t first, int32_t n) {
-    if (!e->ext_active) return fail(ZC_EINVAL, "no stepwise search in progress (call zc_c4_ext_begin first)");
-    if (first < e->ext_first || n < 0 || (int64_t)first + n > (int64_t)e->ext_first + e->ext_n)
-        return fail(ZC_EINVAL, "games [%d, %d) outside the stepwise search's range [%d, %d)", first, first + n,
-                    e->ext_first, e->ext_first + e->ext_n);
-    return ZC_OK;
-}
-
-int check_flush(const zc_engine *e, int32_t flush) {
-    const int nflush = (e->ext_sims + e->ext_bs - 1) / e->ext_bs;
-    if (flush < 0 || flush >= nflush) return fail(ZC_EINVAL, "flush %d outside [0, %d)", flush, nflush);
-    return ZC_OK;
 }
 }  // namespace
 
@@ -704,12 +742,7 @@ int zc_c4_ext_begin(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state 
     if (int r = check_carry(eng, first, n)) return r;
     std::lock_guard<std::mutex> lk(eng->mu);
     ZC_HIP(hipSetDevice(eng->cfg.device));
-    eng->ext_first = first;
-    eng->ext_n = n;
-    eng->ext_sims = sims;
-    eng->ext_bs = bs;
-    eng->ext_c = c;
-    eng->ext_active = true;
+    set_step(eng->c4_value, first, n, sims, c, bs, value_flushes(sims, bs));
     if (!n) return ZC_OK;
     zc::ExtParams p = ext_params(eng, first, n);
     p.roots = d_roots;
@@ -720,13 +753,8 @@ int zc_c4_ext_begin(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state 
 
 int zc_c4_ext_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, zc_c4_state *d_leaves, void *d_planes,
                      int32_t planes_dtype, int32_t *d_counts, void *hip_stream) {
-    if (!eng) return fail(ZC_EINVAL, "null argument");
-    if (planes_dtype != ZC_F32 && planes_dtype != ZC_F16) return fail(ZC_EINVAL, "planes_dtype must be ZC_F32 or ZC_F16");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_ext_range(eng, first, n)) return r;
-    if (int r = check_flush(eng, flush)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
+    if (int r = check_planes_dtype(planes_dtype)) return r;
+    ZC_STEP_ENTRY(c4_value, flush, true, true)
     zc::ExtParams p = ext_params(eng, first, n);
     p.flush = flush;
     p.leaves = d_leaves;
@@ -740,12 +768,7 @@ int zc_c4_ext_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, zc
 
 int zc_c4_ext_backup(zc_engine *eng, int32_t first, int32_t n, int32_t flush, const double *d_values,
                      void *hip_stream) {
-    if (!eng || (n && !d_values)) return fail(ZC_EINVAL, "null argument");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_ext_range(eng, first, n)) return r;
-    if (int r = check_flush(eng, flush)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
+    ZC_STEP_ENTRY(c4_value, flush, true, d_values)
     zc::ExtParams p = ext_params(eng, first, n);
     p.flush = flush;
     p.values = d_values;
@@ -756,11 +779,7 @@ int zc_c4_ext_backup(zc_engine *eng, int32_t first, int32_t n, int32_t flush, co
 
 int zc_c4_ext_end(zc_engine *eng, int32_t first, int32_t n, int32_t *d_move, int32_t *d_na, zc_game_stats *d_stats,
                   void *hip_stream) {
-    if (!eng || (n && (!d_move || !d_na || !d_stats))) return fail(ZC_EINVAL, "null argument");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_ext_range(eng, first, n)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
+    ZC_STEP_ENTRY(c4_value, 0, false, d_move && d_na && d_stats)
     zc::ExtParams p = ext_params(eng, first, n);
     p.out_move = d_move;
     p.out_na = d_na;
@@ -774,10 +793,7 @@ int zc_c4_hp_walk(zc_engine *eng, int32_t game, int32_t flush, int32_t leaf, zc_
                   void *hip_stream) {
     if (!eng || !d_node) return fail(ZC_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_ext_range(eng, game, 1)) return r;
-    if (int r = check_flush(eng, flush)) return r;
-    const int nb = std::min(eng->ext_bs, eng->ext_sims - flush * eng->ext_bs);
-    if (leaf < 0 || leaf >= nb) return fail(ZC_EINVAL, "leaf %d outside flush %d's [0, %d)", leaf, flush, nb);
+    if (int r = check_hp(eng->c4_value, game, flush, leaf)) return r;
     ZC_HIP(hipSetDevice(eng->cfg.device));
     zc::ExtParams p = ext_params(eng, game, 1);
     p.flush = flush;
@@ -792,10 +808,7 @@ int zc_c4_hp_expand(zc_engine *eng, int32_t game, int32_t flush, int32_t leaf, i
                     zc_c4_state *d_leaf, void *hip_stream) {
     if (!eng) return fail(ZC_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_ext_range(eng, game, 1)) return r;
-    if (int r = check_flush(eng, flush)) return r;
-    const int nb = std::min(eng->ext_bs, eng->ext_sims - flush * eng->ext_bs);
-    if (leaf < 0 || leaf >= nb) return fail(ZC_EINVAL, "leaf %d outside flush %d's [0, %d)", leaf, flush, nb);
+    if (int r = check_hp(eng->c4_value, game, flush, leaf)) return r;
     if (untried_index < -1 || untried_index > 6) return fail(ZC_EINVAL, "untried index %d outside [-1, 7)", untried_index);
     ZC_HIP(hipSetDevice(eng->cfg.device));
     zc::ExtParams p = ext_params(eng, game, 1);
@@ -1047,6 +1060,11 @@ int check_chess(zc_engine *e, int32_t first, int32_t n, int32_t sims, double c, 
     if (!isfinite(freedom)) return fail(ZC_EINVAL, "policy_freedom must be finite");
     return ZC_OK;
 }
+
+zc::ChessParams chess_value_params(zc_engine *e, int32_t first, int32_t n) {  // of the zc_chess_ext_* search
+    const zc_engine::ChessValueSearch &s = e->chess_value;
+    return chess_params(e, first, n, s.sims, s.c, s.bs, s.policy, s.freedom);
+}
 }  // namespace
 
 extern "C" {
@@ -1188,46 +1206,22 @@ int zc_chess_ext_begin(zc_engine *eng, int32_t first, int32_t n, const zc_chess_
     std::lock_guard<std::mutex> lk(eng->mu);
     ZC_HIP(hipSetDevice(eng->cfg.device));
     if (int r = ensure_chess(eng)) return r;
-    eng->cx_first = first;
-    eng->cx_n = n;
-    eng->cx_sims = sims;
-    eng->cx_bs = bs;
-    eng->cx_c = c;
-    eng->cx_policy = policy;
-    eng->cx_freedom = freedom;
-    eng->cx_active = true;
+    set_step(eng->chess_value, first, n, sims, c, bs, value_flushes(sims, bs));
+    eng->chess_value.policy = policy;
+    eng->chess_value.freedom = freedom;
     if (!n) return ZC_OK;
-    zc::ChessParams p = chess_params(eng, first, n, sims, c, bs, policy, freedom);
+    zc::ChessParams p = chess_value_params(eng, first, n);
     p.roots = d_roots;
     zc::launch_chess_ext_begin(p, (hipStream_t)hip_stream);
     ZC_HIP(hipGetLastError());
     return ZC_OK;
 }
 
-}  // extern "C"
-
-namespace {
-int check_cx(zc_engine *e, int32_t first, int32_t n, int32_t flush, bool need_flush) {
-    if (!e->cx_active) return fail(ZC_EINVAL, "no chess stepwise search in progress (call zc_chess_ext_begin first)");
-    if (first < e->cx_first || n < 0 || (int64_t)first + n > (int64_t)e->cx_first + e->cx_n)
-        return fail(ZC_EINVAL, "games [%d, %d) outside the stepwise search's range", first, first + n);
-    const int nflush = (e->cx_sims + e->cx_bs - 1) / e->cx_bs;
-    if (need_flush && (flush < 0 || flush >= nflush)) return fail(ZC_EINVAL, "flush %d outside [0, %d)", flush, nflush);
-    return ZC_OK;
-}
-}  // namespace
-
-extern "C" {
-
 int zc_chess_ext_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, zc_chess_state *d_leaves,
                         void *d_planes, int32_t planes_dtype, int32_t *d_counts, void *hip_stream) {
-    if (!eng) return fail(ZC_EINVAL, "null argument");
-    if (planes_dtype != ZC_F32 && planes_dtype != ZC_F16) return fail(ZC_EINVAL, "planes_dtype must be ZC_F32 or ZC_F16");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_cx(eng, first, n, flush, true)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
-    zc::ChessParams p = chess_params(eng, first, n, eng->cx_sims, eng->cx_c, eng->cx_bs, eng->cx_policy, eng->cx_freedom);
+    if (int r = check_planes_dtype(planes_dtype)) return r;
+    ZC_STEP_ENTRY(chess_value, flush, true, true)
+    zc::ChessParams p = chess_value_params(eng, first, n);
     p.flush = flush;
     p.leaves = d_leaves;
     p.planes = d_planes;
@@ -1240,12 +1234,8 @@ int zc_chess_ext_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush,
 
 int zc_chess_ext_backup(zc_engine *eng, int32_t first, int32_t n, int32_t flush, const double *d_values,
                         void *hip_stream) {
-    if (!eng || (n && !d_values)) return fail(ZC_EINVAL, "null argument");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_cx(eng, first, n, flush, true)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
-    zc::ChessParams p = chess_params(eng, first, n, eng->cx_sims, eng->cx_c, eng->cx_bs, eng->cx_policy, eng->cx_freedom);
+    ZC_STEP_ENTRY(chess_value, flush, true, d_values)
+    zc::ChessParams p = chess_value_params(eng, first, n);
     p.flush = flush;
     p.values = d_values;
     zc::launch_chess_ext_backup(p, (hipStream_t)hip_stream);
@@ -1255,12 +1245,8 @@ int zc_chess_ext_backup(zc_engine *eng, int32_t first, int32_t n, int32_t flush,
 
 int zc_chess_ext_end(zc_engine *eng, int32_t first, int32_t n, uint16_t *d_move, int32_t *d_na, zc_game_stats *d_stats,
                      void *hip_stream) {
-    if (!eng || (n && (!d_move || !d_na || !d_stats))) return fail(ZC_EINVAL, "null argument");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_cx(eng, first, n, 0, false)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
-    zc::ChessParams p = chess_params(eng, first, n, eng->cx_sims, eng->cx_c, eng->cx_bs, eng->cx_policy, eng->cx_freedom);
+    ZC_STEP_ENTRY(chess_value, 0, false, d_move && d_na && d_stats)
+    zc::ChessParams p = chess_value_params(eng, first, n);
     p.out_move = d_move;
     p.out_na = d_na;
     p.out_stats = d_stats;
@@ -1273,11 +1259,9 @@ int zc_chess_hp_walk(zc_engine *eng, int32_t game, int32_t flush, int32_t leaf, 
                      void *hip_stream) {
     if (!eng || !d_node) return fail(ZC_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_cx(eng, game, 1, flush, true)) return r;
-    const int nb = std::min(eng->cx_bs, eng->cx_sims - flush * eng->cx_bs);
-    if (leaf < 0 || leaf >= nb) return fail(ZC_EINVAL, "leaf %d outside flush %d's [0, %d)", leaf, flush, nb);
+    if (int r = check_hp(eng->chess_value, game, flush, leaf)) return r;
     ZC_HIP(hipSetDevice(eng->cfg.device));
-    zc::ChessParams p = chess_params(eng, game, 1, eng->cx_sims, eng->cx_c, eng->cx_bs, eng->cx_policy, eng->cx_freedom);
+    zc::ChessParams p = chess_value_params(eng, game, 1);
     p.flush = flush;
     p.hp_leaf = leaf;
     p.hp_node = d_node;
@@ -1290,13 +1274,11 @@ int zc_chess_hp_expand(zc_engine *eng, int32_t game, int32_t flush, int32_t leaf
                        zc_chess_state *d_leaf, void *hip_stream) {
     if (!eng) return fail(ZC_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_cx(eng, game, 1, flush, true)) return r;
-    const int nb = std::min(eng->cx_bs, eng->cx_sims - flush * eng->cx_bs);
-    if (leaf < 0 || leaf >= nb) return fail(ZC_EINVAL, "leaf %d outside flush %d's [0, %d)", leaf, flush, nb);
+    if (int r = check_hp(eng->chess_value, game, flush, leaf)) return r;
     if (untried_index < -1 || untried_index >= ZC_CHESS_MAX_MOVES)
         return fail(ZC_EINVAL, "untried index %d outside [-1, %d)", untried_index, ZC_CHESS_MAX_MOVES);
     ZC_HIP(hipSetDevice(eng->cfg.device));
-    zc::ChessParams p = chess_params(eng, game, 1, eng->cx_sims, eng->cx_c, eng->cx_bs, eng->cx_policy, eng->cx_freedom);
+    zc::ChessParams p = chess_value_params(eng, game, 1);
     p.flush = flush;
     p.hp_leaf = leaf;
     p.hp_index = untried_index;
@@ -1332,13 +1314,9 @@ int zc_chess_rollouts_async(zc_engine *eng, int32_t game, int32_t n_states, cons
 int zc_chess_ext_rollouts(zc_engine *eng, int32_t first, int32_t n, int32_t flush, const uint16_t *d_hist,
                           const int32_t *d_hist_len, int32_t hist_cap, double *d_values, int32_t *d_status,
                           void *hip_stream) {
-    if (!eng || (n && (!d_hist || !d_hist_len || !d_values))) return fail(ZC_EINVAL, "null argument");
     if (hist_cap < 1) return fail(ZC_EINVAL, "hist_cap must be >= 1");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_cx(eng, first, n, flush, true)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
-    zc::ChessParams p = chess_params(eng, first, n, eng->cx_sims, eng->cx_c, eng->cx_bs, eng->cx_policy, eng->cx_freedom);
+    ZC_STEP_ENTRY(chess_value, flush, true, d_hist && d_hist_len && d_values)
+    zc::ChessParams p = chess_value_params(eng, first, n);
     p.flush = flush;
     p.rhist = d_hist;
     p.rhlen = d_hist_len;
@@ -1352,12 +1330,8 @@ int zc_chess_ext_rollouts(zc_engine *eng, int32_t first, int32_t n, int32_t flus
 
 int zc_chess_ext_leaf_moves(zc_engine *eng, int32_t first, int32_t n, int32_t flush, uint16_t *d_moves,
                             int32_t *d_depth, void *hip_stream) {
-    if (!eng || (n && (!d_moves || !d_depth))) return fail(ZC_EINVAL, "null argument");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_cx(eng, first, n, flush, true)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
-    zc::ChessParams p = chess_params(eng, first, n, eng->cx_sims, eng->cx_c, eng->cx_bs, eng->cx_policy, eng->cx_freedom);
+    ZC_STEP_ENTRY(chess_value, flush, true, d_moves && d_depth)
+    zc::ChessParams p = chess_value_params(eng, first, n);
     p.flush = flush;
     p.path_moves = d_moves;
     p.path_depth = d_depth;
@@ -1369,29 +1343,49 @@ int zc_chess_ext_leaf_moves(zc_engine *eng, int32_t first, int32_t n, int32_t fl
 // ---------------------------------------------------------------- chess PUCT search
 int zc_chess_puct_flushes(int32_t sims, int32_t bs) {
     if (sims < 2 || bs < 1) return fail(ZC_EINVAL, "PUCT search needs sims >= 2 and batch_size >= 1");
-    return 1 + (sims - 1 + bs - 1) / bs;
+    return puct_flushes(sims, bs);
 }
 
 }  // extern "C"
 
 namespace {
-zc::ChessParams puct_params(zc_engine *e, int32_t first, int32_t n) {
-    zc::ChessParams p = chess_params(e, first, n, e->px_sims, e->px_c, e->px_bs, 0, 0.0);
-    p.dir_alpha = e->px_alpha;
-    p.dir_eps = e->px_eps;
-    p.seed = e->px_seed;
-    // d_search_no is indexed by game - first_game of the begin call; a launch over a
-    // sub-range [first, first + n) indexes it from its own first game
-    p.search_no = e->px_search_no ? e->px_search_no + (first - e->px_first) : nullptr;
-    return p;
-}
-int check_px(zc_engine *e, int32_t first, int32_t n, int32_t flush, bool need_flush) {
-    if (!e->px_active) return fail(ZC_EINVAL, "no PUCT search in progress (call zc_chess_puct_begin first)");
-    if (first < e->px_first || n < 0 || (int64_t)first + n > (int64_t)e->px_first + e->px_n)
-        return fail(ZC_EINVAL, "games [%d, %d) outside the PUCT search's range", first, first + n);
-    const int nflush = 1 + (e->px_sims - 1 + e->px_bs - 1) / e->px_bs;
-    if (need_flush && (flush < 0 || flush >= nflush)) return fail(ZC_EINVAL, "flush %d outside [0, %d)", flush, nflush);
+// What zc_chess_puct_begin and zc_c4_puct_begin(_reuse) share: the checks, and the search
+// recorded in *s, a copy of the engine's that the caller stores back once its arena exists.
+int puct_begin(const zc_engine *eng, int32_t first, int32_t n, const void *d_roots, int32_t sims, double c_puct,
+               int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no, PuctSearch *s) {
+    if (n && !d_roots) return fail(ZC_EINVAL, "null argument");
+    if (int r = check_search(eng, first, n, sims, c_puct, bs)) return r;
+    if (sims < 2) return fail(ZC_EINVAL, "PUCT search needs sims >= 2 (flush 0 evaluates the root)");
+    if (!(alpha > 0.0f) || !(eps >= 0.0f && eps <= 1.0f)) return fail(ZC_EINVAL, "need alpha > 0 and 0 <= eps <= 1");
+    set_step(*s, first, n, sims, c_puct, bs, puct_flushes(sims, bs));
+    s->alpha = alpha;
+    s->eps = eps;
+    s->seed = seed;
+    s->search_no = d_search_no;
     return ZC_OK;
+}
+
+int check_puct_backup(int32_t flush, int32_t logits_dtype, int32_t rows_per_game) {
+    if (logits_dtype != ZC_F32 && logits_dtype != ZC_F16) return fail(ZC_EINVAL, "logits_dtype must be ZC_F32 or ZC_F16");
+    if (rows_per_game < 0 || (rows_per_game > 0 && flush != 0))
+        return fail(ZC_EINVAL, "rows_per_game must be 0 (batch_size rows), or >= 1 for flush 0 (the roots)");
+    return ZC_OK;
+}
+
+// d_search_no is indexed by game - first_game of the begin call; a launch over a sub-range
+// [first, first + n) indexes it from its own first game
+int32_t *search_no_at(const PuctSearch &s, int32_t first) {
+    return s.search_no ? s.search_no + (first - s.first) : nullptr;
+}
+
+zc::ChessParams puct_params(zc_engine *e, int32_t first, int32_t n) {
+    const PuctSearch &s = e->chess_puct;
+    zc::ChessParams p = chess_params(e, first, n, s.sims, s.c, s.bs, 0, 0.0);
+    p.dir_alpha = s.alpha;
+    p.dir_eps = s.eps;
+    p.seed = s.seed;
+    p.search_no = search_no_at(s, first);
+    return p;
 }
 }  // namespace
 
@@ -1400,23 +1394,13 @@ extern "C" {
 int zc_chess_puct_begin(zc_engine *eng, int32_t first, int32_t n, const zc_chess_state *d_roots, int32_t sims,
                         double c_puct, int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no,
                         void *hip_stream) {
-    if (!eng || (n && !d_roots)) return fail(ZC_EINVAL, "null argument");
-    if (int r = check_search(eng, first, n, sims, c_puct, bs)) return r;
-    if (sims < 2) return fail(ZC_EINVAL, "PUCT search needs sims >= 2 (flush 0 evaluates the root)");
-    if (!(alpha > 0.0f) || !(eps >= 0.0f && eps <= 1.0f)) return fail(ZC_EINVAL, "need alpha > 0 and 0 <= eps <= 1");
+    if (!eng) return fail(ZC_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(eng->mu);
+    PuctSearch s = eng->chess_puct;
+    if (int r = puct_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, &s)) return r;
     ZC_HIP(hipSetDevice(eng->cfg.device));
     if (int r = ensure_chess(eng)) return r;
-    eng->px_first = first;
-    eng->px_n = n;
-    eng->px_sims = sims;
-    eng->px_bs = bs;
-    eng->px_c = c_puct;
-    eng->px_alpha = alpha;
-    eng->px_eps = eps;
-    eng->px_seed = seed;
-    eng->px_search_no = d_search_no;
-    eng->px_active = true;
+    eng->chess_puct = s;
     if (!n) return ZC_OK;
     zc::ChessParams p = puct_params(eng, first, n);
     p.roots = d_roots;
@@ -1427,13 +1411,9 @@ int zc_chess_puct_begin(zc_engine *eng, int32_t first, int32_t n, const zc_chess
 
 int zc_chess_puct_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, zc_chess_state *d_leaves,
                          void *d_planes, int32_t planes_dtype, int32_t *d_counts, void *hip_stream) {
-    if (!eng) return fail(ZC_EINVAL, "null argument");
     if (planes_dtype != ZC_F32 && planes_dtype != ZC_F16 && planes_dtype != ZC_F16_NHWC32)
         return fail(ZC_EINVAL, "planes_dtype must be ZC_F32, ZC_F16 or ZC_F16_NHWC32");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_px(eng, first, n, flush, true)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
+    ZC_STEP_ENTRY(chess_puct, flush, true, true)
     zc::ChessParams p = puct_params(eng, first, n);
     p.flush = flush;
     p.leaves = d_leaves;
@@ -1447,14 +1427,8 @@ int zc_chess_puct_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush
 
 int zc_chess_puct_backup_ex(zc_engine *eng, int32_t first, int32_t n, int32_t flush, const double *d_values,
                             const void *d_logits, int32_t logits_dtype, int32_t rows_per_game, void *hip_stream) {
-    if (!eng || (n && (!d_values || !d_logits))) return fail(ZC_EINVAL, "null argument");
-    if (logits_dtype != ZC_F32 && logits_dtype != ZC_F16) return fail(ZC_EINVAL, "logits_dtype must be ZC_F32 or ZC_F16");
-    if (rows_per_game < 0 || (rows_per_game > 0 && flush != 0))
-        return fail(ZC_EINVAL, "rows_per_game must be 0 (batch_size rows), or >= 1 for flush 0 (the roots)");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_px(eng, first, n, flush, true)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
+    if (int r = check_puct_backup(flush, logits_dtype, rows_per_game)) return r;
+    ZC_STEP_ENTRY(chess_puct, flush, true, d_values && d_logits)
     zc::ChessParams p = puct_params(eng, first, n);
     p.flush = flush;
     p.values = d_values;
@@ -1473,12 +1447,8 @@ int zc_chess_puct_backup(zc_engine *eng, int32_t first, int32_t n, int32_t flush
 
 int zc_chess_puct_end(zc_engine *eng, int32_t first, int32_t n, float temperature, uint16_t *d_move, int32_t *d_na,
                       float *d_prior, zc_game_stats *d_stats, void *hip_stream) {
-    if (!eng || (n && (!d_move || !d_na || !d_stats))) return fail(ZC_EINVAL, "null argument");
     if (!(temperature >= 0.0f)) return fail(ZC_EINVAL, "temperature must be >= 0");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_px(eng, first, n, 0, false)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
+    ZC_STEP_ENTRY(chess_puct, 0, false, d_move && d_na && d_stats)
     zc::ChessParams p = puct_params(eng, first, n);
     p.temperature = temperature;
     p.out_move = d_move;
@@ -1514,56 +1484,39 @@ int ensure_c4p(zc_engine *e) {
     return rc;
 }
 zc::C4PuctParams c4p_params(zc_engine *e, int32_t first, int32_t n) {
+    const PuctSearch &s = e->c4_puct;
     zc::C4PuctParams p{};
     p.first_game = first;
     p.n_games = n;
-    p.sims = e->qx_sims;
-    p.bs = e->qx_bs;
+    p.sims = s.sims;
+    p.bs = s.bs;
     p.M = e->M;
     p.max_batch = e->cfg.max_batch;
-    p.c = e->qx_c;
+    p.c = s.c;
     p.nodes = e->c4p_nodes;
     p.ctl = e->c4p_ctl;
     p.paths = e->c4p_paths;
     p.meta = e->c4p_meta;
-    p.dir_alpha = e->qx_alpha;
-    p.dir_eps = e->qx_eps;
-    p.seed = e->qx_seed;
-    p.search_no = e->qx_search_no ? e->qx_search_no + (first - e->qx_first) : nullptr;
+    p.dir_alpha = s.alpha;
+    p.dir_eps = s.eps;
+    p.seed = s.seed;
+    p.search_no = search_no_at(s, first);
     return p;
-}
-int check_qx(zc_engine *e, int32_t first, int32_t n, int32_t flush, bool need_flush) {
-    if (!e->qx_active) return fail(ZC_EINVAL, "no Connect4 PUCT search in progress (call zc_c4_puct_begin first)");
-    if (first < e->qx_first || n < 0 || (int64_t)first + n > (int64_t)e->qx_first + e->qx_n)
-        return fail(ZC_EINVAL, "games [%d, %d) outside the PUCT search's range", first, first + n);
-    const int nflush = 1 + (e->qx_sims - 1 + e->qx_bs - 1) / e->qx_bs;
-    if (need_flush && (flush < 0 || flush >= nflush)) return fail(ZC_EINVAL, "flush %d outside [0, %d)", flush, nflush);
-    return ZC_OK;
 }
 // zc_c4_puct_begin / zc_c4_puct_begin_reuse: the same validation and search parameters; the
 // reuse form launches the re-root kernel in place of the begin kernel.
 int c4p_begin(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state *d_roots, int32_t sims, double c_puct,
               int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no, bool reuse, int32_t *d_kept,
               void *hip_stream) {
-    if (!eng || (n && !d_roots)) return fail(ZC_EINVAL, "null argument");
-    if (int r = check_search(eng, first, n, sims, c_puct, bs)) return r;
-    if (sims < 2) return fail(ZC_EINVAL, "PUCT search needs sims >= 2 (flush 0 evaluates the root)");
-    if (!(alpha > 0.0f) || !(eps >= 0.0f && eps <= 1.0f)) return fail(ZC_EINVAL, "need alpha > 0 and 0 <= eps <= 1");
+    if (!eng) return fail(ZC_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(eng->mu);
+    PuctSearch s = eng->c4_puct;
+    if (int r = puct_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, &s)) return r;
     ZC_HIP(hipSetDevice(eng->cfg.device));
     if (int r = ensure_c4p(eng)) return r;
     if (reuse && !eng->c4p_remap)
         if (int r = dalloc(eng, &eng->c4p_remap, (size_t)eng->cfg.max_games * (size_t)eng->M)) return r;
-    eng->qx_first = first;
-    eng->qx_n = n;
-    eng->qx_sims = sims;
-    eng->qx_bs = bs;
-    eng->qx_c = c_puct;
-    eng->qx_alpha = alpha;
-    eng->qx_eps = eps;
-    eng->qx_seed = seed;
-    eng->qx_search_no = d_search_no;
-    eng->qx_active = true;
+    eng->c4_puct = s;
     if (!n) return ZC_OK;
     zc::C4PuctParams p = c4p_params(eng, first, n);
     p.roots = d_roots;
@@ -1612,12 +1565,8 @@ int zc_c4_puct_forget(zc_engine *eng, int32_t first, int32_t n, void *hip_stream
 
 int zc_c4_puct_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, zc_c4_state *d_leaves, void *d_planes,
                       int32_t planes_dtype, int32_t *d_counts, void *hip_stream) {
-    if (!eng) return fail(ZC_EINVAL, "null argument");
-    if (planes_dtype != ZC_F32 && planes_dtype != ZC_F16) return fail(ZC_EINVAL, "planes_dtype must be ZC_F32 or ZC_F16");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_qx(eng, first, n, flush, true)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
+    if (int r = check_planes_dtype(planes_dtype)) return r;
+    ZC_STEP_ENTRY(c4_puct, flush, true, true)
     zc::C4PuctParams p = c4p_params(eng, first, n);
     p.flush = flush;
     p.leaves = d_leaves;
@@ -1631,14 +1580,8 @@ int zc_c4_puct_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, z
 
 int zc_c4_puct_backup_ex(zc_engine *eng, int32_t first, int32_t n, int32_t flush, const double *d_values,
                          const void *d_logits, int32_t logits_dtype, int32_t rows_per_game, void *hip_stream) {
-    if (!eng || (n && (!d_values || !d_logits))) return fail(ZC_EINVAL, "null argument");
-    if (logits_dtype != ZC_F32 && logits_dtype != ZC_F16) return fail(ZC_EINVAL, "logits_dtype must be ZC_F32 or ZC_F16");
-    if (rows_per_game < 0 || (rows_per_game > 0 && flush != 0))
-        return fail(ZC_EINVAL, "rows_per_game must be 0 (batch_size rows), or >= 1 for flush 0 (the roots)");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_qx(eng, first, n, flush, true)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
+    if (int r = check_puct_backup(flush, logits_dtype, rows_per_game)) return r;
+    ZC_STEP_ENTRY(c4_puct, flush, true, d_values && d_logits)
     zc::C4PuctParams p = c4p_params(eng, first, n);
     p.flush = flush;
     p.values = d_values;
@@ -1657,12 +1600,8 @@ int zc_c4_puct_backup(zc_engine *eng, int32_t first, int32_t n, int32_t flush, c
 
 int zc_c4_puct_end(zc_engine *eng, int32_t first, int32_t n, float temperature, int32_t *d_move, int32_t *d_na,
                    float *d_prior, zc_game_stats *d_stats, void *hip_stream) {
-    if (!eng || (n && (!d_move || !d_na || !d_stats))) return fail(ZC_EINVAL, "null argument");
     if (!(temperature >= 0.0f)) return fail(ZC_EINVAL, "temperature must be >= 0");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (int r = check_qx(eng, first, n, 0, false)) return r;
-    if (!n) return ZC_OK;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
+    ZC_STEP_ENTRY(c4_puct, 0, false, d_move && d_na && d_stats)
     zc::C4PuctParams p = c4p_params(eng, first, n);
     p.temperature = temperature;
     p.out_move = d_move;
@@ -1673,6 +1612,7 @@ int zc_c4_puct_end(zc_engine *eng, int32_t first, int32_t n, float temperature, 
     ZC_HIP(hipGetLastError());
     return ZC_OK;
 }
+#undef ZC_STEP_ENTRY
 
 int zc_debug_c4_puct_tree(zc_engine *eng, int32_t game, int32_t max_nodes, void *out_nodes, int32_t *out_count) {
     if (!eng || !out_nodes || !out_count) return fail(ZC_EINVAL, "null argument");

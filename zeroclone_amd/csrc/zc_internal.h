@@ -421,36 +421,36 @@ struct zc_engine {
     uint64_t rollout_seed = 0;
     int carry_lo = 0, carry_hi = 0;  // games that may hold a carried self-play move (engine.hip check_carry)
     zc::ChessArena ca;  // allocated on the first chess search
-    // the Connect4 PUCT tree (allocated on the first zc_c4_puct_begin) and its search in progress
+    // the Connect4 PUCT tree (allocated on the first zc_c4_puct_begin)
     zc::C4PNode *c4p_nodes = nullptr;
     int32_t *c4p_ctl = nullptr;
     uint32_t *c4p_paths = nullptr, *c4p_meta = nullptr;
     uint16_t *c4p_remap = nullptr;  // [G][M], allocated on the first zc_c4_puct_begin_reuse
-    int qx_first = 0, qx_n = 0, qx_sims = 0, qx_bs = 0;
-    double qx_c = 0;
-    float qx_alpha = 0, qx_eps = 0;
-    uint64_t qx_seed = 0;
-    int32_t *qx_search_no = nullptr;
-    bool qx_active = false;
-    // the chess PUCT search in progress
-    int px_first = 0, px_n = 0, px_sims = 0, px_bs = 0;
-    double px_c = 0;
-    float px_alpha = 0, px_eps = 0;
-    uint64_t px_seed = 0;
-    int32_t *px_search_no = nullptr;
-    bool px_active = false;
-    // the chess stepwise search in progress
-    int cx_first = 0, cx_n = 0, cx_sims = 0, cx_bs = 0, cx_policy = 0;
-    double cx_c = 0, cx_freedom = 0;
-    bool cx_active = false;
+    // A stepwise search in progress (begin .. end), as its begin call gave it: the entry points'
+    // prefix (for messages), the games [first, first + n), the search parameters and the
+    // number of flushes they make (engine.hip check_step).
+    struct StepSearch {
+        const char *what;
+        int first = 0, n = 0, sims = 0, bs = 0, flushes = 0;
+        double c = 0;
+        bool active = false;
+    };
+    struct ChessValueSearch : StepSearch {
+        int policy = 0;
+        double freedom = 0;
+    };
+    struct PuctSearch : StepSearch {
+        float alpha = 0, eps = 0;
+        uint64_t seed = 0;
+        int32_t *search_no = nullptr;
+    };
+    StepSearch c4_value{"zc_c4_ext"};
+    ChessValueSearch chess_value{{"zc_chess_ext"}};
+    PuctSearch chess_puct{{"zc_chess_puct"}}, c4_puct{{"zc_c4_puct"}};
     // the any-backend search (zc_gen_*): its tree and the search in progress
     zc::GenArena ga;
     int gx_sims = 0, gx_bs = 0;
     double gx_c = 0;
     bool gx_active = false;
-    // the stepwise search in progress (zc_c4_ext_begin .. end)
-    int ext_first = 0, ext_n = 0, ext_sims = 0, ext_bs = 0, ext_flushes_done = 0;
-    double ext_c = 0;
-    bool ext_active = false;
     std::mutex mu;
 };

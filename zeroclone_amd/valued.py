@@ -16,6 +16,9 @@ i*batch_size + j) for the leaf's side to move.  Two value functions are provided
 * `HostValue(value, backend)` — any reference-style Value object: the leaves go to the host
   as c4_backend states and `value.batch(states, backend=backend)` is called once per game
   per flush, as the reference does.  Slow, but it runs any plugin on the GPU tree search.
+
+The chess value search and the two PUCT searches follow the same protocol; `_StepSearch`
+holds what the four share and each class what differs: its begin, select, backup and end.
 """
 from __future__ import annotations
 
@@ -29,18 +32,23 @@ def _stream(dev) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
 
 
+def _ptr(t) -> int:
+    return t.data_ptr() if t is not None else 0
+
+
 def _split_flushes(search, nfl: int, fns: list, first_game: int, select, evaluate_backup):
-    """The flushes of k contiguous game parts, part i on stream i (stream 0: the current one;
-    the others fork from it and join back), fns[i] the part's value / network function.  The
-    parts share no tree, buffer or counter — select and backup of a part touch only its games
-    and its slices of the leaf / plane / count / value buffers, and each fns[i] owns its
-    network buffers — so the order of the launches across parts does not matter, and the GPU
-    runs one part's search kernels beside another part's network.  select(first, n, f, leaves,
-    planes, counts, stream); evaluate_backup(first, n, f, fn, leaves, planes, counts, values,
-    stream) calls fn and backs its output up."""
+    """The flush loop of every stepwise search: the flushes of k contiguous game parts, part i
+    on stream i (stream 0: the current one; the others fork from it and join back), fns[i] the
+    part's value / network function; one function is one part, the whole search on the current
+    stream.  The parts share no tree, buffer or counter — select and backup of a part touch
+    only its games and its slices of the leaf / plane / count / value buffers, and each fns[i]
+    owns its network buffers — so the order of the launches across parts does not matter, and
+    the GPU runs one part's search kernels beside another part's network.  select(first, n, f,
+    leaves, planes, counts, stream); evaluate_backup(first, n, f, fn, leaves, planes, counts,
+    values, stream) calls fn and backs its output up."""
     n, bs, k = search.n, search.bs, len(fns)
     main = torch.cuda.current_stream(search.dev)
-    if getattr(search, "_side", None) is None or len(search._side) < k - 1:
+    if len(search._side) < k - 1:
         search._side = [torch.cuda.Stream(search.dev) for _ in range(k - 1)]
     streams = [main] + search._side[:k - 1]
     for st in streams[1:]:
@@ -63,12 +71,15 @@ def _split_flushes(search, nfl: int, fns: list, first_game: int, select, evaluat
 
 
 def _value_backup(sims: int, bs: int, backup):
-    """evaluate_backup of a value search's part (_split_flushes): the part's network on its
-    leaves (a short last flush on its nb leaves only, NetValue.rows), then backup(first, n,
-    flush, values, stream)."""
+    """evaluate_backup of a value search's part (_split_flushes): fn.flush_values(first, n,
+    flush, stream) where fn has it (values computed on the device from the tree itself), else
+    the part's network on its leaves (a short last flush on its nb leaves only, NetValue.rows),
+    then backup(first, n, flush, values, stream)."""
     def evaluate_backup(first, m, f, fn, lv, pv, cv, vv, st):
-        nb = min(bs, sims - f * bs)
-        if nb < bs and hasattr(fn, "rows") and pv is not None:
+        nb = min(bs, sims - f * bs)   # every game's pending leaves (0 after an error)
+        if hasattr(fn, "flush_values"):
+            v = fn.flush_values(first, m, f, st)
+        elif nb < bs and hasattr(fn, "rows") and pv is not None:
             v = fn.rows(pv, m, bs, nb, vv)
         else:
             v = fn(lv, pv, cv)
@@ -123,9 +134,23 @@ def _warm_parts(search, fns):
             fn(None, search.planes[lo * bs:hi * bs:bs].contiguous(), search.counts[lo:hi])
 
 
-class C4ValuedSearch:
-    def __init__(self, eng: "_native.NativeEngine", n_games: int, batch_size: int = 32,
-                 planes_dtype: torch.dtype = torch.float16, leaves: bool = True, planes: bool = True):
+class _StepSearch:
+    """What the four stepwise searches share: the buffers, the checks and the move
+
+        begin -> [select(f) -> evaluate -> backup(f)] * flushes -> end    (_split_flushes)
+
+    A search class gives the row shapes below and _begin(first, roots, sims, par, stream),
+    _select (as _split_flushes calls it), _evaluate_backup(sims) (the rule for _split_flushes),
+    _end(first, par, stream) and _flushes(sims); par is the move's own parameter, a value
+    search's c or a PUCT search's temperature."""
+    STATE = ""                       # the C struct of a root / leaf row
+    LEAF = ((0,), torch.uint8)       # a leaf row's shape and dtype (the roots' too)
+    PLANES = (0, 0, 0)               # one leaf's planes
+    MOVE = torch.int32
+    NA = 0                           # root visit counts (and priors) per game
+    PRIOR = False
+
+    def _alloc(self, eng, n_games: int, batch_size: int, planes_dtype, leaves: bool = True, planes: bool = True):
         if batch_size > eng.max_batch:
             raise ValueError(f"batch_size {batch_size} > engine max_batch {eng.max_batch}")
         if n_games > eng.max_games:
@@ -133,70 +158,117 @@ class C4ValuedSearch:
         if planes_dtype not in (torch.float16, torch.float32):
             raise ValueError("planes_dtype must be float16 or float32")
         self.eng, self.n, self.bs = eng, n_games, batch_size
-        self.dev = torch.device("cuda", eng.device)
-        L = n_games * batch_size
-        self.leaves = torch.zeros((L, 3), dtype=torch.int64, device=self.dev) if leaves else None
-        self.planes = torch.zeros((L, 2, 6, 7), dtype=planes_dtype, device=self.dev) if planes else None
-        self.counts = torch.zeros(n_games, dtype=torch.int32, device=self.dev)
-        self.values = torch.zeros(L, dtype=torch.float64, device=self.dev)
-        self.move = torch.zeros(n_games, dtype=torch.int32, device=self.dev)
-        self.na = torch.zeros((n_games, 7), dtype=torch.int32, device=self.dev)
-        self.stats = torch.zeros((n_games, _native.STATS_FIELDS), dtype=torch.int64, device=self.dev)
+        self.dev = dev = torch.device("cuda", eng.device)
+        L, (row, row_dtype) = n_games * batch_size, self.LEAF
+        self.leaves = torch.zeros((L, *row), dtype=row_dtype, device=dev) if leaves else None
+        self.planes = torch.zeros((L, *self.PLANES), dtype=planes_dtype, device=dev) if planes else None
+        self.counts = torch.zeros(n_games, dtype=torch.int32, device=dev)
+        self.values = torch.zeros(L, dtype=torch.float64, device=dev)
+        self.move = torch.zeros(n_games, dtype=self.MOVE, device=dev)
+        self.na = torch.zeros((n_games, self.NA), dtype=torch.int32, device=dev)
+        if self.PRIOR:
+            self.prior = torch.zeros((n_games, self.NA), dtype=torch.float32, device=dev)
+        self.stats = torch.zeros((n_games, _native.STATS_FIELDS), dtype=torch.int64, device=dev)
+        self._side = []   # the streams of parts 1.. (_split_flushes)
 
-    def _ptr(self, t):
-        return t.data_ptr() if t is not None else 0
+    def _enqueue(self, roots: torch.Tensor, sims: int, fn, first_game: int, par: float):
+        row, row_dtype = self.LEAF
+        if roots.shape != (self.n, *row) or roots.dtype != row_dtype or not roots.is_contiguous():
+            raise ValueError(f"roots must be a contiguous {str(row_dtype)[6:]} [n_games, {row[0]}] tensor of "
+                             f"{self.STATE} rows")
+        if roots.device != self.dev:
+            raise ValueError("roots must live on the engine's device")
+        s = _stream(self.dev)
+        self._begin(first_game, roots, sims, par, s)
+        fns = list(fn) if isinstance(fn, (list, tuple)) else [fn]
+        _split_flushes(self, self._flushes(sims), fns, first_game, self._select, self._evaluate_backup(sims))
+        self._end(first_game, par, s)
+        return self.move, self.na, self.stats
+
+    def _run(self, *move):
+        self._enqueue(*move)
+        torch.cuda.current_stream(self.dev).synchronize()
+        return self.move, self.na, self.stats
+
+    def _capture(self, roots, sims, fn, first_game, par):
+        side = torch.cuda.Stream(self.dev)
+        side.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(side):  # warm the function's kernels outside capture
+            _warm_parts(self, fn if isinstance(fn, (list, tuple)) else [fn])
+        torch.cuda.current_stream(self.dev).wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._enqueue(roots, sims, fn, first_game, par)
+        return g
+
+
+class _ValueSearch(_StepSearch):
+    """value_fn: one callable, or a list of k callables — then the games are split into k
+    contiguous parts searched on k streams (_split_flushes).  The results are the same."""
+
+    def _flushes(self, sims: int) -> int:
+        return (sims + self.bs - 1) // self.bs
 
     def enqueue(self, roots: torch.Tensor, sims: int, c: float, value_fn, first_game: int = 0):
         """Enqueue one whole move on torch's current stream (no host synchronisation unless
         value_fn makes one)."""
-        if roots.shape != (self.n, 3) or roots.dtype != torch.int64 or not roots.is_contiguous():
-            raise ValueError("roots must be a contiguous int64 [n_games, 3] tensor of zc_c4_state rows")
-        if roots.device != self.dev:
-            raise ValueError("roots must live on the engine's device")
-        s = _stream(self.dev)
-        e, n = self.eng, self.n
-        e.c4_ext_begin(first_game, n, roots.data_ptr(), sims, c, self.bs, s)
-        nfl = (sims + self.bs - 1) // self.bs
-        if isinstance(value_fn, (list, tuple)):   # the games in parts on their own streams (_split_flushes)
-            def select(first, m, f, lv, pv, cv, st):
-                e.c4_ext_select(first, m, f, self._ptr(lv), self._ptr(pv), pv is None or pv.dtype == torch.float16,
-                                cv.data_ptr(), st)
-            _split_flushes(self, nfl, list(value_fn), first_game, select,
-                           _value_backup(sims, self.bs, e.c4_ext_backup))
-            nfl = 0
-        for f in range(nfl):
-            e.c4_ext_select(first_game, n, f, self._ptr(self.leaves), self._ptr(self.planes),
-                            self.planes is None or self.planes.dtype == torch.float16, self.counts.data_ptr(), s)
-            nb = min(self.bs, sims - f * self.bs)   # every game's pending leaves (0 after an error)
-            if nb < self.bs and hasattr(value_fn, "rows") and self.planes is not None:
-                v = value_fn.rows(self.planes, n, self.bs, nb, self.values)   # a short last flush
-            else:
-                v = value_fn(self.leaves, self.planes, self.counts)
-            if v is not self.values:
-                self.values.copy_(v.reshape(-1))
-            e.c4_ext_backup(first_game, n, f, self.values.data_ptr(), _stream(self.dev))
-        e.c4_ext_end(first_game, n, self.move.data_ptr(), self.na.data_ptr(), self.stats.data_ptr(),
-                     _stream(self.dev))
-        return self.move, self.na, self.stats
+        return self._enqueue(roots, sims, value_fn, first_game, c)
 
     def run(self, roots: torch.Tensor, sims: int, c: float, value_fn, first_game: int = 0):
-        self.enqueue(roots, sims, c, value_fn, first_game)
-        torch.cuda.current_stream(self.dev).synchronize()
-        return self.move, self.na, self.stats
+        return self._run(roots, sims, value_fn, first_game, c)
 
     def capture(self, roots: torch.Tensor, sims: int, c: float, value_fn, first_game: int = 0):
         """Capture one move into a HIP graph (value_fn must be capturable, e.g. NetValue).
         Returns the graph; graph.replay() re-runs the move on the current contents of
         `roots` and of the games' RNG streams."""
-        side = torch.cuda.Stream(self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):  # warm the value function's kernels outside capture
-            _warm_parts(self, value_fn if isinstance(value_fn, (list, tuple)) else [value_fn])
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self.enqueue(roots, sims, c, value_fn, first_game)
-        return g
+        return self._capture(roots, sims, value_fn, first_game, c)
+
+
+class _PuctSearch(_StepSearch):
+    """net_fn: one callable, or a list of k callables — then the games are split into k
+    contiguous parts searched on k streams (_split_flushes): one part's select, backup and
+    policy GEMM overlap another part's tower.  The results are the same."""
+    PRIOR = True
+
+    def _alloc_puct(self, eng, n_games, batch_size, c_puct, alpha, eps, seed, planes_dtype, leaves):
+        self._alloc(eng, n_games, batch_size, planes_dtype, leaves)
+        self.c, self.alpha, self.eps, self.seed = c_puct, alpha, eps, seed
+        # per-game search number: the Philox counter word of the root noise and the
+        # temperature sample; each search adds 1 on the device (graph replays included)
+        self.search_no = torch.zeros(n_games, dtype=torch.int32, device=self.dev)
+
+    def _flushes(self, sims: int) -> int:
+        return _native.check(_native.lib().zc_chess_puct_flushes(int(sims), int(self.bs)))
+
+    def enqueue(self, roots: torch.Tensor, sims: int, net_fn, temperature: float = 0.0, first_game: int = 0):
+        return self._enqueue(roots, sims, net_fn, first_game, temperature)
+
+    def run(self, roots, sims, net_fn, temperature: float = 0.0, first_game: int = 0):
+        return self._run(roots, sims, net_fn, first_game, temperature)
+
+    def capture(self, roots, sims, net_fn, temperature: float = 0.0, first_game: int = 0):
+        return self._capture(roots, sims, net_fn, first_game, temperature)
+
+
+class C4ValuedSearch(_ValueSearch):
+    STATE, LEAF, PLANES, MOVE, NA = "zc_c4_state", ((3,), torch.int64), (2, 6, 7), torch.int32, 7
+
+    def __init__(self, eng: "_native.NativeEngine", n_games: int, batch_size: int = 32,
+                 planes_dtype: torch.dtype = torch.float16, leaves: bool = True, planes: bool = True):
+        self._alloc(eng, n_games, batch_size, planes_dtype, leaves, planes)
+
+    def _begin(self, first, roots, sims, c, s):
+        self.eng.c4_ext_begin(first, self.n, roots.data_ptr(), sims, c, self.bs, s)
+
+    def _select(self, first, m, f, lv, pv, cv, s):
+        self.eng.c4_ext_select(first, m, f, _ptr(lv), _ptr(pv), pv is None or pv.dtype == torch.float16,
+                               cv.data_ptr(), s)
+
+    def _evaluate_backup(self, sims):
+        return _value_backup(sims, self.bs, self.eng.c4_ext_backup)
+
+    def _end(self, first, c, s):
+        self.eng.c4_ext_end(first, self.n, self.move.data_ptr(), self.na.data_ptr(), self.stats.data_ptr(), s)
 
 
 class NetValue:
@@ -252,77 +324,42 @@ class HostValue:
         return torch.from_numpy(out).to(leaves.device)
 
 
-class ChessValuedSearch:
+class ChessValuedSearch(_ValueSearch):
     """Stepwise chess search (zc_chess_ext_*): the configs/chess_value.yaml path — a value
     network evaluates every flush's leaves (planes [n*bs, 17, 8, 8]) between the select and
     backup kernels.  Same protocol and value_fn contract as C4ValuedSearch."""
+    STATE, LEAF, PLANES, MOVE, NA = ("zc_chess_state", ((72,), torch.uint8), (17, 8, 8), torch.int16,
+                                     _native.CHESS_MAX_MOVES)
 
     def __init__(self, eng: "_native.NativeEngine", n_games: int, batch_size: int = 32,
                  planes_dtype: torch.dtype = torch.float16, leaves: bool = True, planes: bool = True,
                  policy: int = _native.ZC_POLICY_RANDOM, freedom: float = 0.0):
-        if batch_size > eng.max_batch:
-            raise ValueError(f"batch_size {batch_size} > engine max_batch {eng.max_batch}")
-        if n_games > eng.max_games:
-            raise ValueError(f"{n_games} games > engine capacity {eng.max_games}")
-        self.eng, self.n, self.bs, self.policy, self.freedom = eng, n_games, batch_size, policy, freedom
+        self._alloc(eng, n_games, batch_size, planes_dtype, leaves, planes)
+        self.policy, self.freedom = policy, freedom
         eng.chess_reserve()   # the tree arena exists before any graph capture
-        self.dev = torch.device("cuda", eng.device)
-        L = n_games * batch_size
-        self.leaves = torch.zeros((L, 72), dtype=torch.uint8, device=self.dev) if leaves else None
-        self.planes = torch.zeros((L, 17, 8, 8), dtype=planes_dtype, device=self.dev) if planes else None
-        self.counts = torch.zeros(n_games, dtype=torch.int32, device=self.dev)
-        self.values = torch.zeros(L, dtype=torch.float64, device=self.dev)
-        self.move = torch.zeros(n_games, dtype=torch.int16, device=self.dev)
-        self.na = torch.zeros((n_games, _native.CHESS_MAX_MOVES), dtype=torch.int32, device=self.dev)
-        self.stats = torch.zeros((n_games, _native.STATS_FIELDS), dtype=torch.int64, device=self.dev)
 
-    def enqueue(self, roots: torch.Tensor, sims: int, c: float, value_fn, first_game: int = 0):
-        if roots.shape != (self.n, 72) or roots.dtype != torch.uint8 or not roots.is_contiguous():
-            raise ValueError("roots must be a contiguous uint8 [n_games, 72] tensor of zc_chess_state rows")
-        e, n = self.eng, self.n
-        p = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
-        e.chess_ext_begin(first_game, n, roots.data_ptr(), sims, c, self.bs, self.policy, self.freedom,
-                          _stream(self.dev))
-        nfl = (sims + self.bs - 1) // self.bs
-        if isinstance(value_fn, (list, tuple)):   # the games in parts on their own streams (_split_flushes)
-            def select(first, m, f, lv, pv, cv, st):
-                e.chess_ext_select(first, m, f, p(lv), p(pv), pv is None or pv.dtype == torch.float16,
-                                   cv.data_ptr(), st)
-            _split_flushes(self, nfl, list(value_fn), first_game, select,
-                           _value_backup(sims, self.bs, e.chess_ext_backup))
-            nfl = 0
-        for f in range(nfl):
-            e.chess_ext_select(first_game, n, f, p(self.leaves), p(self.planes),
-                               self.planes is None or self.planes.dtype == torch.float16, self.counts.data_ptr(),
-                               _stream(self.dev))
-            nb = min(self.bs, sims - f * self.bs)   # every game's pending leaves (0 after an error)
-            if hasattr(value_fn, "flush_values"):   # values computed on the device from the tree itself
-                v = value_fn.flush_values(first_game, n, f, _stream(self.dev))
-            elif nb < self.bs and hasattr(value_fn, "rows") and self.planes is not None:
-                v = value_fn.rows(self.planes, n, self.bs, nb, self.values)   # a short last flush
-            else:
-                v = value_fn(self.leaves, self.planes, self.counts)
-            if v is not self.values:
-                self.values.copy_(v.reshape(-1))
-            e.chess_ext_backup(first_game, n, f, self.values.data_ptr(), _stream(self.dev))
-        e.chess_ext_end(first_game, n, self.move.data_ptr(), self.na.data_ptr(), self.stats.data_ptr(),
-                        _stream(self.dev))
-        return self.move, self.na, self.stats
+    def _begin(self, first, roots, sims, c, s):
+        self.eng.chess_ext_begin(first, self.n, roots.data_ptr(), sims, c, self.bs, self.policy, self.freedom, s)
 
-    def run(self, roots: torch.Tensor, sims: int, c: float, value_fn, first_game: int = 0):
-        self.enqueue(roots, sims, c, value_fn, first_game)
-        torch.cuda.current_stream(self.dev).synchronize()
-        return self.move, self.na, self.stats
+    def _select(self, first, m, f, lv, pv, cv, s):
+        self.eng.chess_ext_select(first, m, f, _ptr(lv), _ptr(pv), pv is None or pv.dtype == torch.float16,
+                                  cv.data_ptr(), s)
 
-    capture = C4ValuedSearch.capture
+    def _evaluate_backup(self, sims):
+        return _value_backup(sims, self.bs, self.eng.chess_ext_backup)
+
+    def _end(self, first, c, s):
+        self.eng.chess_ext_end(first, self.n, self.move.data_ptr(), self.na.data_ptr(), self.stats.data_ptr(), s)
 
 
-class ChessPuctSearch:
+class ChessPuctSearch(_PuctSearch):
     """AlphaZero-style PUCT search for chess (zc_chess_puct_*).
 
     net_fn(leaves, planes, counts) -> (values fp64 [n*bs], logits [n*bs, 4096] fp32/fp16,
     index from*64 + to).  Flush 0 evaluates the roots; Dirichlet(alpha) noise of weight eps
     goes on the root priors; end() picks by visits (temperature 0) or samples."""
+    STATE, LEAF, PLANES, MOVE, NA = ChessValuedSearch.STATE, ChessValuedSearch.LEAF, (17, 8, 8), torch.int16, \
+        _native.CHESS_MAX_MOVES
 
     def __init__(self, eng: "_native.NativeEngine", n_games: int, batch_size: int = 32, c_puct: float = 1.5,
                  dirichlet_alpha: float = 0.3, dirichlet_eps: float = 0.25, seed: int = 0,
@@ -330,82 +367,31 @@ class ChessPuctSearch:
         """planes_nhwc: the select kernel writes the planes in the MFMA tower's input layout, fp16
         [n * batch_size, 64, 32] (17 planes then zeros, square-major), so the network takes them
         without a conversion launch (MfmaPolicyValueNetwork with the convolutional head)."""
-        if batch_size > eng.max_batch:
-            raise ValueError(f"batch_size {batch_size} > engine max_batch {eng.max_batch}")
         if planes_nhwc and planes_dtype != torch.float16:
             raise ValueError("planes_nhwc needs fp16 planes")
-        self.eng, self.n, self.bs = eng, n_games, batch_size
-        self.c, self.alpha, self.eps, self.seed = c_puct, dirichlet_alpha, dirichlet_eps, seed
-        eng.chess_reserve()   # the tree arena exists before any graph capture
-        self.dev = torch.device("cuda", eng.device)
-        L = n_games * batch_size
         self.planes_nhwc = planes_nhwc
-        self.leaves = torch.zeros((L, 72), dtype=torch.uint8, device=self.dev) if leaves else None
-        self.planes = torch.zeros((L, 64, 32) if planes_nhwc else (L, 17, 8, 8), dtype=planes_dtype, device=self.dev)
-        self.counts = torch.zeros(n_games, dtype=torch.int32, device=self.dev)
-        self.values = torch.zeros(L, dtype=torch.float64, device=self.dev)
-        self.move = torch.zeros(n_games, dtype=torch.int16, device=self.dev)
-        self.na = torch.zeros((n_games, _native.CHESS_MAX_MOVES), dtype=torch.int32, device=self.dev)
-        self.prior = torch.zeros((n_games, _native.CHESS_MAX_MOVES), dtype=torch.float32, device=self.dev)
-        self.stats = torch.zeros((n_games, _native.STATS_FIELDS), dtype=torch.int64, device=self.dev)
-        # per-game search number: the Philox counter word of the root noise and the
-        # temperature sample; each search adds 1 on the device (graph replays included)
-        self.search_no = torch.zeros(n_games, dtype=torch.int32, device=self.dev)
+        if planes_nhwc:
+            self.PLANES = (64, 32)
+        self._alloc_puct(eng, n_games, batch_size, c_puct, dirichlet_alpha, dirichlet_eps, seed, planes_dtype, leaves)
+        eng.chess_reserve()   # the tree arena exists before any graph capture
 
-    def enqueue(self, roots: torch.Tensor, sims: int, net_fn, temperature: float = 0.0, first_game: int = 0):
-        """net_fn: one callable, or a list of k callables — then the games are split into k
-        contiguous parts searched on k streams (`_enqueue_split`): one part's select, backup
-        and policy GEMM overlap another part's tower.  The results are the same."""
-        e, n = self.eng, self.n
-        p = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
-        nfl = _native.check(_native.lib().zc_chess_puct_flushes(int(sims), int(self.bs)))
-        e.chess_puct_begin(first_game, n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps, self.seed,
-                           self.search_no.data_ptr(), stream=_stream(self.dev))
-        if isinstance(net_fn, (list, tuple)):
-            self._enqueue_split(nfl, list(net_fn), first_game)
-            e.chess_puct_end(first_game, n, temperature, self.move.data_ptr(), self.na.data_ptr(),
-                             self.prior.data_ptr(), self.stats.data_ptr(), _stream(self.dev))
-            return self.move, self.na, self.stats
-        evaluate_backup = _puct_backup(self.bs, e.chess_puct_backup)
-        for f in range(nfl):
-            e.chess_puct_select(first_game, n, f, p(self.leaves), p(self.planes),
-                                self.planes.dtype == torch.float16, self.counts.data_ptr(), _stream(self.dev),
-                                planes_nhwc=self.planes_nhwc)
-            evaluate_backup(first_game, n, f, net_fn, self.leaves, self.planes, self.counts, self.values,
-                            _stream(self.dev))
-        e.chess_puct_end(first_game, n, temperature, self.move.data_ptr(), self.na.data_ptr(), self.prior.data_ptr(),
-                         self.stats.data_ptr(), _stream(self.dev))
-        return self.move, self.na, self.stats
+    def _begin(self, first, roots, sims, temperature, s):
+        self.eng.chess_puct_begin(first, self.n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps,
+                                  self.seed, self.search_no.data_ptr(), stream=s)
 
-    def _enqueue_split(self, nfl: int, fns: list, first_game: int):
-        """The search split over len(fns) streams (_split_flushes): one part's select and
-        backup beside another part's tower."""
-        e = self.eng
+    def _select(self, first, m, f, lv, pv, cv, s):
+        self.eng.chess_puct_select(first, m, f, _ptr(lv), pv.data_ptr(), pv.dtype == torch.float16, cv.data_ptr(), s,
+                                   planes_nhwc=self.planes_nhwc)
 
-        def select(first, n, f, lv, pv, cv, s):
-            e.chess_puct_select(first, n, f, lv.data_ptr() if lv is not None else 0, pv.data_ptr(),
-                                pv.dtype == torch.float16, cv.data_ptr(), s, planes_nhwc=self.planes_nhwc)
+    def _evaluate_backup(self, sims):
+        return _puct_backup(self.bs, self.eng.chess_puct_backup)
 
-        _split_flushes(self, nfl, fns, first_game, select, _puct_backup(self.bs, e.chess_puct_backup))
-
-    def run(self, roots, sims, net_fn, temperature: float = 0.0, first_game: int = 0):
-        self.enqueue(roots, sims, net_fn, temperature, first_game)
-        torch.cuda.current_stream(self.dev).synchronize()
-        return self.move, self.na, self.stats
-
-    def capture(self, roots, sims, net_fn, temperature: float = 0.0, first_game: int = 0):
-        side = torch.cuda.Stream(self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):
-            _warm_parts(self, net_fn if isinstance(net_fn, (list, tuple)) else [net_fn])
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self.enqueue(roots, sims, net_fn, temperature, first_game)
-        return g
+    def _end(self, first, temperature, s):
+        self.eng.chess_puct_end(first, self.n, temperature, self.move.data_ptr(), self.na.data_ptr(),
+                                self.prior.data_ptr(), self.stats.data_ptr(), s)
 
 
-class C4PuctSearch:
+class C4PuctSearch(_PuctSearch):
     """AlphaZero-style PUCT search for Connect4 (zc_c4_puct_*, SURVEY §8 a21 on the target
     game): the chess PUCT search's selection, virtual loss, Dirichlet root noise and
     temperature on the Connect4 rules.
@@ -418,26 +404,13 @@ class C4PuctSearch:
     previous search holds it one or two plies below its root (zc_c4_puct_begin_reuse), and then
     adds sims - 1 visits below the kept ones; `kept` [n] int32 = nodes kept (0: a fresh tree).
     The engine needs max_sims above sims for anything to be kept; forget() drops the trees."""
+    STATE, LEAF, PLANES, MOVE, NA = C4ValuedSearch.STATE, C4ValuedSearch.LEAF, (2, 6, 7), torch.int32, 7
 
     def __init__(self, eng: "_native.NativeEngine", n_games: int, batch_size: int = 32, c_puct: float = 1.5,
                  dirichlet_alpha: float = 0.3, dirichlet_eps: float = 0.25, seed: int = 0,
                  planes_dtype: torch.dtype = torch.float16, leaves: bool = True, reuse: bool = False):
-        if batch_size > eng.max_batch:
-            raise ValueError(f"batch_size {batch_size} > engine max_batch {eng.max_batch}")
-        self.eng, self.n, self.bs = eng, n_games, batch_size
+        self._alloc_puct(eng, n_games, batch_size, c_puct, dirichlet_alpha, dirichlet_eps, seed, planes_dtype, leaves)
         self.reuse = bool(reuse)
-        self.c, self.alpha, self.eps, self.seed = c_puct, dirichlet_alpha, dirichlet_eps, seed
-        self.dev = torch.device("cuda", eng.device)
-        L = n_games * batch_size
-        self.leaves = torch.zeros((L, 3), dtype=torch.int64, device=self.dev) if leaves else None
-        self.planes = torch.zeros((L, 2, 6, 7), dtype=planes_dtype, device=self.dev)
-        self.counts = torch.zeros(n_games, dtype=torch.int32, device=self.dev)
-        self.values = torch.zeros(L, dtype=torch.float64, device=self.dev)
-        self.move = torch.zeros(n_games, dtype=torch.int32, device=self.dev)
-        self.na = torch.zeros((n_games, 7), dtype=torch.int32, device=self.dev)
-        self.prior = torch.zeros((n_games, 7), dtype=torch.float32, device=self.dev)
-        self.stats = torch.zeros((n_games, _native.STATS_FIELDS), dtype=torch.int64, device=self.dev)
-        self.search_no = torch.zeros(n_games, dtype=torch.int32, device=self.dev)   # as ChessPuctSearch
         # the tree arena exists before any graph capture
         z = torch.zeros((1, 3), dtype=torch.int64, device=self.dev)
         eng.c4_puct_begin(0, 0, z.data_ptr(), 2, c_puct, batch_size, dirichlet_alpha, dirichlet_eps, seed)
@@ -452,32 +425,20 @@ class C4PuctSearch:
         games), stream-ordered: their next search starts afresh."""
         self.eng.c4_puct_forget(first_game, self.n if n is None else n, _stream(self.dev))
 
-    def enqueue(self, roots: torch.Tensor, sims: int, net_fn, temperature: float = 0.0, first_game: int = 0):
-        e, n = self.eng, self.n
-        p = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
-        nfl = _native.check(_native.lib().zc_chess_puct_flushes(int(sims), int(self.bs)))
+    def _begin(self, first, roots, sims, temperature, s):
+        e, args = self.eng, (first, self.n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps, self.seed,
+                             self.search_no.data_ptr())
         if self.reuse:
-            e.c4_puct_begin_reuse(first_game, n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps,
-                                  self.seed, self.search_no.data_ptr(), self.kept.data_ptr(), stream=_stream(self.dev))
+            e.c4_puct_begin_reuse(*args, self.kept.data_ptr(), stream=s)
         else:
-            e.c4_puct_begin(first_game, n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps, self.seed,
-                            self.search_no.data_ptr(), stream=_stream(self.dev))
-        if isinstance(net_fn, (list, tuple)):   # split over streams, as ChessPuctSearch
-            def select(first, m, f, lv, pv, cv, s):
-                e.c4_puct_select(first, m, f, lv.data_ptr() if lv is not None else 0, pv.data_ptr(),
-                                 pv.dtype == torch.float16, cv.data_ptr(), s)
+            e.c4_puct_begin(*args, stream=s)
 
-            _split_flushes(self, nfl, list(net_fn), first_game, select, _puct_backup(self.bs, e.c4_puct_backup))
-            nfl = 0
-        evaluate_backup = _puct_backup(self.bs, e.c4_puct_backup)
-        for f in range(nfl):
-            e.c4_puct_select(first_game, n, f, p(self.leaves), p(self.planes), self.planes.dtype == torch.float16,
-                             self.counts.data_ptr(), _stream(self.dev))
-            evaluate_backup(first_game, n, f, net_fn, self.leaves, self.planes, self.counts, self.values,
-                            _stream(self.dev))
-        e.c4_puct_end(first_game, n, temperature, self.move.data_ptr(), self.na.data_ptr(), self.prior.data_ptr(),
-                      self.stats.data_ptr(), _stream(self.dev))
-        return self.move, self.na, self.stats
+    def _select(self, first, m, f, lv, pv, cv, s):
+        self.eng.c4_puct_select(first, m, f, _ptr(lv), pv.data_ptr(), pv.dtype == torch.float16, cv.data_ptr(), s)
 
-    run = ChessPuctSearch.run
-    capture = ChessPuctSearch.capture
+    def _evaluate_backup(self, sims):
+        return _puct_backup(self.bs, self.eng.c4_puct_backup)
+
+    def _end(self, first, temperature, s):
+        self.eng.c4_puct_end(first, self.n, temperature, self.move.data_ptr(), self.na.data_ptr(),
+                             self.prior.data_ptr(), self.stats.data_ptr(), s)
