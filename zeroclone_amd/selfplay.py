@@ -3,7 +3,8 @@
 `C4SelfPlay` / `ChessSelfPlay` are the batched form of scripts/train.py:simulate_games
 (:151-170) + Engine.play_mcts_parallel (engine/engine.py:131-138): G games live on one GPU;
 one `step()` searches every game, plays the chosen moves and evaluates them
-(Engine.play_move/_evaluate) on the device.  Game slot g of rank r is global slot r*G + g
+(Engine.play_move/_evaluate) on the device; both are `_SelfPlayPool` with the game's launches
+filled in.  Game slot g of rank r is global slot r*G + g
 and draws from its own CPython MT19937 stream seeded seed + global slot id, so per-game
 results do not depend on the number of GPUs.
 
@@ -27,7 +28,7 @@ import os
 import numpy as np
 import torch
 
-from . import _native
+from . import _native, valued
 
 ONGOING = _native.ZC_C4_ONGOING
 IDLE = _native.ZC_SLOT_IDLE
@@ -356,28 +357,8 @@ def _room(traj, stream: int | None = None):
         traj.ensure_room()
 
 
-def _check_record_policy(record_policy: bool, sims: int, record: bool = True):
-    """A policy entry's count field is 16 bits, and the entries ride on the trajectories."""
-    if not record_policy:
-        return
-    if sims > _native.ZC_TRAJ_PI_MAX_COUNT:
-        raise ValueError(f"record_policy stores visit counts in 16 bits: sims {sims} > {_native.ZC_TRAJ_PI_MAX_COUNT}")
-    if not record:
-        raise ValueError("record_policy needs the trajectory recorder (record=True)")
-
-
 _NO_FUSED_POLICY = ("the fused multi-step launches export no per-move visit counts: with record_policy=True "
                     "play with step()")
-
-
-def _adopt_policy(t: "Trajectories", o: "Trajectories"):
-    """adopt(): the games in progress bring their recorded visit counts along."""
-    if t.policy_width is None:
-        return
-    if o.policy_width != t.policy_width or o.pi_slot_cap != t.pi_slot_cap:
-        raise ValueError("adopt() with record_policy needs a pool recording the policy with the same pi_slot_cap")
-    t.slot_pi.copy_(o.slot_pi)
-    t.slot_off.copy_(o.slot_off)
 
 
 def _warm(search, fn, sims: int):
@@ -385,9 +366,8 @@ def _warm(search, fn, sims: int):
     roots shape: valued._warm_parts), and once at the short last flush's shape
     (NetValue.rows) when the simulations are not a multiple of the batch: kernels loaded and
     buffers allocated before a graph capture."""
-    from .valued import _warm_parts
     fns = list(fn) if isinstance(fn, (list, tuple)) else [fn]
-    _warm_parts(search, fns)
+    valued._warm_parts(search, fns)
     nb, k, n, bs = sims % search.bs, len(fns), search.n, search.bs
     for i, f in enumerate(fns):
         lo, hi = i * n // k, (i + 1) * n // k
@@ -395,209 +375,109 @@ def _warm(search, fn, sims: int):
             f.rows(search.planes[lo * bs:hi * bs], hi - lo, bs, nb, search.values[lo * bs:hi * bs])
 
 
-class C4SelfPlay:
-    """Connect4 self-play pool on one GPU: search (zc_c4_search_async) + play/evaluate
-    (zc_c4_play_async) + trajectory recording (zc_traj_record_async), all stream-ordered,
-    no host synchronisation per step.  With `net=` the search takes its leaf values from a
-    value network (C4ValuedSearch, C2(iii)); with `puct_net=` it is the PUCT search with a
-    policy + value network (C4PuctSearch, SURVEY §8 a21), moves sampled at `temperature`;
-    both step() only (the network runs between kernels) and capture_step() into one graph."""
+class _SelfPlayPool:
+    """What `C4SelfPlay` and `ChessSelfPlay` share: G games of one GPU, the engine and its game
+    streams, the three-way search choice of a step (the game's own search kernel, a value
+    network, PUCT), the recorder, the captured step graph and the fused multi-move launches.
 
-    MAX_LEN = 43   # the opening + at most 42 moves
+    A game supplies the attributes below, its state (`roots`, `moves`, ... and `start()`) and
+    four launches: `_search` (its own search kernel into moves / na / stats), `_root_moves`
+    (the move list that names a root's visit counts), `_play` (play the searched moves; returns
+    what `Trajectories.record` is to be given) and `_launch` (a fused multi-move launch);
+    `_adopt_state` is its share of `adopt()`."""
 
-    def __init__(self, games: int, sims: int, c: float = 1.4, batch_size: int = 32, seed: int = 0,
-                 rank: int = 0, device: int = 0, record: bool = True, games_cap: int | None = None,
-                 net=None, puct_net=None, temperature: float = 1.0, puct_seed: int = 1, streams: int = 1,
-                 record_policy: bool = False, pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
-                 reuse_tree: bool = False, tree_nodes: int | None = None):
-        """record_policy: every step()'s root visit counts go with the positions into the
-        trajectories (TrajBatch.pi / policy_targets(7)), in every search mode.
-        reuse_tree (PUCT mode): each search keeps the subtree of the move just played
-        (C4PuctSearch(reuse=True)) and adds sims - 1 visits to it; a tree holds up to
-        `tree_nodes` nodes (default min(2 * sims, 65534)), and a search whose kept nodes leave
-        no room for its own starts afresh.  start() and adopt() drop the kept trees."""
-        _check_record_policy(record_policy, sims, record)
-        if reuse_tree:
-            if puct_net is None:
-                raise ValueError("reuse_tree keeps the PUCT search's tree: it needs puct_net")
-            # a kept root carries the visits of every earlier search of its game: at most 42 searches
-            if record_policy and 42 * sims > _native.ZC_TRAJ_PI_MAX_COUNT:
-                raise ValueError(f"record_policy stores visit counts in 16 bits: with reuse_tree a root can hold "
-                                 f"42 * sims = {42 * sims} > {_native.ZC_TRAJ_PI_MAX_COUNT} visits")
-        self.reuse_tree = bool(reuse_tree)
+    MOVE_DTYPE: torch.dtype   # of `moves`, as the game's kernels write them
+    NA_WIDTH: int        # moves per root: na's row
+    POLICY_WIDTH: int    # Trajectories(policy_width=...)
+    POOL_ROWS: int       # pooled positions reserved per game of games_cap
+    FUSED_SEARCH: str    # the search of run() / run_pooled(), for their refusal
+    record = True        # Connect4 alone can play unrecorded
+
+    def __init__(self, games: int, sims: int, c: float, batch_size: int, seed: int, rank: int, device,
+                 temperature: float, record_policy: bool, init_row: torch.Tensor, max_len: int,
+                 games_cap: int | None, pi_slot_cap: int | None, pi_pool_cap: int | None,
+                 record: bool = True, max_sims: int | None = None):
+        """The refusals come before the engine: they need no GPU."""
+        if record_policy and sims > _native.ZC_TRAJ_PI_MAX_COUNT:   # an entry's count field is 16 bits
+            raise ValueError(f"record_policy stores visit counts in 16 bits: sims {sims} > "
+                             f"{_native.ZC_TRAJ_PI_MAX_COUNT}")
+        if record_policy and not record:   # the entries ride on the trajectories
+            raise ValueError("record_policy needs the trajectory recorder (record=True)")
         self.record_policy = bool(record_policy)
         self.G, self.sims, self.c, self.bs = games, sims, c, batch_size
         self.dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        max_sims = (tree_nodes or min(2 * sims, 65534)) if reuse_tree else sims
-        self.eng = _native.NativeEngine(max_games=games, max_sims=max_sims, max_batch=batch_size,
+        self.eng = _native.NativeEngine(max_games=games, max_sims=max_sims or sims, max_batch=batch_size,
                                         device=self.dev.index or 0)
         self.first_id = rank * games
         self.eng.seed(0, [seed + self.first_id + g for g in range(games)])
-        self.roots = torch.zeros((games, 3), dtype=torch.int64, device=self.dev)
-        self.moves = torch.zeros(games, dtype=torch.int32, device=self.dev)
-        self.moves16 = torch.zeros(games, dtype=torch.int16, device=self.dev)
-        self.na = torch.zeros((games, 7), dtype=torch.int32, device=self.dev)
+        self.moves = torch.zeros(games, dtype=self.MOVE_DTYPE, device=self.dev)
+        self.na = torch.zeros((games, self.NA_WIDTH), dtype=torch.int32, device=self.dev)
         self.stats = torch.zeros((games, _native.STATS_FIELDS), dtype=torch.int64, device=self.dev)
         self.results = torch.zeros(games, dtype=torch.int32, device=self.dev)
-        self.record = record
+        self.totals = torch.zeros(2, dtype=torch.int64, device=self.dev)   # expansions, depth sum since reset
         self.traj = None
         if record:
             cap = games_cap or max(8 * games, 1024)
-            self.traj = Trajectories(games, torch.zeros(24, dtype=torch.uint8), self.MAX_LEN, cap,
-                                     cap * self.MAX_LEN, self.dev, policy_width=7 if record_policy else None,
+            self.traj = Trajectories(games, init_row, max_len, cap, cap * self.POOL_ROWS, self.dev,
+                                     policy_width=self.POLICY_WIDTH if record_policy else None,
                                      pi_slot_cap=pi_slot_cap, pi_pool_cap=pi_pool_cap)
-        self.totals = torch.zeros(2, dtype=torch.int64, device=self.dev)   # expansions, depth sum since reset
-        self.carry_pending = False   # run_pooled(carry=True) left moves in flight (drain() finishes them)
         self.vs = self.value_fn = self.ps = self.net_fn = None
         self.temperature = float(temperature)
-        if net is not None:
-            from .valued import C4ValuedSearch, NetValue
-            self.vs = C4ValuedSearch(self.eng, games, batch_size, leaves=False)
-            self.value_fn = NetValue(net)
-            if streams > 1:   # the games in parts on their own streams (valued._split_flushes)
-                self.value_fn = [NetValue(net.replica() if hasattr(net, "replica") else net) for _ in range(streams)]
-        if puct_net is not None:
-            from .valued import C4PuctSearch, PolicyNet
-            self.ps = C4PuctSearch(self.eng, games, batch_size, seed=puct_seed, leaves=False, reuse=self.reuse_tree)
-            self.net_fn = PolicyNet(puct_net)
-            if streams > 1:
-                self.net_fn = [PolicyNet(puct_net.replica()) for _ in range(streams)]
+        self._run_k = self._ticket = None
 
-    def start(self, quota: int | None = None):
-        """Every slot back to the opening; with a quota, slots beyond it idle and finished
-        slots start new games only while fewer than `quota` have started."""
-        if self.carry_pending:   # the games restart: their carried moves are dropped
-            # (after every stream's launches: the carry launch may have run on a caller's stream)
-            torch.cuda.synchronize(self.dev)
-            self.eng.c4_carry_discard(0, self.G, torch.cuda.current_stream(self.dev).cuda_stream)
-            self.carry_pending = False
-        self.roots.zero_()
-        if self.reuse_tree:
-            self.ps.forget()
-        if self.traj is not None:
-            self.traj.start(quota, games_cap=quota)
+    def _networks(self, net, value_search, value_kw: dict, streams: int,
+                  puct_net, puct_search, puct_kw: dict, puct_streams: int):
+        """`net=`: the value search and its network; `puct_net=`: the PUCT search and its.  With
+        more than one stream, a list of replicas: the games in parts on their own streams
+        (valued._split_flushes)."""
+        if net is not None:
+            self.vs = value_search(self.eng, self.G, self.bs, leaves=False, **value_kw)
+            self.value_fn = valued.NetValue(net)
+            if streams > 1:
+                self.value_fn = [valued.NetValue(net.replica() if hasattr(net, "replica") else net)
+                                 for _ in range(streams)]
+        if puct_net is not None:
+            self.ps = puct_search(self.eng, self.G, self.bs, leaves=False, **puct_kw)
+            self.net_fn = valued.PolicyNet(puct_net)
+            if puct_streams > 1:
+                self.net_fn = [valued.PolicyNet(puct_net.replica()) for _ in range(puct_streams)]
+
+    def _stream(self, stream: int | None) -> int:
+        return stream if stream is not None else torch.cuda.current_stream(self.dev).cuda_stream
 
     def step(self, stream: int | None = None) -> torch.Tensor:
         """One move for every game (on torch's current stream unless given); returns the
         per-game results tensor (ONGOING = 2, IDLE = 3).  Finished games restart from the
-        opening."""
+        initial position."""
         _room(self.traj, stream)
         self.step_search(stream)
         return self.step_finish(stream)
 
-    def run(self, moves: int, stream: int | None = None, kernel_done=None) -> torch.Tensor:
-        """`moves` moves for every game in ONE launch (zc_c4_selfplay_async: each game at its
-        own pace, finished games refilled from the opening in the kernel), then the
-        trajectory recording of every step, in step order — the same games, pool and labels
-        as `moves` calls of step().  Needs the unlimited quota (start(None)): with a quota the
-        refill depends on other slots' finishes, which step() decides once per step.
-        Returns the per-step results [moves, G]; self.stats sums the moves' counters."""
-        if self.record_policy:
-            raise ValueError(_NO_FUSED_POLICY)
-        if self.traj is not None and self.traj.quota != _UNLIMITED:
-            raise ValueError("run() plays without a game quota; use step() under simulate_games' quota")
-        if self.vs is not None or self.ps is not None:
-            raise ValueError("run() fuses the rollout search; network modes step()")
-        s = stream if stream is not None else torch.cuda.current_stream(self.dev).cuda_stream
-        if getattr(self, "_run_k", None) != moves:
-            self._run_states = torch.zeros((moves, self.G, 3), dtype=torch.int64, device=self.dev)
-            self._run_moves = torch.zeros((moves, self.G), dtype=torch.int16, device=self.dev)
-            self._run_results = torch.zeros((moves, self.G), dtype=torch.int32, device=self.dev)
-            self._run_k = moves
-        self.eng.c4_selfplay_async(self.roots.data_ptr(), self.G, self.sims, self.c, self.bs, moves,
-                                   self._run_states.data_ptr(), self._run_moves.data_ptr(),
-                                   self._run_results.data_ptr(), self.stats.data_ptr(), stream=s)
-        self.carry_pending = False   # carried moves were resumed first
-        if kernel_done is not None:   # an event recorded after the launch, before the recording
-            kernel_done.record()
-        if self.record:
-            self.traj.record_steps(self._run_states.data_ptr(), self._run_moves, self._run_results, moves, stream=s)
-        self.results.copy_(self._run_results[-1])
-        return self._run_results
-
-    def run_pooled(self, budget: int, moves_cap: int, stream: int | None = None, kernel_done=None,
-                   carry: bool = False) -> torch.Tensor:
-        """`budget` moves shared by all games in ONE launch (zc_c4_selfplay_pooled_async): each
-        game takes its next move from a device counter while the budget lasts, at most
-        `moves_cap` moves.  A throughput schedule, not the reference's: scripts/train.py:151-170
-        is lockstep (one move per unfinished game per call).  Game i's k-th move is the k-th move
-        run() would play;
-        how many moves each game gets follows the games' pace.  The trajectory recording
-        replays the steps in order (slots without a k-th move: ZC_SLOT_SKIP, untouched).
-        carry=True (zc_c4_selfplay_carry_async): once the budget is spent the in-flight moves
-        stop at their next flush and carry over — the next run()/run_pooled() resumes them
-        first; drain() finishes them; step() and the lockstep searches refuse until then.
-        Returns the per-step results [moves_cap, G]; self.stats sums the launch's counters."""
-        if self.record_policy:
-            raise ValueError(_NO_FUSED_POLICY)
-        if self.traj is not None and self.traj.quota != _UNLIMITED:
-            raise ValueError("run_pooled() plays without a game quota; use step() under simulate_games' quota")
-        if self.vs is not None or self.ps is not None:
-            raise ValueError("run_pooled() fuses the rollout search; network modes step()")
-        s = stream if stream is not None else torch.cuda.current_stream(self.dev).cuda_stream
-        if getattr(self, "_run_k", None) != moves_cap:
-            self._run_states = torch.zeros((moves_cap, self.G, 3), dtype=torch.int64, device=self.dev)
-            self._run_moves = torch.zeros((moves_cap, self.G), dtype=torch.int16, device=self.dev)
-            self._run_results = torch.zeros((moves_cap, self.G), dtype=torch.int32, device=self.dev)
-            self._run_k = moves_cap
-        if getattr(self, "_ticket", None) is None:
-            self._ticket = torch.zeros(2, dtype=torch.int32, device=self.dev)   # counter, most moves played
-        self.eng.c4_selfplay_pooled_async(self.roots.data_ptr(), self.G, self.sims, self.c, self.bs, moves_cap,
-                                          budget, self._ticket.data_ptr(), self._run_states.data_ptr(),
-                                          self._run_moves.data_ptr(), self._run_results.data_ptr(),
-                                          self.stats.data_ptr(), stream=s, carry=carry)
-        self.carry_pending = bool(carry)
-        if kernel_done is not None:
-            kernel_done.record()
-        if self.record:
-            self.traj.record_steps(self._run_states.data_ptr(), self._run_moves, self._run_results, moves_cap,
-                                   reached=self._ticket[1:], stream=s)
-        return self._run_results
-
-    def drain(self, stream: int | None = None) -> torch.Tensor:
-        """Finish the moves run_pooled(carry=True) left in flight (a pooled launch with no
-        budget: each carried move is resumed and finished, nothing new starts), recorded like
-        any launch's moves.  Returns that launch's per-step results."""
-        return self.run_pooled(0, 1, stream=stream)
-
     def step_search(self, stream: int | None = None) -> torch.Tensor:
-        """The search half of a step (zc_c4_search_async); returns the results tensor the
-        finish half will fill."""
-        if self.carry_pending:
-            raise RuntimeError("moves carried over by run_pooled(carry=True) are in flight: drain() first")
-        s = stream if stream is not None else torch.cuda.current_stream(self.dev).cuda_stream
-        if self.ps is not None or self.vs is not None:
-            if self.ps is not None:
-                mv, na, st = self.ps.enqueue(self.roots, self.sims, self.net_fn, temperature=self.temperature)
-            else:
-                mv, na, st = self.vs.enqueue(self.roots, self.sims, self.c, self.value_fn)
+        """The search half of a step; returns the results tensor the finish half will fill."""
+        s = self._stream(stream)
+        if self.ps is not None:
+            mv, na, st = self.ps.enqueue(self.roots, self.sims, self.net_fn, temperature=self.temperature)
+        elif self.vs is not None:
+            mv, na, st = self.vs.enqueue(self.roots, self.sims, self.c, self.value_fn)
+        else:
+            self._search(s)
+            na = self.na
+        if na is not self.na:
             self.moves.copy_(mv)
             self.stats.copy_(st)
-        else:
-            na = self.na
-            self.eng.c4_search_async(self.roots.data_ptr(), self.G, self.sims, self.c, self.bs,
-                                     self.moves.data_ptr(), self.na.data_ptr(), self.stats.data_ptr(), stream=s)
         if self.record_policy:   # the visit counts of the positions searched, before they are played
-            self.traj.record_policy(na, stream=s)
+            self.traj.record_policy(na, self._root_moves(s), stream=s)
         self.totals += self.stats[:, :2].sum(0)
         return self.results
 
-    def adopt(self, other: "C4SelfPlay"):
-        """Take over another pool's games in progress (positions and their recorded
-        histories, game numbers; this pool's streams and pool stay its own) — e.g. a
-        network-mode pool starting from a burned-in rollout pool's mixed game ages."""
-        if self.carry_pending:   # its carried searches belong to the roots being replaced
-            raise RuntimeError("moves carried over by run_pooled(carry=True) are in flight: drain() first")
-        self.roots.copy_(other.roots)
-        if self.reuse_tree:
-            self.ps.forget()
-        if self.traj is not None and other.traj is not None:
-            t, o = self.traj, other.traj
-            t.hist.copy_(o.hist)
-            t.hmoves.copy_(o.hmoves)
-            t.slot.copy_(o.slot)
-            t.ctl[_native.ZC_TRAJ_NEXT] = o.ctl[_native.ZC_TRAJ_NEXT]
-            _adopt_policy(t, o)
+    def step_finish(self, stream: int | None = None) -> torch.Tensor:
+        """Play + evaluate the searched moves, record the positions, refill finished games."""
+        s = self._stream(stream)
+        rec = self._play(s)
+        if rec is not None:
+            self.traj.record(*rec, stream=s)
+        return self.results
 
     def capture_step(self):
         """One whole step (search with its network, play, record) as a HIP graph; each
@@ -617,38 +497,207 @@ class C4SelfPlay:
             self.traj.pinned = True   # the graph holds the pool's buffers from now on
         return g
 
-    def step_finish(self, stream: int | None = None) -> torch.Tensor:
-        """Play + evaluate the searched moves, record the positions, refill finished games."""
-        s = stream if stream is not None else torch.cuda.current_stream(self.dev).cuda_stream
-        self.eng.c4_play_async(self.roots.data_ptr(), self.G, self.moves.data_ptr(), self.results.data_ptr(),
-                               reset=not self.record, stream=s)
+    def adopt(self, other):
+        """Take over another pool's games in progress: positions (and what else the game keeps
+        of them), recorded histories with their visit counts, game numbers; this pool's streams
+        and pool stay its own — e.g. a network-mode pool starting from a burned-in pool's mixed
+        game ages."""
+        self._adopt_state(other)
+        if self.traj is None or other.traj is None:
+            return
+        t, o = self.traj, other.traj
+        t.hist.copy_(o.hist)
+        t.hmoves.copy_(o.hmoves)
+        t.slot.copy_(o.slot)
+        t.ctl[_native.ZC_TRAJ_NEXT] = o.ctl[_native.ZC_TRAJ_NEXT]
+        if t.policy_width is not None:
+            if o.policy_width != t.policy_width or o.pi_slot_cap != t.pi_slot_cap:
+                raise ValueError("adopt() with record_policy needs a pool recording the policy with the same "
+                                 "pi_slot_cap")
+            t.slot_pi.copy_(o.slot_pi)
+            t.slot_off.copy_(o.slot_off)
+
+    def _fused(self, moves: int, budget: int | None, stream: int | None, kernel_done, carry: bool = False):
+        """run() (budget None) and run_pooled(): the game's `_launch` into the [moves][G] outputs,
+        then the recording of every step, in step order.  Needs the unlimited quota
+        (start(None)): with a quota the refill depends on other slots' finishes, which step()
+        decides once per step.  `kernel_done`: an event recorded after the launch, before the
+        recording."""
+        name = "run" if budget is None else "run_pooled"
+        if self.record_policy:
+            raise ValueError(_NO_FUSED_POLICY)
+        if self.traj is not None and self.traj.quota != _UNLIMITED:
+            raise ValueError(f"{name}() plays without a game quota; use step() under simulate_games' quota")
+        if self.vs is not None or self.ps is not None:
+            raise ValueError(f"{name}() fuses the {self.FUSED_SEARCH} search; network modes step()")
+        s = self._stream(stream)
+        if self._run_k != moves:   # rows shaped like the roots'
+            self._run_states = torch.zeros((moves,) + self.roots.shape, dtype=self.roots.dtype, device=self.dev)
+            self._run_moves = torch.zeros((moves, self.G), dtype=torch.int16, device=self.dev)
+            self._run_results = torch.zeros((moves, self.G), dtype=torch.int32, device=self.dev)
+            self._run_k = moves
+        if budget is not None and self._ticket is None:
+            self._ticket = torch.zeros(2, dtype=torch.int32, device=self.dev)   # counter, most moves played
+        self._launch(moves, budget, carry, s)
+        if kernel_done is not None:
+            kernel_done.record()
         if self.record:
-            # on the step's own stream: the copy reads the search's moves and feeds the record
-            # kernel, both enqueued on s (torch's current stream would race with a side stream)
-            if s == torch.cuda.current_stream(self.dev).cuda_stream:
-                self.moves16.copy_(self.moves)
-            else:
-                with torch.cuda.stream(torch.cuda.ExternalStream(s, device=self.dev)):
-                    self.moves16.copy_(self.moves)
-            self.traj.record(self.roots.data_ptr(), self.moves16, self.results, stream=s)
-        return self.results
+            self.traj.record_steps(self._run_states.data_ptr(), self._run_moves, self._run_results, moves,
+                                   reached=self._ticket[1:] if budget is not None else None, stream=s)
+        return self._run_results
+
+    def check(self):
+        """Raises what the device collected (chess)."""
 
     def take(self) -> TrajBatch:
+        self.check()
         return self.traj.take()
+
+    def finished_games(self, batch: TrajBatch | None = None):
+        """Host view of taken games (tests / inspection): (global slot id, moves, result,
+        positions with labels) per game, in start order.  Connect4: columns and [n, 3] rows;
+        chess: ((fr, fc, tr, tc), value) moves and [n, 9] int64 rows."""
+        return _host_games(batch if batch is not None else self.take(), self.first_id, self._move)
+
+    def close(self):
+        self.eng.close()
+
+
+class C4SelfPlay(_SelfPlayPool):
+    """Connect4 self-play pool on one GPU: search (zc_c4_search_async) + play/evaluate
+    (zc_c4_play_async) + trajectory recording (zc_traj_record_async), all stream-ordered,
+    no host synchronisation per step.  With `net=` the search takes its leaf values from a
+    value network (C4ValuedSearch, C2(iii)); with `puct_net=` it is the PUCT search with a
+    policy + value network (C4PuctSearch, SURVEY §8 a21), moves sampled at `temperature`;
+    both step() only (the network runs between kernels) and capture_step() into one graph."""
+
+    MAX_LEN = 43   # the opening + at most 42 moves
+    MOVE_DTYPE, NA_WIDTH, POLICY_WIDTH, POOL_ROWS, FUSED_SEARCH = torch.int32, 7, 7, MAX_LEN, "rollout"
+    _move = staticmethod(int)
+
+    def __init__(self, games: int, sims: int, c: float = 1.4, batch_size: int = 32, seed: int = 0,
+                 rank: int = 0, device: int = 0, record: bool = True, games_cap: int | None = None,
+                 net=None, puct_net=None, temperature: float = 1.0, puct_seed: int = 1, streams: int = 1,
+                 record_policy: bool = False, pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
+                 reuse_tree: bool = False, tree_nodes: int | None = None):
+        """record_policy: every step()'s root visit counts go with the positions into the
+        trajectories (TrajBatch.pi / policy_targets(7)), in every search mode.
+        reuse_tree (PUCT mode): each search keeps the subtree of the move just played
+        (C4PuctSearch(reuse=True)) and adds sims - 1 visits to it; a tree holds up to
+        `tree_nodes` nodes (default min(2 * sims, 65534)), and a search whose kept nodes leave
+        no room for its own starts afresh.  start() and adopt() drop the kept trees."""
+        if reuse_tree:
+            if puct_net is None:
+                raise ValueError("reuse_tree keeps the PUCT search's tree: it needs puct_net")
+            # a kept root carries the visits of every earlier search of its game: at most 42 searches
+            if record_policy and 42 * sims > _native.ZC_TRAJ_PI_MAX_COUNT:
+                raise ValueError(f"record_policy stores visit counts in 16 bits: with reuse_tree a root can hold "
+                                 f"42 * sims = {42 * sims} > {_native.ZC_TRAJ_PI_MAX_COUNT} visits")
+        super().__init__(games, sims, c, batch_size, seed, rank, device, temperature, record_policy,
+                         torch.zeros(24, dtype=torch.uint8), self.MAX_LEN, games_cap, pi_slot_cap, pi_pool_cap,
+                         record=record,
+                         max_sims=(tree_nodes or min(2 * sims, 65534)) if reuse_tree else None)
+        self.reuse_tree = bool(reuse_tree)
+        self.record = record
+        self.roots = torch.zeros((games, 3), dtype=torch.int64, device=self.dev)
+        self.moves16 = torch.zeros(games, dtype=torch.int16, device=self.dev)
+        self.carry_pending = False   # run_pooled(carry=True) left moves in flight (drain() finishes them)
+        self._networks(net, valued.C4ValuedSearch, {}, streams,
+                       puct_net, valued.C4PuctSearch, dict(seed=puct_seed, reuse=self.reuse_tree), streams)
+
+    def start(self, quota: int | None = None):
+        """Every slot back to the opening; with a quota, slots beyond it idle and finished
+        slots start new games only while fewer than `quota` have started."""
+        if self.carry_pending:   # the games restart: their carried moves are dropped
+            # (after every stream's launches: the carry launch may have run on a caller's stream)
+            torch.cuda.synchronize(self.dev)
+            self.eng.c4_carry_discard(0, self.G, self._stream(None))
+            self.carry_pending = False
+        self.roots.zero_()
+        if self.reuse_tree:
+            self.ps.forget()
+        if self.traj is not None:
+            self.traj.start(quota, games_cap=quota)
+
+    def step_search(self, stream: int | None = None) -> torch.Tensor:
+        if self.carry_pending:
+            raise RuntimeError("moves carried over by run_pooled(carry=True) are in flight: drain() first")
+        return super().step_search(stream)
+
+    def _search(self, s: int):
+        self.eng.c4_search_async(self.roots.data_ptr(), self.G, self.sims, self.c, self.bs,
+                                 self.moves.data_ptr(), self.na.data_ptr(), self.stats.data_ptr(), stream=s)
+
+    def _root_moves(self, s: int):
+        return None   # a visit count's index is its column
+
+    def _play(self, s: int):
+        self.eng.c4_play_async(self.roots.data_ptr(), self.G, self.moves.data_ptr(), self.results.data_ptr(),
+                               reset=not self.record, stream=s)
+        if not self.record:
+            return None
+        # on the step's own stream: the copy reads the search's moves and feeds the record
+        # kernel, both enqueued on s (torch's current stream would race with a side stream)
+        if s == self._stream(None):
+            self.moves16.copy_(self.moves)
+        else:
+            with torch.cuda.stream(torch.cuda.ExternalStream(s, device=self.dev)):
+                self.moves16.copy_(self.moves)
+        return self.roots.data_ptr(), self.moves16, self.results
+
+    def _adopt_state(self, other: "C4SelfPlay"):
+        if self.carry_pending:   # its carried searches belong to the roots being replaced
+            raise RuntimeError("moves carried over by run_pooled(carry=True) are in flight: drain() first")
+        self.roots.copy_(other.roots)
+        if self.reuse_tree:
+            self.ps.forget()
+
+    def _launch(self, moves: int, budget: int | None, carry: bool, s: int):
+        """zc_c4_selfplay_async / zc_c4_selfplay_pooled_async (carry: zc_c4_selfplay_carry_async);
+        either resumes carried moves first."""
+        head = (self.roots.data_ptr(), self.G, self.sims, self.c, self.bs, moves)
+        outs = (self._run_states.data_ptr(), self._run_moves.data_ptr(), self._run_results.data_ptr(),
+                self.stats.data_ptr())
+        if budget is None:
+            self.eng.c4_selfplay_async(*head, *outs, stream=s)
+        else:
+            self.eng.c4_selfplay_pooled_async(*head, budget, self._ticket.data_ptr(), *outs, stream=s, carry=carry)
+        self.carry_pending = bool(carry)
+
+    def run(self, moves: int, stream: int | None = None, kernel_done=None) -> torch.Tensor:
+        """`moves` moves for every game in ONE launch (zc_c4_selfplay_async: each game at its
+        own pace, finished games refilled from the opening in the kernel), then the
+        trajectory recording of every step, in step order — the same games, pool and labels
+        as `moves` calls of step().  Needs the unlimited quota (start(None)).
+        Returns the per-step results [moves, G]; self.stats sums the moves' counters."""
+        self.results.copy_(self._fused(moves, None, stream, kernel_done)[-1])
+        return self._run_results
+
+    def run_pooled(self, budget: int, moves_cap: int, stream: int | None = None, kernel_done=None,
+                   carry: bool = False) -> torch.Tensor:
+        """`budget` moves shared by all games in ONE launch (zc_c4_selfplay_pooled_async): each
+        game takes its next move from a device counter while the budget lasts, at most
+        `moves_cap` moves.  A throughput schedule, not the reference's: scripts/train.py:151-170
+        is lockstep (one move per unfinished game per call).  Game i's k-th move is the k-th move
+        run() would play;
+        how many moves each game gets follows the games' pace.  The trajectory recording
+        replays the steps in order (slots without a k-th move: ZC_SLOT_SKIP, untouched).
+        carry=True (zc_c4_selfplay_carry_async): once the budget is spent the in-flight moves
+        stop at their next flush and carry over — the next run()/run_pooled() resumes them
+        first; drain() finishes them; step() and the lockstep searches refuse until then.
+        Returns the per-step results [moves_cap, G]; self.stats sums the launch's counters."""
+        return self._fused(moves_cap, budget, stream, kernel_done, carry)
+
+    def drain(self, stream: int | None = None) -> torch.Tensor:
+        """Finish the moves run_pooled(carry=True) left in flight (a pooled launch with no
+        budget: each carried move is resumed and finished, nothing new starts), recorded like
+        any launch's moves.  Returns that launch's per-step results."""
+        return self._fused(1, 0, stream, None)
 
     def take_positions(self) -> torch.Tensor:
         """Positions of the games finished since the last take, in start order: [n, 3] int64
         device rows (stones X, stones O, turn | Engine.get_dataset label << 32)."""
         return positions_of(self.take())
-
-    def finished_games(self, batch: TrajBatch | None = None):
-        """Host view of taken games (tests / inspection): (global slot id, moves, result,
-        positions [n, 3] with labels) per game, in start order."""
-        b = batch if batch is not None else self.take()
-        return _host_games(b, self.first_id, lambda m: int(m))
-
-    def close(self):
-        self.eng.close()
 
 
 def positions_of(b: TrajBatch) -> torch.Tensor:
@@ -670,7 +719,7 @@ def _host_games(b: TrajBatch, first_id: int, move_fn):
     return out
 
 
-class ChessSelfPlay:
+class ChessSelfPlay(_SelfPlayPool):
     """Device-resident chess self-play: the chess form of `C4SelfPlay`.  G games live on one
     GPU as zc_chess_state rows; one `step()` searches every game — Value('crude_chess_score')
     in the search kernel, a value network between the stepwise select and backup kernels
@@ -687,6 +736,10 @@ class ChessSelfPlay:
     `take()`.  `capture_step()` records a whole step (search, network, play, record) in one
     HIP graph."""
 
+    MOVE_DTYPE, NA_WIDTH, POLICY_WIDTH, POOL_ROWS = torch.int16, _native.CHESS_MAX_MOVES, 4096, 160
+    FUSED_SEARCH = "crude-score"
+    _move = staticmethod(lambda m: _native.unpack_chess_move(int(m) & 0xFFFF))
+
     def __init__(self, games: int, sims: int, c: float = 1.4, batch_size: int = 32, seed: int = 0,
                  rank: int = 0, device: int = 0, policy: int = _native.ZC_POLICY_IMMEDIATE_VALUE,
                  freedom: float = 3.0, net=None, init_fen: str | None = None, games_cap: int | None = None,
@@ -695,44 +748,23 @@ class ChessSelfPlay:
                  pi_slot_cap: int | None = None, pi_pool_cap: int | None = None):
         """record_policy: every step()'s root visit counts go with the positions into the
         trajectories (TrajBatch.pi / policy_targets(4096)), in every search mode."""
-        _check_record_policy(record_policy, sims)
-        self.record_policy = bool(record_policy)
-        self.G, self.sims, self.c, self.bs = games, sims, c, batch_size
-        self.policy, self.freedom = int(policy), float(freedom)
-        self.dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        self.eng = _native.NativeEngine(max_games=games, max_sims=sims, max_batch=batch_size,
-                                        device=self.dev.index or 0)
-        self.eng.chess_reserve()
-        self.first_id = rank * games
-        self.eng.seed(0, [seed + self.first_id + g for g in range(games)])
         init = _native.chess_from_fen(init_fen) if init_fen else _native.chess_init()
-        self.init_row = torch.from_numpy(np.frombuffer(init.tobytes(), np.uint8).reshape(1, 72).copy()).to(self.dev)
+        init = torch.from_numpy(np.frombuffer(init.tobytes(), np.uint8).reshape(1, 72).copy())
+        max_len = 2 * hist_cap + 1
+        if record_policy and pi_slot_cap is None:   # a position has at most min(sims, 256) visited moves
+            pi_slot_cap = (max_len - 1) * min(sims, _native.CHESS_MAX_MOVES)
+        super().__init__(games, sims, c, batch_size, seed, rank, device, temperature, record_policy,
+                         init, max_len, games_cap, pi_slot_cap, pi_pool_cap)
+        self.eng.chess_reserve()
+        self.policy, self.freedom = int(policy), float(freedom)
+        self.init_row = init.to(self.dev)
         self.roots = self.init_row.repeat(games, 1).contiguous()
-        self.moves = torch.zeros(games, dtype=torch.int16, device=self.dev)
-        self.na = torch.zeros((games, _native.CHESS_MAX_MOVES), dtype=torch.int32, device=self.dev)
-        self.stats = torch.zeros((games, _native.STATS_FIELDS), dtype=torch.int64, device=self.dev)
         self.post = torch.zeros_like(self.roots)
-        self.results = torch.zeros(games, dtype=torch.int32, device=self.dev)
-        self.totals = torch.zeros(2, dtype=torch.int64, device=self.dev)   # expansions, depth sum since reset
-        self.vs = self.value_fn = self.ps = self.net_fn = None
-        self.temperature = float(temperature)
-        if net is not None:
-            from .valued import ChessValuedSearch, NetValue
-            self.vs = ChessValuedSearch(self.eng, games, batch_size, leaves=False, policy=self.policy,
-                                        freedom=self.freedom)
-            self.value_fn = NetValue(net)
-            if streams > 1:   # the games in parts on their own streams (valued._split_flushes)
-                self.value_fn = [NetValue(net.replica() if hasattr(net, "replica") else net) for _ in range(streams)]
-        if puct_net is not None:
-            from .valued import ChessPuctSearch, PolicyNet
-            # a network with the convolutional head takes the planes in its input layout straight
-            # from the select kernel (no conversion launch per flush)
-            self.ps = ChessPuctSearch(self.eng, games, batch_size, seed=puct_seed, leaves=False,
-                                      planes_nhwc=bool(getattr(puct_net, "conv_head", False))
-                                      and os.environ.get("ZC_PUCT_NHWC", "1") != "0")   # 0: A/B runs only
-            self.net_fn = PolicyNet(puct_net)
-            if puct_streams > 1:   # the games in parts on their own streams (valued._split_flushes)
-                self.net_fn = [PolicyNet(puct_net.replica()) for _ in range(puct_streams)]
+        # a network with the convolutional head takes the planes in its input layout straight
+        # from the select kernel (no conversion launch per flush)
+        nhwc = bool(getattr(puct_net, "conv_head", False)) and os.environ.get("ZC_PUCT_NHWC", "1") != "0"   # 0: A/B
+        self._networks(net, valued.ChessValuedSearch, dict(policy=self.policy, freedom=self.freedom), streams,
+                       puct_net, valued.ChessPuctSearch, dict(seed=puct_seed, planes_nhwc=nhwc), puct_streams)
         self.hist_cap = hist_cap  # moves per side
         self.hist = torch.zeros((games, 2, self.hist_cap), dtype=torch.int16, device=self.dev)
         self.hlen = torch.zeros((games, 2), dtype=torch.int32, device=self.dev)
@@ -741,13 +773,6 @@ class ChessSelfPlay:
         b.d_roots, b.d_init, b.d_hist = self.roots.data_ptr(), self.init_row.data_ptr(), self.hist.data_ptr()
         b.d_hist_len, b.hist_cap, b.d_err = self.hlen.data_ptr(), self.hist_cap, self.err.data_ptr()
         self._pb = b
-        max_len = 2 * self.hist_cap + 1
-        cap = games_cap or max(8 * games, 1024)
-        if record_policy and pi_slot_cap is None:   # a position has at most min(sims, 256) visited moves
-            pi_slot_cap = (max_len - 1) * min(sims, _native.CHESS_MAX_MOVES)
-        self.traj = Trajectories(games, self.init_row[0], max_len, cap, cap * 160, self.dev,
-                                 policy_width=4096 if record_policy else None, pi_slot_cap=pi_slot_cap,
-                                 pi_pool_cap=pi_pool_cap)
         if record_policy:
             self.root_moves = torch.zeros((games, _native.CHESS_MAX_MOVES), dtype=torch.int16, device=self.dev)
             self.root_counts = torch.zeros(games, dtype=torch.int32, device=self.dev)
@@ -757,118 +782,56 @@ class ChessSelfPlay:
         self.hlen.zero_()
         self.traj.start(quota, games_cap=quota)
 
-    def _stream(self, stream):
-        return stream if stream is not None else torch.cuda.current_stream(self.dev).cuda_stream
+    def _search(self, s: int):
+        self.eng.chess_search_async(0, self.G, self.roots.data_ptr(), self.sims, self.c, self.bs, self.policy,
+                                    self.freedom, self.moves.data_ptr(), self.na.data_ptr(),
+                                    self.stats.data_ptr(), s)
 
-    def step(self, stream: int | None = None) -> torch.Tensor:
-        """One move for every game; returns the per-game results tensor (ONGOING = 2,
-        IDLE = 3).  Finished games restart from the initial position."""
-        _room(self.traj, stream)
-        s = self._stream(stream)
-        if self.ps is not None:
-            mv, na, st = self.ps.enqueue(self.roots, self.sims, self.net_fn, temperature=self.temperature)
-        elif self.vs is not None:
-            mv, na, st = self.vs.enqueue(self.roots, self.sims, self.c, self.value_fn)
-        else:
-            self.eng.chess_search_async(0, self.G, self.roots.data_ptr(), self.sims, self.c, self.bs, self.policy,
-                                        self.freedom, self.moves.data_ptr(), self.na.data_ptr(),
-                                        self.stats.data_ptr(), s)
-            mv, na, st = self.moves, self.na, self.stats
-        if mv is not self.moves:
-            self.moves.copy_(mv)
-            self.stats.copy_(st)
-        if self.record_policy:   # the roots' move lists name the visit counts' moves, before the play
-            self.eng.chess_legal_moves_async(self.G, self.roots.data_ptr(), self.root_moves.data_ptr(),
-                                             self.root_counts.data_ptr(), s)
-            self.traj.record_policy(na, self.root_moves, stream=s)
+    def _root_moves(self, s: int):
+        """The roots' legal-move lists name the visit counts' moves (before the play)."""
+        self.eng.chess_legal_moves_async(self.G, self.roots.data_ptr(), self.root_moves.data_ptr(),
+                                         self.root_counts.data_ptr(), s)
+        return self.root_moves
+
+    def _play(self, s: int):
         _native.check(_native.lib().zc_chess_play_step_async(
             self.G, ctypes.byref(self._pb), ctypes.c_void_p(self.moves.data_ptr()),
             ctypes.c_void_p(self.stats.data_ptr()), ctypes.c_void_p(self.post.data_ptr()),
             ctypes.c_void_p(self.results.data_ptr()), ctypes.c_void_p(s)))
-        self.traj.record(self.post.data_ptr(), self.moves, self.results, stream=s)
-        self.totals += self.stats[:, :2].sum(0)
-        return self.results
+        return self.post.data_ptr(), self.moves, self.results
 
-    def adopt(self, other: "ChessSelfPlay"):
-        """Take over another pool's games in progress: positions, both sides' move histories
-        (the repetition draw), recorded histories and game numbers (same hist_cap)."""
+    def _adopt_state(self, other: "ChessSelfPlay"):
+        """Beside the positions, both sides' move histories (the repetition draw)."""
         if other.hist_cap != self.hist_cap:
             raise ValueError("adopt() needs the same hist_cap")
         self.roots.copy_(other.roots)
         self.hist.copy_(other.hist)
         self.hlen.copy_(other.hlen)
-        t, o = self.traj, other.traj
-        t.hist.copy_(o.hist)
-        t.hmoves.copy_(o.hmoves)
-        t.slot.copy_(o.slot)
-        t.ctl[_native.ZC_TRAJ_NEXT] = o.ctl[_native.ZC_TRAJ_NEXT]
-        _adopt_policy(t, o)
 
-    def capture_step(self):
-        """One whole step (search with its network, play, record) as a HIP graph; each
-        replay plays the next move of every game."""
-        side = torch.cuda.Stream(self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):   # the network's kernels warmed outside the capture
-            if self.ps is not None:
-                _warm(self.ps, self.net_fn, self.sims)
-            elif self.vs is not None:
-                _warm(self.vs, self.value_fn, self.sims)
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self.step()
-        if self.traj is not None:
-            self.traj.pinned = True   # the graph holds the pool's buffers from now on
-        return g
-
-    def _run_buffers(self, moves: int):
-        if getattr(self, "_run_k", None) != moves:
-            self._run_states = torch.zeros((moves, self.G, 72), dtype=torch.uint8, device=self.dev)
-            self._run_moves = torch.zeros((moves, self.G), dtype=torch.int16, device=self.dev)
-            self._run_results = torch.zeros((moves, self.G), dtype=torch.int32, device=self.dev)
-            self._run_k = moves
+    def _launch(self, moves: int, budget: int | None, carry: bool, s: int):
+        """zc_chess_selfplay_async / zc_chess_selfplay_pooled_async."""
+        head = [self.eng.handle, 0, self.G, ctypes.byref(self._pb), self.sims, self.c, self.bs, self.policy,
+                self.freedom, moves]
+        outs = [ctypes.c_void_p(self._run_states.data_ptr()), ctypes.c_void_p(self._run_moves.data_ptr()),
+                ctypes.c_void_p(self._run_results.data_ptr()), ctypes.c_void_p(self.stats.data_ptr()),
+                ctypes.c_void_p(s)]
+        if budget is None:
+            _native.check(_native.lib().zc_chess_selfplay_async(*head, *outs))
+        else:
+            _native.check(_native.lib().zc_chess_selfplay_pooled_async(
+                *head, int(budget), ctypes.c_void_p(self._ticket.data_ptr()), *outs))
 
     def run(self, moves: int, stream: int | None = None, kernel_done=None) -> torch.Tensor:
         """Crude score: `moves` moves for every game in ONE launch (zc_chess_selfplay_async),
         then the multi-step recording — the same games, pool and labels as `moves` calls of
         step().  Returns the per-step results [moves, G]; self.stats sums the moves."""
-        return self._launch(moves, None, stream, kernel_done)
+        return self._fused(moves, None, stream, kernel_done)
 
     def run_pooled(self, budget: int, moves_cap: int, stream: int | None = None, kernel_done=None) -> torch.Tensor:
         """Crude score: `budget` moves shared by the games in ONE launch (at most moves_cap
         each; a throughput schedule, the reference's train.py is lockstep).  Game i's k-th
         move is the k-th move run() would play."""
-        return self._launch(moves_cap, budget, stream, kernel_done)
-
-    def _launch(self, moves, budget, stream, kernel_done):
-        if self.record_policy:
-            raise ValueError(_NO_FUSED_POLICY)
-        if self.vs is not None or self.ps is not None:
-            raise ValueError("run()/run_pooled() fuse the crude-score search; network modes step()")
-        if self.traj.quota != _UNLIMITED:
-            raise ValueError("run() plays without a game quota; use step() under simulate_games' quota")
-        s = self._stream(stream)
-        self._run_buffers(moves)
-        args = [self.eng.handle, 0, self.G, ctypes.byref(self._pb), self.sims, self.c, self.bs, self.policy,
-                self.freedom, moves]
-        outs = [ctypes.c_void_p(self._run_states.data_ptr()), ctypes.c_void_p(self._run_moves.data_ptr()),
-                ctypes.c_void_p(self._run_results.data_ptr()), ctypes.c_void_p(self.stats.data_ptr()),
-                ctypes.c_void_p(s)]
-        reached = None
-        if budget is None:
-            _native.check(_native.lib().zc_chess_selfplay_async(*args, *outs))
-        else:
-            if getattr(self, "_ticket", None) is None:
-                self._ticket = torch.zeros(2, dtype=torch.int32, device=self.dev)
-            reached = self._ticket[1:]
-            _native.check(_native.lib().zc_chess_selfplay_pooled_async(
-                *args, int(budget), ctypes.c_void_p(self._ticket.data_ptr()), *outs))
-        if kernel_done is not None:
-            kernel_done.record()
-        self.traj.record_steps(self._run_states.data_ptr(), self._run_moves, self._run_results, moves,
-                               reached=reached, stream=s)
-        return self._run_results
+        return self._fused(moves_cap, budget, stream, kernel_done)
 
     def check(self):
         e = self.err.cpu().tolist()
@@ -881,19 +844,6 @@ class ChessSelfPlay:
             raise RuntimeError("chess search exceeded the tree's child-slot pool or depth limit")
         if e[2]:
             raise RuntimeError("no legal move at a non-terminal root")
-
-    def take(self) -> TrajBatch:
-        self.check()
-        return self.traj.take()
-
-    def finished_games(self, batch: TrajBatch | None = None):
-        """(global slot id, moves ((fr, fc, tr, tc), value), result, rows [n, 9] int64) per
-        game, in start order (host copies)."""
-        b = batch if batch is not None else self.take()
-        return _host_games(b, self.first_id, lambda m: _native.unpack_chess_move(int(m) & 0xFFFF))
-
-    def close(self):
-        self.eng.close()
 
 
 def simulate_games(pool, total_games: int, max_steps: int | None = None, check_every: int = 4) -> list[int]:
