@@ -499,6 +499,24 @@ int zc_chess_puct_backup_ex(zc_engine *eng, int32_t first_game, int32_t n_games,
                             int32_t rows_per_game, void *hip_stream);
 int zc_chess_puct_end(zc_engine *eng, int32_t first_game, int32_t n_games, float temperature, uint16_t *d_out_move,
                       int32_t *d_out_root_na, float *d_out_root_prior, zc_game_stats *d_out_stats, void *hip_stream);
+/* Tree reuse: zc_c4_puct_begin_reuse's rules (below) on the chess tree, with these differences.
+ * "Holds the position" is equality of board[64], turn, fifty and castle (the reserved bytes are
+ * not compared).  "No other search since" covers every chess search of the game: the crude,
+ * value-network, host-policy and rollout searches share the arena, and any begin drops the kept
+ * tree.  A chess tree is node records plus a per-game pool of S = 64 * (max_sims + 1) child
+ * slots, so the room rule has two halves, and the game starts afresh unless both hold:
+ *   kept_nodes + sims - 1 <= max_sims + 1    and    kept_slots + 64 * (sims - 1) <= S,
+ * kept_slots = the kept nodes' move counts summed (a reused search has a fresh search's slot
+ * headroom per new node; the re-root itself never causes ZC_STATUS_CAPACITY).  The kept nodes
+ * are renumbered in creation order and their slot ranges packed in that order from slot 0, N, W
+ * and P bit for bit; noise is mixed into the kept root's priors over all its (up to 256) moves
+ * as into a fresh root's.  A root without legal moves starts afresh: ZC_STATUS_NO_MOVES. */
+int zc_chess_puct_begin_reuse(zc_engine *eng, int32_t first_game, int32_t n_games, const zc_chess_state *d_roots,
+                              int32_t sims, double c_puct, int32_t batch_size, float dirichlet_alpha,
+                              float dirichlet_eps, uint64_t seed, int32_t *d_search_no, int32_t *d_kept,
+                              void *hip_stream);
+/* Stream-ordered: the games' kept chess PUCT trees are dropped; their next search starts afresh. */
+int zc_chess_puct_forget(zc_engine *eng, int32_t first_game, int32_t n_games, void *hip_stream);
 
 /* ---- Connect4 PUCT search (AlphaZero-style; no reference counterpart) -----
  * The chess PUCT search's rules (above) on the Connect4 rules of c4_backend.py: moves in

@@ -231,6 +231,11 @@ SIGNATURES = [
     ("zc_chess_puct_end", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p]),
+    ("zc_chess_puct_begin_reuse", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                 ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_float,
+                                                 ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p]),
+    ("zc_chess_puct_forget", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     ("zc_c4_puct_begin", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
                                         ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_float,
                                         ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
@@ -692,6 +697,17 @@ class NativeEngine:
         check(lib().zc_chess_puct_begin(self._h, first_game, n, ctypes.c_void_p(d_roots), int(sims), float(c_puct),
                                         int(batch_size), float(alpha), float(eps), int(seed) & (2**64 - 1),
                                         ctypes.c_void_p(d_search_no or None), ctypes.c_void_p(stream or None)))
+
+    def chess_puct_begin_reuse(self, first_game, n, d_roots, sims, c_puct, batch_size, alpha, eps, seed,
+                               d_search_no=0, d_kept=0, stream=0):
+        """chess_puct_begin that keeps each game's subtree of its new root (zc_chess_puct_begin_reuse)."""
+        check(lib().zc_chess_puct_begin_reuse(self._h, first_game, n, ctypes.c_void_p(d_roots), int(sims),
+                                              float(c_puct), int(batch_size), float(alpha), float(eps),
+                                              int(seed) & (2**64 - 1), ctypes.c_void_p(d_search_no or None),
+                                              ctypes.c_void_p(d_kept or None), ctypes.c_void_p(stream or None)))
+
+    def chess_puct_forget(self, first_game, n, stream=0):
+        check(lib().zc_chess_puct_forget(self._h, first_game, n, ctypes.c_void_p(stream or None)))
 
     def chess_puct_select(self, first_game, n, flush, d_leaves=0, d_planes=0, planes_f16=True, d_counts=0, stream=0,
                           planes_nhwc=False):

@@ -16,8 +16,12 @@
 //           a terminal leaf's value is -1 (side to move mated) or 0 (no moves otherwise);
 //   root    flush 0 evaluates the root alone; its priors get Dirichlet(alpha) noise with
 //           weight eps, drawn with a counter-based Philox4x32-10 stream keyed by (seed, game).
+//   reuse   (opt-in, zc_chess_puct_begin_reuse) the subtree of the position now at the root, one
+//           or two plies below the last search's root, is compacted in place into the next
+//           tree, node records and child slots; such a search has no flush-0 leaf and adds
+//           sims - 1 visits.
 //
-// Launches (one wave per game): begin (root node), select (flush f's leaves, planes),
+// Launches (one wave per game): begin or re-root (root node), select (flush f's leaves, planes),
 // backup (priors + values), end (move by visits or temperature sampling, visit counts).
 #include <hip/hip_fp16.h>
 
@@ -179,7 +183,305 @@ __global__ __launch_bounds__(64) void puct_begin_kernel(ChessParams p) {
         ctl[cNb] = 0;
         ctl[cExp] = 0;
         ctl[cDepth] = 0;
+        ctl[cDone] = 0;
+        ctl[cReused] = 0;
     }
+}
+
+// ---- tree reuse: the subtree of the position now at the root becomes the next tree ----
+// (c4_puct.hip's re-root on the chess tree's two address spaces.)  Node ids are in creation
+// order and so are the slot ranges (puct_commit_kernel hands them out in creation order), so a
+// kept node's new id is <= its old id and its new first slot <= its old one: one ascending pass
+// numbers the kept nodes and sums their move counts into the new bases, the node records and
+// then the slots move down in place, 64 at a time with every load of a chunk returned before
+// any of its stores is issued, and a last pass renumbers the parents.  Every index read from
+// the arena is bounded before it is used: a tree that fails a bound is not kept.
+
+__device__ __forceinline__ void vm_drain() {
+    wave_sync_mem();
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// Whether node id (0 < id < n) holds the position in tgt[0..16]: board, turn, fifty, castle
+// (word 16's low three bytes; the reserved bytes are not compared).
+__device__ __forceinline__ bool reroot_holds(const CTree &t, const uint32_t *tgt, int id, int n) {
+    if (id <= 0 || id >= n) return false;
+    const uint32_t *w = (const uint32_t *)&t.nodes[id].st;
+    bool same = ((w[16] ^ tgt[16]) & 0x00FFFFFFu) == 0u;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) same = same && w[q] == tgt[q];
+    return same;
+}
+
+// The first node in slot order among node `par`'s children that holds the position, or -1;
+// kids[q] takes the child in slot q * 64 + lane (0xFFFF: none).  false: a bound failed.
+__device__ bool reroot_scan(const CTree &t, const uint32_t *tgt, int par, int n, int s, uint32_t (&kids)[4], int &hit) {
+    const uint32_t lane = lane_id();
+    const int nm = uni((int)t.nodes[par].nmoves);
+    const uint32_t base = uni(t.nodes[par].base);
+    hit = -1;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) kids[q] = 0xFFFFu;
+    if (nm > ZC_CHESS_MAX_MOVES || (int64_t)base + nm > (int64_t)s) return false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = q * 64 + (int)lane;
+        if (q * 64 < nm && j < nm) kids[q] = t.ch[base + j];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (q * 64 >= nm || hit >= 0) continue;
+        const uint64_t m = __ballot(reroot_holds(t, tgt, (int)kids[q], n));
+        if (m) hit = __builtin_amdgcn_readlane((int)kids[q], __builtin_ctzll(m));
+    }
+    return true;
+}
+
+// The node holding the position one ply below the root, else two plies below it (the root's
+// children in slot order, each one's children in slot order); -1: none, or a bound failed.
+__device__ int reroot_find(const CTree &t, const uint32_t *tgt, int n, int s) {
+    uint32_t c1[4], c2[4];
+    int hit;
+    if (!reroot_scan(t, tgt, 0, n, s, c1, hit)) return -1;
+    if (hit >= 0) return hit;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        uint64_t m = __ballot(c1[q] != 0xFFFFu);
+        while (m) {
+            const int l = __builtin_ctzll(m);
+            m &= m - 1;
+            const int c = __builtin_amdgcn_readlane((int)c1[q], l);
+            if (c <= 0 || c >= n) return -1;
+            if (!reroot_scan(t, tgt, c, n, s, c2, hit)) return -1;
+            if (hit >= 0) return hit;
+        }
+    }
+    return -1;
+}
+
+// Pass 1 (c4_puct.hip reroot_number, plus the slots): remap[i] = the new id of node i of r's
+// subtree, 0xFFFF for any other node i >= r; rbase[new id] = the node's new first slot, the
+// running sum of the kept nodes' move counts.  Returns the nodes kept and, in `kslots`, their
+// slots; 0 when a kept node's slot range fails a bound.
+__device__ int reroot_number(const CTree &t, uint16_t *remap, uint32_t *rbase, int n, int s, int r, int &kslots) {
+    const uint32_t lane = lane_id();
+    int cnt = 0, tot = 0;
+    bool bad = false;
+    for (int b0 = r; b0 < n; b0 += 64) {
+        const int i = b0 + (int)lane;
+        const bool valid = i < n;
+        const int par = valid ? (int)t.nodes[i].parent : 0xFFFF;
+        const int nm = valid ? (int)t.nodes[i].nmoves : 0;
+        const uint32_t ob = valid ? t.nodes[i].base : 0u;
+        // a parent in an earlier chunk: its entry is final
+        bool k = valid && (i == r || (par >= r && par < b0 && remap[par] != 0xFFFF));
+        const bool inpar = valid && par >= b0 && par < i;
+        const int pl = inpar ? par - b0 : 0;  // the parent's lane
+        uint64_t b = __ballot(k);
+        for (;;) {  // parents in this chunk: at most one round per level of the tree
+            k = k || (inpar && ((b >> pl) & 1ull));
+            const uint64_t nb = __ballot(k);
+            if (nb == b) break;
+            b = nb;
+        }
+        const int id = cnt + __popcll(b & ((1ull << lane) - 1ull));
+        // exclusive prefix sum of the kept nodes' move counts over the chunk, plus the carry
+        const int mine = k ? nm : 0;
+        int inc = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(inc, o);
+            if ((int)lane >= o) inc += up;
+        }
+        const int nbase = tot + inc - mine;
+        // the slots move down, never up, and come from inside the slots in use
+        if (k && (nm > ZC_CHESS_MAX_MOVES || (int64_t)ob + nm > (int64_t)s || (uint32_t)nbase > ob)) bad = true;
+        if (valid) remap[i] = k ? (uint16_t)id : (uint16_t)0xFFFF;
+        if (k) rbase[id] = (uint32_t)nbase;
+        cnt += __popcll(b);
+        tot += __builtin_amdgcn_readlane(inc, 63);
+        vm_drain();  // the next chunk's lanes read these entries
+    }
+    kslots = tot;
+    return __ballot(bad) ? 0 : cnt;
+}
+
+// Pass 2: the kept records move to their new ids, 64 ids a chunk as 6 x 64 16-byte pieces.
+__device__ void reroot_move_nodes(ChessNode *T, const uint16_t *remap, int n, int r) {
+    const uint32_t lane = lane_id();
+    constexpr int kPieces = (int)sizeof(ChessNode) / 16;
+    for (int b0 = r; b0 < n; b0 += 64) {
+        const int rows = min(64, n - b0);
+        const uint4 *src = reinterpret_cast<const uint4 *>(T + b0);
+        uint4 v[kPieces];
+        uint32_t dst[kPieces];
+#pragma unroll
+        for (int it = 0; it < kPieces; ++it) {
+            const int q = it * 64 + (int)lane, rec = q / kPieces;
+            const bool valid = rec < rows;
+            v[it] = valid ? src[q] : make_uint4(0, 0, 0, 0);
+            dst[it] = valid ? (uint32_t)remap[b0 + rec] : 0xFFFFu;
+        }
+        vm_drain();  // every load of the chunk has returned before any of its stores is issued
+#pragma unroll
+        for (int it = 0; it < kPieces; ++it)
+            if (dst[it] != 0xFFFFu) reinterpret_cast<uint4 *>(T + dst[it])[(it * 64 + (int)lane) % kPieces] = v[it];
+        wave_sync_mem();
+    }
+    vm_drain();
+}
+
+// Pass 3: the kept slots move to [0, kslots) by flat slot index, 64 slots a step: a window of
+// 64 kept nodes (new ids; a moved record still holds its old base) gives, per slot, its node by
+// a search over the window's new bases in registers, and so its old slot.  New slot d comes from
+// an old slot >= d, so a step's stores land only on slots that this or an earlier step has
+// loaded.  The child ids go through the table on the way.
+__device__ void reroot_move_slots(const CTree &t, const uint16_t *remap, const uint32_t *rbase, int kept, int n, int r) {
+    const uint32_t lane = lane_id();
+    for (int k0 = 0; k0 < kept; k0 += 64) {
+        const int k = k0 + (int)lane;
+        const bool kv = k < kept;
+        const uint32_t nb = kv ? rbase[k] : 0xFFFFFFFFu;  // non-decreasing over the window's lanes
+        const uint32_t ob = kv ? t.nodes[k].base : 0u;
+        const uint32_t nm = kv ? (uint32_t)t.nodes[k].nmoves : 0u;
+        const uint32_t lo = uni(nb);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(nb + nm), min(63, kept - 1 - k0));
+        for (uint32_t d0 = lo; d0 < hi; d0 += 64) {
+            const uint32_t d = d0 + lane;
+            int j = 0;  // the last lane of the window whose new base is <= d: the slot's node
+#pragma unroll
+            for (int step = 32; step > 0; step >>= 1) {
+                const uint32_t x = (uint32_t)__shfl((int)nb, j + step);
+                if (x <= d) j += step;
+            }
+            const uint32_t src = (uint32_t)__shfl((int)ob, j) + (d - (uint32_t)__shfl((int)nb, j));
+            const bool dv = d < hi && src >= d && (int64_t)src < t.S;
+            uint16_t mv = 0, ch = 0xFFFF;
+            uint8_t ut = 0;
+            int32_t na = 0;
+            double w = 0.0;
+            float pr = 0.0f;
+            if (dv) {
+                mv = t.mv[src];
+                ut = t.ut[src];
+                ch = t.ch[src];
+                na = t.na[src];
+                w = t.w[src];
+                pr = t.pr[src];
+            }
+            const bool in = dv && (int)ch >= r && (int)ch < n;
+            const uint16_t nch = remap[in ? (int)ch : r];  // always a valid entry: no branch around the load
+            vm_drain();  // every load of the step has returned before any of its stores is issued
+            if (dv) {
+                t.mv[d] = mv;
+                t.ut[d] = ut;
+                t.ch[d] = in ? nch : (uint16_t)0xFFFF;
+                t.na[d] = na;
+                t.w[d] = w;
+                t.pr[d] = pr;
+            }
+            wave_sync_mem();
+        }
+    }
+    vm_drain();
+}
+
+// Pass 4: the moved records' links, one node a lane: the parent through the table (it still
+// holds an old id >= r: a kept node's parent is kept), the depth counted from the new root, the
+// new base; the new root as puct_begin_kernel writes a root.
+__device__ void reroot_link(ChessNode *T, const uint16_t *remap, const uint32_t *rbase, int kept, int n, int r,
+                            int rdepth) {
+    for (int id = (int)lane_id(); id < kept; id += 64) {
+        ChessNode *N = &T[id];
+        const uint32_t par = N->parent;
+        const bool in = par >= (uint32_t)r && par < (uint32_t)n;
+        const uint16_t np = remap[in ? par : (uint32_t)r];
+        N->base = rbase[id];
+        N->depth = (uint16_t)((int)N->depth - rdepth);
+        N->parent = (id == 0 || !in) ? (uint16_t)0xFFFF : np;
+        if (id == 0) N->pact = 0xFFFF;
+    }
+    vm_drain();
+}
+
+__global__ __launch_bounds__(64) void puct_reroot_kernel(ChessParams p) {
+    __shared__ CLds L;
+    __shared__ uint32_t tgt[18];
+    const int gl = blockIdx.x;
+    if (gl >= p.n_games) return;
+    const int g = p.first_game + gl;
+    const CTree t = ctree(p, g);
+    int32_t *ctl = p.ca.ctl + (size_t)g * kCtlWords;
+    uint16_t *remap = p.ca.remap + (size_t)g * p.M;
+    uint32_t *rbase = p.ca.rbase + (size_t)g * p.M;
+    const uint32_t lane = lane_id();
+    if (lane < 18) {
+        const uint32_t w = ((const uint32_t *)&p.roots[gl])[lane];
+        tgt[lane] = w;
+        ((uint32_t *)&L.st)[lane] = w;
+        ((uint32_t *)&p.ca.roots[g])[lane] = w;
+    }
+    wave_sync_mem();
+    const int n = uni(ctl[cNodes]), s = uni(ctl[cSlots]);
+    int r = -1, kept = 0, kslots = 0;
+    if (uni(ctl[cDone]) == 1 && n >= 2 && n <= p.M && s >= 0 && (int64_t)s <= t.S) r = uni(reroot_find(t, tgt, n, s));
+    if (r > 0) {  // evaluated, with legal moves
+        const int nm = uni((int)t.nodes[r].nmoves);
+        if (!uni((int)t.nodes[r].evaluated) || nm == 0 || nm > ZC_CHESS_MAX_MOVES) r = -1;
+    }
+    if (r > 0) {
+        kept = reroot_number(t, remap, rbase, n, s, r, kslots);
+        // room for this search's nodes and for kChessSlotsPerNode slots each, as a fresh search has
+        if ((int64_t)kept + p.sims - 1 > (int64_t)p.M ||
+            (int64_t)kslots + (int64_t)kChessSlotsPerNode * (p.sims - 1) > t.S)
+            kept = 0;
+    }
+    int slots = 0, status = 0;
+    if (kept) {
+        const int rdepth = uni((int)t.nodes[r].depth);
+        reroot_move_nodes(t.nodes, remap, n, r);
+        reroot_move_slots(t, remap, rbase, kept, n, r);
+        reroot_link(t.nodes, remap, rbase, kept, n, r, rdepth);
+        slots = kslots;
+        if (p.dir_eps > 0.0f) {  // the fresh path's root noise (backup kernel), on the kept priors
+            const uint2 key = make_uint2((uint32_t)p.seed, (uint32_t)(p.seed >> 32));
+            const int nm = uni((int)t.nodes[0].nmoves);
+            float pr[4], gm[4], gs = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int k = q * 64 + (int)lane;
+                pr[q] = k < nm ? t.pr[k] : 0.0f;
+                gm[q] = k < nm ? gamma_draw(p.dir_alpha, key, (uint32_t)g, (uint32_t)k, search_number(p, gl)) : 0.0f;
+                gs += gm[q];
+            }
+            gs = wave_sum_f(gs);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int k = q * 64 + (int)lane;
+                pr[q] = (1.0f - p.dir_eps) * pr[q] + p.dir_eps * (gs > 0.0f ? gm[q] / gs : 0.0f);
+                if (k < nm) t.pr[k] = pr[q];
+            }
+        }
+    } else {  // as puct_begin_kernel
+        create_node(t, L, 0, 0xFFFF, 0xFFFF, 0, slots, status);
+        if (!status && uni((int)t.nodes[0].nmoves) == 0) status = ZC_STATUS_NO_MOVES;
+    }
+    if (lane == 0) {
+        ctl[cNodes] = kept ? kept : 1;
+        ctl[cSlots] = slots;
+        ctl[cStatus] = status;
+        ctl[cNb] = 0;
+        ctl[cExp] = 0;
+        ctl[cDepth] = 0;
+        ctl[cDone] = 0;
+        ctl[cReused] = kept ? 1 : 0;
+        if (p.out_kept) p.out_kept[gl] = kept;
+    }
+}
+
+__global__ void puct_forget_kernel(ChessParams p) {
+    const int gl = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gl < p.n_games) p.ca.ctl[(size_t)(p.first_game + gl) * kCtlWords + cDone] = 0;
 }
 
 __global__ __launch_bounds__(64) void puct_select_kernel(ChessParams p) {
@@ -192,6 +494,7 @@ __global__ __launch_bounds__(64) void puct_select_kernel(ChessParams p) {
     const uint32_t lane = lane_id();
     int status = uni(ctl[cStatus]);
     int nb = status ? 0 : flush_leaves(p, p.flush);
+    if (p.flush == 0 && uni(ctl[cReused])) nb = 0;  // a kept root is evaluated already
     int nnodes = uni(ctl[cNodes]), slots = uni(ctl[cSlots]);
     uint32_t *paths = p.ca.paths + (size_t)g * p.max_batch * kChessPath;
     uint32_t *meta = p.ca.meta + (size_t)g * p.max_batch;
@@ -213,6 +516,9 @@ __global__ __launch_bounds__(64) void puct_select_kernel(ChessParams p) {
         ctl[cNb] = nb;
         ctl[cExp] += cn.expansions;
         ctl[cDepth] += cn.depth_sum;
+        // the slots in use before this flush, for puct_commit_kernel: its blocks must not read
+        // cSlots, which the block of the flush's last created node rewrites in the same grid
+        ctl[cSlots0] = slots;
         if (p.counts) p.counts[gl] = nb;
     }
     const size_t obase = (size_t)gl * p.bs;
@@ -314,7 +620,7 @@ __global__ __launch_bounds__(64) void puct_commit_kernel(ChessParams p) {
     }
     for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
     const bool last = __ballot(later) == 0ull;
-    const int slots0 = uni(ctl[cSlots]);
+    const int slots0 = uni(ctl[cSlots0]);  // as puct_select_kernel saved it (cSlots changes under this grid)
     int n = uni(p.ca.xinfo[2 * (x0 + j)]);
     const uint32_t mc = (uint32_t)uni(p.ca.xinfo[2 * (x0 + j) + 1]);
     const int base = slots0 + before;
@@ -435,7 +741,7 @@ __global__ __launch_bounds__(64) void puct_end_kernel(ChessParams p) {
     if (gl >= p.n_games) return;
     const int g = p.first_game + gl;
     const CTree t = ctree(p, g);
-    const int32_t *ctl = p.ca.ctl + (size_t)g * kCtlWords;
+    int32_t *ctl = p.ca.ctl + (size_t)g * kCtlWords;
     const uint32_t lane = lane_id();
     const int status = uni(ctl[cStatus]);
     const ChessNode *R = &t.nodes[0];
@@ -500,8 +806,9 @@ __global__ __launch_bounds__(64) void puct_end_kernel(ChessParams p) {
         st.status = status;
         st.expansions = ctl[cExp];
         st.depth_sum = ctl[cDepth];
-        st.leaves = p.sims;
+        st.leaves = ctl[cReused] ? p.sims - 1 : p.sims;
         p.out_stats[gl] = st;
+        ctl[cDone] = status == 0 ? 1 : 0;
     }
 }
 
@@ -509,6 +816,12 @@ __global__ __launch_bounds__(64) void puct_end_kernel(ChessParams p) {
 
 void launch_chess_puct_begin(const ChessParams &p, hipStream_t s) {
     hipLaunchKernelGGL(puct_begin_kernel, dim3(p.n_games), dim3(64), 0, s, p);
+}
+void launch_chess_puct_reroot(const ChessParams &p, hipStream_t s) {
+    hipLaunchKernelGGL(puct_reroot_kernel, dim3(p.n_games), dim3(64), 0, s, p);
+}
+void launch_chess_puct_forget(const ChessParams &p, hipStream_t s) {
+    hipLaunchKernelGGL(puct_forget_kernel, dim3((p.n_games + 63) / 64), dim3(64), 0, s, p);
 }
 void launch_chess_puct_select(const ChessParams &p, hipStream_t s) {
     hipLaunchKernelGGL(puct_select_kernel, dim3(p.n_games), dim3(64), 0, s, p);

@@ -358,6 +358,7 @@ __device__ __forceinline__ void root_init(const ChessParams &p, const CTree &t, 
         ctl[cDepth] = 0;
         ctl[cUse0] = (int32_t)(uint32_t)use0;
         ctl[cUse0 + 1] = (int32_t)(uint32_t)(use0 >> 32);
+        ctl[cDone] = 0;  // this arena no longer holds a finished PUCT tree (zc_chess_puct_begin_reuse)
     }
     wave_sync_mem();
 }

@@ -83,7 +83,12 @@ __device__ __forceinline__ CTree ctree(const ChessParams &p, int g) {
                  a.prior ? a.prior + so : nullptr, a.S};
 }
 
-enum : int { cNodes = 0, cSlots = 1, cStatus = 2, cNb = 3, cExp = 4, cDepth = 5, cUse0 = 6, cHpNode = 8 };
+// cDone: the game's last search was a PUCT search that ran to end with status 0 (its tree may
+// be re-rooted, chess_puct.hip); every search's begin clears it.  cReused: the PUCT search in
+// progress started from a kept subtree (flush 0 has no leaf).  cSlots0: the slots in use before
+// the PUCT flush being committed (puct_select_kernel -> puct_commit_kernel).
+enum : int { cNodes = 0, cSlots = 1, cStatus = 2, cNb = 3, cExp = 4, cDepth = 5, cUse0 = 6, cHpNode = 8,
+             cDone = 10, cReused = 11, cSlots0 = 12 };
 
 struct CLds {
     ChessScratch s;

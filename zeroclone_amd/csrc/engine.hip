@@ -64,7 +64,8 @@ int dalloc(zc_engine *e, T **p, size_t count) {
 }
 
 void free_chess(zc::ChessArena &c) {
-    void *ptrs[] = {c.nodes, c.mv, c.ut, c.ch, c.na, c.w, c.prior, c.ctl, c.paths, c.meta, c.roots, c.xmv, c.xinfo};
+    void *ptrs[] = {c.nodes, c.mv, c.ut, c.ch, c.na, c.w, c.prior, c.ctl, c.paths, c.meta, c.roots, c.xmv, c.xinfo,
+                    c.remap, c.rbase};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     c = zc::ChessArena{};
@@ -1387,6 +1388,37 @@ zc::ChessParams puct_params(zc_engine *e, int32_t first, int32_t n) {
     p.search_no = search_no_at(s, first);
     return p;
 }
+
+// zc_chess_puct_begin / zc_chess_puct_begin_reuse: the same validation and search parameters;
+// the reuse form launches the re-root kernel in place of the begin kernel.
+int chess_puct_begin(zc_engine *eng, int32_t first, int32_t n, const zc_chess_state *d_roots, int32_t sims,
+                     double c_puct, int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no, bool reuse,
+                     int32_t *d_kept, void *hip_stream) {
+    if (!eng) return fail(ZC_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lk(eng->mu);
+    PuctSearch s = eng->chess_puct;
+    if (int r = puct_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, &s)) return r;
+    ZC_HIP(hipSetDevice(eng->cfg.device));
+    if (int r = ensure_chess(eng)) return r;
+    if (reuse && !eng->ca.rbase) {  // the re-root's scratch, with the arena from now on
+        const size_t GM = (size_t)eng->cfg.max_games * (size_t)eng->M;
+        if (!eng->ca.remap)
+            if (int r = dalloc(eng, &eng->ca.remap, GM)) return r;
+        if (int r = dalloc(eng, &eng->ca.rbase, GM)) return r;
+    }
+    eng->chess_puct = s;
+    if (!n) return ZC_OK;
+    zc::ChessParams p = puct_params(eng, first, n);
+    p.roots = d_roots;
+    if (reuse) {
+        p.out_kept = d_kept;
+        zc::launch_chess_puct_reroot(p, (hipStream_t)hip_stream);
+    } else {
+        zc::launch_chess_puct_begin(p, (hipStream_t)hip_stream);
+    }
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1394,17 +1426,28 @@ extern "C" {
 int zc_chess_puct_begin(zc_engine *eng, int32_t first, int32_t n, const zc_chess_state *d_roots, int32_t sims,
                         double c_puct, int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no,
                         void *hip_stream) {
+    return chess_puct_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, false, nullptr,
+                            hip_stream);
+}
+
+int zc_chess_puct_begin_reuse(zc_engine *eng, int32_t first, int32_t n, const zc_chess_state *d_roots, int32_t sims,
+                              double c_puct, int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no,
+                              int32_t *d_kept, void *hip_stream) {
+    return chess_puct_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, true, d_kept,
+                            hip_stream);
+}
+
+int zc_chess_puct_forget(zc_engine *eng, int32_t first, int32_t n, void *hip_stream) {
     if (!eng) return fail(ZC_EINVAL, "null argument");
+    if (int r = check_games(eng, first, n)) return r;
     std::lock_guard<std::mutex> lk(eng->mu);
-    PuctSearch s = eng->chess_puct;
-    if (int r = puct_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, &s)) return r;
+    if (!n || !eng->ca.nodes) return ZC_OK;  // no tree yet: nothing is kept
     ZC_HIP(hipSetDevice(eng->cfg.device));
-    if (int r = ensure_chess(eng)) return r;
-    eng->chess_puct = s;
-    if (!n) return ZC_OK;
-    zc::ChessParams p = puct_params(eng, first, n);
-    p.roots = d_roots;
-    zc::launch_chess_puct_begin(p, (hipStream_t)hip_stream);
+    zc::ChessParams p{};
+    p.first_game = first;
+    p.n_games = n;
+    p.ca = eng->ca;
+    zc::launch_chess_puct_forget(p, (hipStream_t)hip_stream);
     ZC_HIP(hipGetLastError());
     return ZC_OK;
 }

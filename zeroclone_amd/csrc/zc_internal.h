@@ -171,6 +171,10 @@ struct ChessArena {
     // material | check << 16} [G][max_batch][2], between the expand and commit kernels
     uint16_t *xmv = nullptr;
     int32_t *xinfo = nullptr;
+    // the PUCT re-root's scratch (allocated on the first zc_chess_puct_begin_reuse): the new id
+    // of each kept node [G][M] by old id, and each kept node's new first slot [G][M] by new id
+    uint16_t *remap = nullptr;
+    uint32_t *rbase = nullptr;
     int64_t S = 0;
 };
 
@@ -202,6 +206,7 @@ struct ChessParams {
     int logits_f16;
     int leaf_rows;              // backup: rows of values / logits per game (0: bs; 1: a roots-only flush)
     float *out_prior;           // end (optional): root priors after noise [n][ZC_CHESS_MAX_MOVES]
+    int32_t *out_kept;          // re-root (optional): [n] nodes kept, 0 = started afresh
     // host-policy search (zc_chess_hp_*): leaf index in the flush, untried index, walk output
     int hp_leaf, hp_index;
     zc_chess_hp_node *hp_node;
@@ -346,6 +351,8 @@ void launch_chess_hp_walk(const ChessParams &p, hipStream_t s);
 void launch_chess_hp_expand(const ChessParams &p, hipStream_t s);
 
 void launch_chess_puct_begin(const ChessParams &p, hipStream_t s);
+void launch_chess_puct_reroot(const ChessParams &p, hipStream_t s);
+void launch_chess_puct_forget(const ChessParams &p, hipStream_t s);
 void launch_chess_puct_select(const ChessParams &p, hipStream_t s);
 void launch_chess_puct_backup(const ChessParams &p, hipStream_t s);
 void launch_chess_puct_end(const ChessParams &p, hipStream_t s);

@@ -745,16 +745,29 @@ class ChessSelfPlay(_SelfPlayPool):
                  freedom: float = 3.0, net=None, init_fen: str | None = None, games_cap: int | None = None,
                  hist_cap: int = 1024, puct_net=None, temperature: float = 1.0, puct_seed: int = 1,
                  puct_streams: int = 1, streams: int = 1, record_policy: bool = False,
-                 pi_slot_cap: int | None = None, pi_pool_cap: int | None = None):
+                 pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
+                 reuse_tree: bool = False, tree_nodes: int | None = None):
         """record_policy: every step()'s root visit counts go with the positions into the
-        trajectories (TrajBatch.pi / policy_targets(4096)), in every search mode."""
+        trajectories (TrajBatch.pi / policy_targets(4096)), in every search mode.
+        reuse_tree (PUCT mode): each search keeps the subtree of the move just played
+        (ChessPuctSearch(reuse=True)) and adds sims - 1 visits to it; a tree holds up to
+        `tree_nodes` nodes (default min(2 * sims, 65534)) and 64 child slots per node, and a
+        search whose kept nodes or slots leave no room for its own starts afresh.  start() and
+        adopt() drop the kept trees.  With record_policy a kept root's visit counts can exceed
+        sims (a chess game has no fixed length, so no bound is refused here): a count beyond 16
+        bits is recorded saturated and sets the recorder's ZC_TRAJ_PI_OVERFLOW bit 2."""
+        if reuse_tree and puct_net is None:
+            raise ValueError("reuse_tree keeps the PUCT search's tree: it needs puct_net")
         init = _native.chess_from_fen(init_fen) if init_fen else _native.chess_init()
         init = torch.from_numpy(np.frombuffer(init.tobytes(), np.uint8).reshape(1, 72).copy())
         max_len = 2 * hist_cap + 1
         if record_policy and pi_slot_cap is None:   # a position has at most min(sims, 256) visited moves
-            pi_slot_cap = (max_len - 1) * min(sims, _native.CHESS_MAX_MOVES)
+            # (a kept root brings the visits of earlier searches: up to every move)
+            pi_slot_cap = (max_len - 1) * (_native.CHESS_MAX_MOVES if reuse_tree else min(sims, _native.CHESS_MAX_MOVES))
         super().__init__(games, sims, c, batch_size, seed, rank, device, temperature, record_policy,
-                         init, max_len, games_cap, pi_slot_cap, pi_pool_cap)
+                         init, max_len, games_cap, pi_slot_cap, pi_pool_cap,
+                         max_sims=(tree_nodes or min(2 * sims, 65534)) if reuse_tree else None)
+        self.reuse_tree = bool(reuse_tree)
         self.eng.chess_reserve()
         self.policy, self.freedom = int(policy), float(freedom)
         self.init_row = init.to(self.dev)
@@ -764,7 +777,8 @@ class ChessSelfPlay(_SelfPlayPool):
         # from the select kernel (no conversion launch per flush)
         nhwc = bool(getattr(puct_net, "conv_head", False)) and os.environ.get("ZC_PUCT_NHWC", "1") != "0"   # 0: A/B
         self._networks(net, valued.ChessValuedSearch, dict(policy=self.policy, freedom=self.freedom), streams,
-                       puct_net, valued.ChessPuctSearch, dict(seed=puct_seed, planes_nhwc=nhwc), puct_streams)
+                       puct_net, valued.ChessPuctSearch, dict(seed=puct_seed, planes_nhwc=nhwc, reuse=self.reuse_tree),
+                       puct_streams)
         self.hist_cap = hist_cap  # moves per side
         self.hist = torch.zeros((games, 2, self.hist_cap), dtype=torch.int16, device=self.dev)
         self.hlen = torch.zeros((games, 2), dtype=torch.int32, device=self.dev)
@@ -780,6 +794,8 @@ class ChessSelfPlay(_SelfPlayPool):
     def start(self, quota: int | None = None):
         self.roots.copy_(self.init_row.expand_as(self.roots))
         self.hlen.zero_()
+        if self.reuse_tree:
+            self.ps.forget()
         self.traj.start(quota, games_cap=quota)
 
     def _search(self, s: int):
@@ -807,6 +823,8 @@ class ChessSelfPlay(_SelfPlayPool):
         self.roots.copy_(other.roots)
         self.hist.copy_(other.hist)
         self.hlen.copy_(other.hlen)
+        if self.reuse_tree:
+            self.ps.forget()
 
     def _launch(self, moves: int, budget: int | None, carry: bool, s: int):
         """zc_chess_selfplay_async / zc_chess_selfplay_pooled_async."""

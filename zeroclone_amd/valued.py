@@ -357,13 +357,20 @@ class ChessPuctSearch(_PuctSearch):
 
     net_fn(leaves, planes, counts) -> (values fp64 [n*bs], logits [n*bs, 4096] fp32/fp16,
     index from*64 + to).  Flush 0 evaluates the roots; Dirichlet(alpha) noise of weight eps
-    goes on the root priors; end() picks by visits (temperature 0) or samples."""
+    goes on the root priors; end() picks by visits (temperature 0) or samples.
+
+    reuse=True: every search keeps, per game, the subtree of its root position when the game's
+    previous search holds it one or two plies below its root (zc_chess_puct_begin_reuse), and
+    then adds sims - 1 visits below the kept ones; `kept` [n] int32 = nodes kept (0: a fresh
+    tree).  The engine needs max_sims above sims for anything to be kept; forget() drops the
+    trees, and so does any other chess search of the game."""
     STATE, LEAF, PLANES, MOVE, NA = ChessValuedSearch.STATE, ChessValuedSearch.LEAF, (17, 8, 8), torch.int16, \
         _native.CHESS_MAX_MOVES
 
     def __init__(self, eng: "_native.NativeEngine", n_games: int, batch_size: int = 32, c_puct: float = 1.5,
                  dirichlet_alpha: float = 0.3, dirichlet_eps: float = 0.25, seed: int = 0,
-                 planes_dtype: torch.dtype = torch.float16, leaves: bool = True, planes_nhwc: bool = False):
+                 planes_dtype: torch.dtype = torch.float16, leaves: bool = True, planes_nhwc: bool = False,
+                 reuse: bool = False):
         """planes_nhwc: the select kernel writes the planes in the MFMA tower's input layout, fp16
         [n * batch_size, 64, 32] (17 planes then zeros, square-major), so the network takes them
         without a conversion launch (MfmaPolicyValueNetwork with the convolutional head)."""
@@ -374,10 +381,26 @@ class ChessPuctSearch(_PuctSearch):
             self.PLANES = (64, 32)
         self._alloc_puct(eng, n_games, batch_size, c_puct, dirichlet_alpha, dirichlet_eps, seed, planes_dtype, leaves)
         eng.chess_reserve()   # the tree arena exists before any graph capture
+        self.reuse = bool(reuse)
+        self.kept = None
+        if self.reuse:   # and so does the re-root's scratch
+            self.kept = torch.zeros(n_games, dtype=torch.int32, device=self.dev)
+            z = torch.zeros((1, 72), dtype=torch.uint8, device=self.dev)
+            eng.chess_puct_begin_reuse(0, 0, z.data_ptr(), 2, c_puct, batch_size, dirichlet_alpha, dirichlet_eps, seed)
+            self.forget()   # trees of an earlier search object on this engine are not this one's
+
+    def forget(self, first_game: int = 0, n: int | None = None):
+        """Drop the kept trees of games [first_game, first_game + n) (default: this search's n
+        games), stream-ordered: their next search starts afresh."""
+        self.eng.chess_puct_forget(first_game, self.n if n is None else n, _stream(self.dev))
 
     def _begin(self, first, roots, sims, temperature, s):
-        self.eng.chess_puct_begin(first, self.n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps,
-                                  self.seed, self.search_no.data_ptr(), stream=s)
+        e, args = self.eng, (first, self.n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps, self.seed,
+                             self.search_no.data_ptr())
+        if self.reuse:
+            e.chess_puct_begin_reuse(*args, self.kept.data_ptr(), stream=s)
+        else:
+            e.chess_puct_begin(*args, stream=s)
 
     def _select(self, first, m, f, lv, pv, cv, s):
         self.eng.chess_puct_select(first, m, f, _ptr(lv), pv.data_ptr(), pv.dtype == torch.float16, cv.data_ptr(), s,
