@@ -201,8 +201,18 @@ int zc_c4_play_async(zc_engine *eng, int32_t n_games, zc_c4_state *d_states, con
 
 #define ZC_STATUS_NO_MOVES 1     /* root has no legal move                                */
 #define ZC_STATUS_BAD_STATE 2    /* sentinel bits set / overlapping stones / bad turn    */
-#define ZC_STATUS_INTERNAL 3     /* search invariant violated (never expected)            */
-#define ZC_STATUS_CAPACITY 4     /* chess: child-slot pool or leaf depth (63) exhausted   */
+/* ZC_STATUS_INTERNAL: a search invariant was violated (never expected from the library's own
+ * values), or — the PUCT searches — the caller's network handed over something no search can
+ * use: a NaN or infinite leaf value, or logits whose softmax over the node's legal moves has no
+ * finite positive sum (NaN or +inf on a legal move, -inf on all of them).  The game's search
+ * stops at that backup: no move (0xFFFF / -1), its tree is not kept for reuse, the other games
+ * of the call are untouched.  Logits of illegal moves are never read; -inf on some legal moves
+ * is a mask (prior exactly 0).
+ * ZC_STATUS_CAPACITY (chess): the child-slot pool ran out, or a walk stood on an expanded,
+ * non-terminal node at level 62 (root = level 0): the deepest node a chess tree holds is at
+ * level 62, and a search that has to go below it ends without a move. */
+#define ZC_STATUS_INTERNAL 3
+#define ZC_STATUS_CAPACITY 4
 
 /* Value('random_rollout').batch(states, backend=c4_backend) (engine/value_functions.py:20-45)
  * on the device: the n states are rolled out IN ORDER on engine game `game`'s stream, as the
@@ -349,8 +359,8 @@ int zc_chess_init(zc_chess_state *out);
  *   d_out_move[i]                       chosen move (packed uint16, 0xFFFF if none)
  *   d_out_root_na[i*ZC_CHESS_MAX_MOVES + j]  Na of root move j (the root's get_legal_moves order)
  *   d_out_stats[i]                      counters; status ZC_STATUS_CAPACITY when the game's
- *                                       child-slot pool (64 * (max_sims+1)) or the leaf depth
- *                                       limit (63) was exhausted
+ *                                       child-slot pool (64 * (max_sims+1)) was exhausted or a
+ *                                       walk had to go below level 62 (ZC_STATUS_CAPACITY above)
  * The engine allocates its chess tree arena on the first chess search.
  * zc_chess_search_async evaluates leaves with Value('crude_chess_score')
  * (value_functions.py:48-55, configs/crude_chess.yaml) inside the kernel; batch_size <= 256. */

@@ -37,6 +37,18 @@ class C4Rules:
         return oracle.check_win(s[0], s[1])
 
 
+class Capacity(Exception):
+    """The search ended with status CAPACITY (no move) in flush `flush`; kind "depth": a walk
+    stood on an evaluated, non-terminal node at level max_level (the flush selects no leaf);
+    kind "slots": a node created in the flush did not fit in slot_cap (the flush's leaves are
+    selected, none is backed up).  Visit counts are then unspecified: the device leaves the
+    virtual losses of the flush's walks in place."""
+
+    def __init__(self, flush, kind):
+        super().__init__(f"CAPACITY ({kind}) in flush {flush}")
+        self.flush, self.kind = flush, kind
+
+
 class Node:
     def __init__(self, state, rules=ChessRules):
         self.s = state
@@ -49,23 +61,32 @@ class Node:
         self.evaluated = False
 
 
-def search(state, sims, bs, c, value_fn, prior_fn, rules=ChessRules, flush_fn=None):
+def search(state, sims, bs, c, value_fn, prior_fn, rules=ChessRules, flush_fn=None, max_level=None, slot_cap=None):
     """value_fn(state) -> value for the side to move; prior_fn(node) -> priors (list,
     float) for the node's moves.  flush_fn(states), if given, is called once per flush with
     the states of its non-terminal leaves before any value_fn / prior_fn call of that flush
     (a batched network fills the cache they read).  Returns (root moves, root visits,
-    chosen index)."""
+    chosen index).
+
+    The two limits of the chess kernel, off by default (None): max_level (the kernel's 62) — a
+    walk standing on an evaluated, non-terminal node at this level raises Capacity; slot_cap
+    (the kernel's 64 * (max_sims + 1)) — the nodes take len(moves) slots in creation order, the
+    root first, and a flush that created a node that does not fit raises Capacity after its
+    walks."""
     root = Node(state, rules)
+    slots = len(root.moves)
     flushes = 1 + (sims - 1 + bs - 1) // bs
     for f in range(flushes):
         nb = 1 if f == 0 else max(0, min(bs, sims - 1 - (f - 1) * bs))
-        leaves = []
+        leaves, made = [], []
         for _ in range(nb):
             if f == 0:
                 leaves.append((root, []))
                 continue
             node, path = root, []
             while len(node.moves) and node.evaluated:
+                if max_level is not None and len(path) >= max_level:
+                    raise Capacity(f, "depth")
                 sq = math.sqrt(float(sum(node.N)))
                 best, bv = -1, -math.inf
                 for j in range(len(node.moves)):
@@ -79,9 +100,14 @@ def search(state, sims, bs, c, value_fn, prior_fn, rules=ChessRules, flush_fn=No
                 if node.child[best] is None:
                     node.child[best] = Node(rules.play(node.s, node.moves[best]), rules)
                     node = node.child[best]
+                    made.append(node)
                     break
                 node = node.child[best]
             leaves.append((node, path))
+        for node in made:
+            slots += len(node.moves)
+            if slot_cap is not None and slots > slot_cap:
+                raise Capacity(f, "slots")
         if flush_fn is not None:
             flush_fn([node.s for node, _ in leaves if len(node.moves)])
         for node, path in leaves:

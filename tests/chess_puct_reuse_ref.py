@@ -7,7 +7,7 @@ arrays) as a pure function."""
 import numpy as np
 
 from oracle.puct_ref import ChessRules, Node
-from puct_reuse_ref import count_nodes, search  # noqa: F401  (search: re-exported for the tests)
+from puct_reuse_ref import count_nodes, count_slots, search  # noqa: F401  (re-exported for the tests)
 
 SLOTS_PER_NODE = 64   # kChessSlotsPerNode: a tree of M nodes has S = 64 * M child slots
 SLOT_ARRAYS = ("mv", "prior", "na", "w", "child")
@@ -29,10 +29,6 @@ def advance(root, k):
     if found is None or not found.evaluated or len(found.moves) == 0:
         return None
     return found
-
-
-def count_slots(node):
-    return len(node.moves) + sum(count_slots(ch) for ch in node.child if ch is not None)
 
 
 def next_root(root, state, sims, max_nodes):

@@ -4,26 +4,40 @@ puct_ref.search restated so that it takes and returns a root Node, the rule that
 new root, and the re-root of a zc_debug_c4_puct_tree dump as a pure function."""
 import math
 
-from oracle.puct_ref import C4Rules, Node
+from oracle.puct_ref import C4Rules, Capacity, Node
 
 
-def search(root, sims, bs, c, value_fn, prior_fn, rules=C4Rules, reused=False):
+def count_slots(node):
+    return len(node.moves) + sum(count_slots(ch) for ch in node.child if ch is not None)
+
+
+def search(root, sims, bs, c, value_fn, prior_fn, rules=C4Rules, reused=False, max_level=None, slot_cap=None,
+           created=None, mutation=None):
     """puct_ref.search from `root` (a fresh Node, or a kept one with reused=True: flush 0, the
     root's own evaluation, then has no leaf, so the search adds sims - 1 visits below it).
-    Returns (root moves, root visits, chosen index); the tree stays in `root`."""
+    Returns (root moves, root visits, chosen index); the tree stays in `root`.
+
+    max_level / slot_cap: puct_ref.search's two limits (a kept tree's slots count as taken);
+    they raise puct_ref.Capacity.  created: a list that takes the nodes this search creates, in
+    creation order.  mutation: a deliberately wrong search for the mutation checks — "sign" (the
+    backup does not alternate the value's sign), "loss" (the virtual loss is not undone) or
+    "once" (a leaf pending more than once in a flush is backed up once)."""
+    slots = count_slots(root)
     flushes = 1 + (sims - 1 + bs - 1) // bs
     for f in range(flushes):
         if f == 0:
             nb = 0 if reused else 1
         else:
             nb = max(0, min(bs, sims - 1 - (f - 1) * bs))
-        leaves = []
+        leaves, made = [], []
         for _ in range(nb):
             if f == 0:
                 leaves.append((root, []))
                 continue
             node, path = root, []
             while len(node.moves) and node.evaluated:
+                if max_level is not None and len(path) >= max_level:
+                    raise Capacity(f, "depth")
                 sq = math.sqrt(float(sum(node.N)))
                 best, bv = -1, -math.inf
                 for j in range(len(node.moves)):
@@ -37,10 +51,22 @@ def search(root, sims, bs, c, value_fn, prior_fn, rules=C4Rules, reused=False):
                 if node.child[best] is None:
                     node.child[best] = Node(rules.play(node.s, node.moves[best]), rules)
                     node = node.child[best]
+                    made.append(node)
                     break
                 node = node.child[best]
             leaves.append((node, path))
+        if created is not None:
+            created.extend(made)
+        for node in made:
+            slots += len(node.moves)
+            if slot_cap is not None and slots > slot_cap:
+                raise Capacity(f, "slots")
+        seen = set()
         for node, path in leaves:
+            if mutation == "once":
+                if id(node) in seen:
+                    continue
+                seen.add(id(node))
             if len(node.moves) == 0:
                 v = -1.0 if rules.win(node.s) else 0.0
             else:
@@ -50,8 +76,8 @@ def search(root, sims, bs, c, value_fn, prior_fn, rules=C4Rules, reused=False):
                     node.evaluated = True
             d = len(path)
             for l, (par, a) in enumerate(path, start=1):
-                r = v if (d - l) % 2 == 0 else -v
-                par.W[a] = par.W[a] + 1.0 - r
+                r = v if (d - l) % 2 == 0 or mutation == "sign" else -v
+                par.W[a] = par.W[a] + (0.0 if mutation == "loss" else 1.0) - r
     best, bn = -1, -1
     for j, n in enumerate(root.N):
         if n > bn:

@@ -103,6 +103,7 @@ C4_PNODE_DTYPE = np.dtype([("s0", "<u8"), ("s1", "<u8"), ("order", "<u4"), ("tur
 assert C4_PNODE_DTYPE.itemsize == 192
 ZC_CHESS_WIN, ZC_CHESS_STALEMATE, ZC_CHESS_FIFTY, ZC_CHESS_OVERFLOW = 1, 2, 4, 8
 ZC_POLICY_RANDOM, ZC_POLICY_IMMEDIATE_VALUE = 0, 1
+ZC_STATUS_INTERNAL = 3
 ZC_STATUS_CAPACITY = 4
 assert CHESS_STATE_DTYPE.itemsize == 72
 assert C4_STATE_DTYPE.itemsize == ctypes.sizeof(C4State) == 24

@@ -404,7 +404,7 @@ __global__ __launch_bounds__(64) void c4_puct_backup_kernel(C4PuctParams p) {
     if (gl >= p.n_games) return;
     const int g = p.first_game + gl;
     C4PNode *T = pnodes(p, g);
-    const int32_t *ctl = p.ctl + (size_t)g * kCtlWords;
+    int32_t *ctl = p.ctl + (size_t)g * kCtlWords;
     const uint32_t lane = lane_id();
     const int nb = uni(ctl[pNb]);
     if (uni(ctl[pStatus]) || nb == 0) return;
@@ -422,6 +422,10 @@ __global__ __launch_bounds__(64) void c4_puct_backup_kernel(C4PuctParams p) {
             v = uni((int)N->won) ? -1.0 : 0.0;  // the side to move has lost / a full board
         } else {
             v = __hiloint2double(uni(__double2hiint(p.values[li])), uni(__double2loint(p.values[li])));
+            if (!(fabs(v) < INFINITY)) {  // a NaN or infinite value: the game's backup stops here
+                if (lane == 0) ctl[pStatus] = ZC_STATUS_INTERNAL;
+                return;
+            }
             if (!uni((int)N->evaluated)) {
                 // priors: softmax of the column logits over the node's legal columns, in
                 // move-list order (slot k = lane k)
@@ -434,6 +438,11 @@ __global__ __launch_bounds__(64) void c4_puct_backup_kernel(C4PuctParams p) {
                 const float mx = wave_max_f(lg);
                 const float e = valid ? expf(lg - mx) : 0.0f;
                 const float sum = wave_sum_f(e);
+                // a NaN or +inf logit on a legal column, or -inf on all of them: no priors
+                if (__ballot(!(sum > 0.0f && sum < INFINITY))) {
+                    if (lane == 0) ctl[pStatus] = ZC_STATUS_INTERNAL;
+                    return;
+                }
                 float pr = e / sum;
                 if (node == 0 && p.dir_eps > 0.0f) {  // Dirichlet(alpha) noise on the root priors
                     const float gm = valid ? gamma_draw(p.dir_alpha, key, (uint32_t)g, lane, search_number(p, gl)) : 0.0f;

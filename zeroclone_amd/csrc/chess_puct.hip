@@ -111,6 +111,10 @@ __device__ int puct_walk(const ChessParams &p, const CTree &t, CLds &L, int &nno
         }
         argmax64(bv, bi);
         const int best = uni(bi);
+        if ((uint32_t)best >= (uint32_t)nm) {  // no score compared above -inf (all NaN): no edge to take
+            status = ZC_STATUS_INTERNAL;
+            break;
+        }
         const uint32_t s = base + (uint32_t)best;
         const int bq = best >> 6;
         const uint32_t chv = bq == 0 ? ch_r[0] : bq == 1 ? ch_r[1] : bq == 2 ? ch_r[2] : ch_r[3];
@@ -658,7 +662,7 @@ __global__ __launch_bounds__(64) void puct_backup_kernel(ChessParams p) {
     if (gl >= p.n_games) return;
     const int g = p.first_game + gl;
     const CTree t = ctree(p, g);
-    const int32_t *ctl = p.ca.ctl + (size_t)g * kCtlWords;
+    int32_t *ctl = p.ca.ctl + (size_t)g * kCtlWords;
     const uint32_t lane = lane_id();
     const int nb = uni(ctl[cNb]);
     if (uni(ctl[cStatus]) || nb == 0) return;
@@ -676,6 +680,10 @@ __global__ __launch_bounds__(64) void puct_backup_kernel(ChessParams p) {
             v = uni((int)N->check) ? -1.0 : 0.0;  // checkmated side to move / no moves
         } else {
             v = __hiloint2double(uni(__double2hiint(p.values[li])), uni(__double2loint(p.values[li])));
+            if (!(fabs(v) < INFINITY)) {  // a NaN or infinite value: the game's backup stops here
+                if (lane == 0) ctl[cStatus] = ZC_STATUS_INTERNAL;
+                return;
+            }
             if (!uni((int)N->evaluated)) {
                 // priors: softmax of the logits of this node's legal moves (from*64 + to)
                 const uint32_t base = uni(N->base);
@@ -700,6 +708,11 @@ __global__ __launch_bounds__(64) void puct_backup_kernel(ChessParams p) {
                     sum += e[q];
                 }
                 sum = wave_sum_f(sum);
+                // a NaN or +inf logit on a legal move, or -inf on all of them: no priors
+                if (__ballot(!(sum > 0.0f && sum < INFINITY))) {
+                    if (lane == 0) ctl[cStatus] = ZC_STATUS_INTERNAL;
+                    return;
+                }
                 float pr[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) pr[q] = e[q] / sum;

@@ -136,7 +136,7 @@ struct ExtParams {
 // Per game: M node records (ChessNode) and a pool of S child slots; node i's moves occupy
 // slots [base, base + nmoves) in the reference's move order.  Slot arrays are SoA so the
 // UCT scan over a node's children is a coalesced read per array.
-constexpr int kChessPath = 64;      // deepest leaf a flush may hold (levels 0..63)
+constexpr int kChessPath = 64;      // path words per leaf; the walks stop at level kChessPath - 2 = 62 (nodes at levels 0..62)
 constexpr int kChessSlotsPerNode = 64;
 
 struct ChessNode {

@@ -631,6 +631,16 @@ class C4SelfPlay(_SelfPlayPool):
     def _root_moves(self, s: int):
         return None   # a visit count's index is its column
 
+    def check(self):
+        """Raises when a game's last stepwise search failed (a failed search plays no move, so the
+        game stays where it is and the next step's search of it fails the same way)."""
+        if self.ps is None and self.vs is None:
+            return
+        bad = self.stats[:, 5].cpu()
+        if (bad == _native.ZC_STATUS_INTERNAL).any():
+            raise RuntimeError(f"the search of {int((bad == _native.ZC_STATUS_INTERNAL).sum())} game(s) ended with "
+                               "ZC_STATUS_INTERNAL: the network returned a non-finite value or logits")
+
     def _play(self, s: int):
         self.eng.c4_play_async(self.roots.data_ptr(), self.G, self.moves.data_ptr(), self.results.data_ptr(),
                                reset=not self.record, stream=s)
@@ -860,8 +870,9 @@ class ChessSelfPlay(_SelfPlayPool):
                                "(the game was not judged)")
         if e[1]:
             raise RuntimeError("chess search exceeded the tree's child-slot pool or depth limit")
-        if e[2]:
-            raise RuntimeError("no legal move at a non-terminal root")
+        if e[2]:   # a search handed over no move: its status was not 0
+            raise RuntimeError("a search returned no move for a live game: no legal move at a non-terminal root, or "
+                               "(PUCT) the network returned a non-finite value or logits (ZC_STATUS_INTERNAL)")
 
 
 def simulate_games(pool, total_games: int, max_steps: int | None = None, check_every: int = 4) -> list[int]:
