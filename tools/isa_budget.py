@@ -19,7 +19,12 @@ the leaf loop itself and the others in a loop of their own — and prints
       continue  one block without a fill that goes on to another: from one win test round the
                 block loop to the next (told from the exit by its LDS read of the next legal
                 set's order words)
-    (no window advance and no empty view on any of them);
+    (no window advance / stream refill and no empty view on any of them);
+  * the stream: the instructions of the leaf head's refill (the code the "enough words ahead?"
+    test branches around: the 64-word window advance of the register-window stream, the
+    224-word bulk step of the draw-ring stream), all of its branches counted, per step and
+    per 64 generated words, and the instructions of a view (from the refill's join to the
+    lane's word: a ds_bpermute_b32 of the window registers, or a byte read of the draw ring);
   * next_free_vgpr and the private segment size of c4_selfplay_kernel<false> and
     c4_search_kernel<false,false>.
 
@@ -168,6 +173,33 @@ def has(byname, path, text):
     return sum(text in s for b in path for _, s in byname[b].ins)
 
 
+# what marks the stream's refill code, and the words one pass of it generates: the tempering
+# mask of the register-window stream (one 64-word window per advance), the draw extraction's
+# mask of the draw-ring stream (kLStep = 224 words per step)
+STREAM_MARKS = {"0x9d2c5680": 64, "0x80004000": 224}
+VIEW_OPS = ("ds_bpermute_b32", "ds_read_u8")
+
+
+def stream_budget(blocks, byname, head, out):
+    """The refill the leaf head branches around, and the view after it (see the module docstring)."""
+    order = [b.name for b in blocks]
+    vi = next(i for i, n in enumerate(head) if any(op in VIEW_OPS for op, _ in byname[n].ins))
+    view, test = byname[head[vi]], byname[head[vi - 1]]
+    lo, hi = order.index(test.name) + 1, order.index(view.name)
+    region = order[lo:hi]   # the test falls into the refill and branches to the view
+    if view.name not in test.succ or not region:
+        raise SystemExit("isa_budget: no refill between the stream test and the view")
+    words = next((w for b in region for m, w in STREAM_MARKS.items() if has(byname, [b], m)), None)
+    if words is None:
+        raise SystemExit("isa_budget: the refill region holds no stream constant")
+    n = cost(byname, region)
+    nview = 1 + next(i for i, (op, _) in enumerate(view.ins) if op in VIEW_OPS)
+    print(f"stream refill  {fmt_counts(byname, region)}  per {words} words, {n * 64 / words:.1f} per 64 words"
+          f"  ({test.name} -> {' '.join(region)})", file=out)
+    print(f"stream view    {nview:3d} instructions  ({' '.join(s.split()[0] for _, s in view.ins[:nview])})", file=out)
+    return {"refill": n, "words": words, "per64": n * 64 / words, "view": nview}
+
+
 def analyse(lines, out):
     fn, blocks = parse_function(lines, KERNEL)
     byname = {b.name: b for b in blocks}
@@ -196,8 +228,9 @@ def analyse(lines, out):
             raise SystemExit(f"isa_budget: no path for {what}")
         return min(paths, key=lambda p: cost(byname, p))
 
-    # no path advances the window or meets an empty view (the temper's constant marks both)
-    calm = {b.name for b in in_leaf if not has(byname, [b.name], "0x9d2c5680")}
+    # no path advances the window / refills the stream or meets an empty view (the temper's
+    # constant, or the draw extraction's, marks both)
+    calm = {b.name for b in in_leaf if not any(has(byname, [b.name], m) for m in STREAM_MARKS)}
     testnames = {t.name for t in tests}
     # leaf header .. win test: the leaf's prologue and one block, by the prefix sums it passes
     head = all_paths(byname, Lh, P1.name, calm - testnames)
@@ -220,8 +253,10 @@ def analyse(lines, out):
     for name, p in paths:
         print(f"path {name:<9} {fmt_counts(byname, p)}", file=out)
     print(file=out)
-    text = "\n".join(lines)
     res = {name: cost(byname, p) for name, p in paths}
+    res["stream"] = stream_budget(blocks, byname, nofill, out)
+    print(file=out)
+    text = "\n".join(lines)
     for key in [KERNEL] + ALSO:
         m = re.search(r"\.amdhsa_kernel (\S*" + re.escape(key) + r"\S*)\n(.*?)\.end_amdhsa_kernel", text, re.S)
         body = m.group(2)

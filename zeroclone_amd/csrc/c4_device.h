@@ -16,8 +16,9 @@ constexpr uint32_t kRingMask = kRingWords - 1;
 constexpr uint64_t kBottom = 0x0000040810204081ull;  // bit 7c: bottom cell of column c
 constexpr uint64_t kFull = kBottom * 0x3Full;        // the 42 playable cells
 constexpr uint64_t kTop = kBottom << 5;              // top playable cell of each column
-// LDS tables: move-list order[128] u32, then sel[128][8] u8 (the r-th set bit of a 7-bit mask)
-constexpr int kTabBytes = 128 * 4 + 128 * 8;
+// LDS tables: move-list order[128] u32, then sel[128][8] u8 (the r-th set bit of a 7-bit mask),
+// then draw_order[128] u32 (the order words indexed by a word's top three tempered bits)
+constexpr int kTabBytes = 128 * 4 + 128 * 8 + 128 * 4;
 
 // Untried moves of a node (record +4 / Fresh.u): bit i (i < 7) set while move i of the
 // node's move list is untried; bits 28..31 = number of moves.  The reference keeps the
@@ -27,9 +28,21 @@ __device__ __forceinline__ uint32_t untried_init(uint32_t n) { return ((1u << n)
 __device__ __forceinline__ uint32_t untried_count(uint32_t u) { return (uint32_t)__popc(u & 0x7Fu); }
 
 // Fill the LDS tables (whole workgroup): s_order = d_order; sel[m][r] = position of the r-th
-// set bit of m (7 when m has fewer), right after s_order.
+// set bit of m (7 when m has fewer), right after s_order; then draw_order.
+// draw_order[m]: random.choice over the n moves of legal set m draws getrandbits(k) = t >> (3 - k)
+// from a word's top three tempered bits t (k = n.bit_length() <= 3) and accepts it when < n,
+// i.e. when t < n << (3 - k).  The word keeps that threshold in bits 24..27 and, in bits
+// 3t..3t+2, the column of move t >> (3 - k) for every accepted t: a rollout block tests and
+// maps t as it stands, without the shift (and without computing it from n).
 __device__ __forceinline__ void load_tables(uint32_t *s_order) {
-    for (int i = (int)threadIdx.x; i < 128; i += blockDim.x) s_order[i] = d_order[i];
+    for (int i = (int)threadIdx.x; i < 128; i += blockDim.x) {
+        const uint32_t o = d_order[i], n = (o >> 24) & 15u;
+        s_order[i] = o;
+        const uint32_t sh = n ? (uint32_t)__builtin_clz(n) - 29u : 0u;
+        uint32_t e = (n << sh) << 24;
+        for (uint32_t t = 0; t < (n << sh); ++t) e |= ((o >> (3u * (t >> sh))) & 7u) << (3u * t);
+        s_order[128 + 256 + i] = e;
+    }
     uint8_t *const s_sel = (uint8_t *)(s_order + 128);
     for (int i = (int)threadIdx.x; i < 1024; i += blockDim.x) {
         const uint32_t m = (uint32_t)i >> 3, r = (uint32_t)i & 7u;
@@ -46,6 +59,7 @@ __device__ __forceinline__ void load_tables(uint32_t *s_order) {
     }
 }
 __device__ __forceinline__ const uint8_t *sel_table(const uint32_t *s_order) { return (const uint8_t *)(s_order + 128); }
+__device__ __forceinline__ const uint32_t *draw_order_table(const uint32_t *s_order) { return s_order + 128 + 256; }
 constexpr int kWin = 64;                             // RNG window: one word per lane
 // LDS bytes after the leaves' paths: select_flush stores a path with all 64 lanes, so the
 // last leaf's lanes >= kMaxDepth land here
@@ -271,12 +285,30 @@ __device__ __forceinline__ void rng_close(const Rng &r, uint64_t use0, uint64_t 
 }
 
 // ------------------------------------------------------------------ the stream in LDS
-// The fused search (c4_search_kernel) keeps its game's stream in a 1024-word LDS ring
-// instead of the HBM ring: the recurrence runs one 64-word step per window advance, lane l
-// generating x[W + 128 + l] (W = the new window start) from inputs read one advance earlier
-// (x[p-624], x[p-623], x[p-227] are all older than W + 128 - 163, so they are known a whole
-// window ahead), and the new raw word is the new `wx` itself — no HBM traffic and no
-// memory wait on the chain.  Invariant: words [W - 832, W + 192) are in the ring.
+// The fused search (c4_search_kernel) keeps its game's stream in LDS instead of the HBM ring,
+// in two rings per wave: the RAW ring (1024 words), which the recurrence and the hand-over
+// need, and beside it the DRAW ring, one byte per word holding temper(x) >> 29.  Every
+// consumer of the stream in this search reads only the top k <= 3 bits of a tempered word
+// (_randbelow(n) with n <= 7), so a 64-word view from ANY position is one byte read per lane
+// (rng_view): no windows in registers, no lane permute, no window select.
+// Positions are kept relative to org = use0 & ~3 (use0 = the stream's position at the launch's
+// start): word org + q sits at slot q % 1024 of both rings, and the draw ring's first 64 bytes
+// are repeated after its end, so a view reads the bytes (q % 1024) + lane without a wrap.
+// The recurrence runs in bulk (lrng_refill): 224 words a step, lane l < 56 producing the four
+// words G + 4l .. G + 4l + 3 and their four draws, whenever fewer than 64 generated words lie
+// ahead of the next unconsumed one.
+//   * 224 <= 227: every input of a step (x[p-624], x[p-623], x[p-227]) is older than every
+//     output, so a step loads, computes, stores.  (256 would read x[p-227] inside itself; two
+//     dependent half-steps would pay the step's fixed costs twice.)
+//   * G - org is a multiple of 4 (lrng_open makes it one), and so are 624 and 228: each lane's
+//     four inputs x[p-624 ..] are one aligned quad, x[p-227 ..] the last three words of one,
+//     and a quad never straddles the ring's wrap.
+//   * the stream runs at most 63 + 224 = 287 words ahead of the next word U, so the ring
+//     [G - 1024, G) always holds the 624-word block of word U-1 (it starts at >= U - 624 >=
+//     G - 911), which lrng_close hands over, and the draws of [U, U + 64).
+//   * words < 624 are never produced by the recurrence (they are seeded): a stream's
+//     generated mark is >= 624 from the start (zc_rng_seed / zc_rng_set_state), the refill
+//     starts there, and the words already in the ring are kept — only their draws are made.
 // The HBM ring is the hand-over format to every other kernel and to zc_rng_get_state: the
 // kernel loads its game's last 1024 words at the start and, at the end, writes back the
 // words [min(U & ~63, block start, G' - 624), G') (U = next word, block = the 624-word block
@@ -285,40 +317,94 @@ __device__ __forceinline__ void rng_close(const Rng &r, uint64_t use0, uint64_t 
 constexpr int kLRingWords = 1024;
 constexpr uint32_t kLRingMask = kLRingWords - 1;
 constexpr int kLRingBytes = kLRingWords * 4;
+constexpr int kLDrawBytes = kLRingWords + kWin;  // the draw ring: one byte per word, the first 64 again
+constexpr int kLStepLanes = 56;                  // lanes of a refill step, four words each
+constexpr int kLStep = 4 * kLStepLanes;          // words per refill step
+static_assert(kLStep <= 227 && kLStep % 4 == 0, "a refill step's inputs must all be older than its outputs");
+static_assert(kLRingWords - 624 - (kWin - 1 + kLStep) >= 0, "the block of word U-1 must stay in the ring");
+
+// The top three bits of the tempered word, temper(x) >> 29, from the raw word: temper's last
+// step (y ^= y >> 18) cannot reach them, its third reaches them through bits 16..14 (the mask
+// 0xefc60000 has all of 31..29 set), and of its second step only bits 31 and 14 matter (the
+// mask 0x9d2c5680 at 31, 30, 29, 16, 15, 14 is 1, 0, 0, 0, 0, 1).
+__host__ __device__ constexpr uint32_t mt_draw3(uint32_t x) {
+    const uint32_t y = x ^ (x >> 11);
+    const uint32_t z = y ^ ((y << 7) & 0x80004000u);
+    return (z ^ (z << 15)) >> 29;
+}
+__host__ __device__ constexpr uint32_t mt_temper_ref(uint32_t y) {
+    y ^= y >> 11;
+    y ^= (y << 7) & 0x9d2c5680u;
+    y ^= (y << 15) & 0xefc60000u;
+    y ^= y >> 18;
+    return y;
+}
+// both are GF(2)-linear in x: equal on zero and on the 32 one-bit words, equal on every word
+__host__ __device__ constexpr bool mt_draw3_matches_temper() {
+    if (mt_draw3(0u) != mt_temper_ref(0u) >> 29) return false;
+    for (int b = 0; b < 32; ++b)
+        if (mt_draw3(1u << b) != mt_temper_ref(1u << b) >> 29) return false;
+    return true;
+}
+static_assert(mt_draw3_matches_temper(), "mt_draw3 is not temper(x) >> 29");
 
 struct LRng {
-    uint32_t *lds;   // this wave's ring: raw x[p] at slot p % 1024
-    uint32_t base;   // low 32 bits of the absolute position at the search's start (use0)
-    int32_t wrel;    // window start - use0
-    uint32_t off;    // next word to consume = window start + off, off in [0, 128)
-    int32_t hrel;    // words [.., use0 + hrel) were in the ring at the start (hrel >= 192 - off)
-    // the two tempered windows stay in their registers: wa/wb hold x[W + lane] and
-    // x[W + 64 + lane] when ph == 0, the other way round when ph is all ones (an advance
-    // overwrites the older one in place and flips ph: no register rotation, so no loop-carried
-    // copies).  ph is a wave mask, so that it selects between the two as it stands
-    uint32_t wa, wb;
-    uint64_t ph;
-    __device__ __forceinline__ uint32_t cur() const { return mask_sel(ph, wa, wb); }  // tempered x[W + lane]
-    uint32_t wx;     // raw x[W + 128 + lane]
-    uint32_t ia, ib, im;  // raw x[p-624], x[p-623], x[p-227] for p = W + 192 + lane (the next step)
-    __device__ __forceinline__ int32_t use() const { return wrel + (int32_t)off; }
-    __device__ __forceinline__ uint32_t slot(int32_t rel) const { return (base + (uint32_t)rel) & kLRingMask; }
+    uint32_t *lds;      // this wave's rings: kLRingWords raw words, then kLDrawBytes of draws
+    const uint8_t *dl;  // the draw ring + this lane: a view reads dl[(next word - org) % 1024]
+    int32_t urel;       // next word to consume - org
+    int32_t lim;        // words generated - org - 64: a view needs urel <= lim
+    int32_t uoff;       // use0 - org (0..3)
+    __device__ __forceinline__ int32_t use() const { return urel - uoff; }  // words consumed since use0
+    __device__ __forceinline__ int32_t grel() const { return lim + kWin; }
+    __device__ __forceinline__ uint8_t *draw() const { return (uint8_t *)(lds + kLRingWords); }
 };
 
+// (the bit select as one v_bfi_b32, which the compiler otherwise splits into two ANDs and an OR
+// once it has merged the shift into them, and the conditional constant as a sign-extended bit
+// ANDed with it instead of a compare and a select)
 __device__ __forceinline__ uint32_t mt_twist(uint32_t a, uint32_t b, uint32_t m) {
-    const uint32_t y = (a & 0x80000000u) | (b & 0x7fffffffu);
-    return m ^ (y >> 1) ^ ((b & 1u) ? 0x9908b0dfu : 0u);
+    uint32_t y;
+    __asm__("v_bfi_b32 %0, %1, %2, %3" : "=v"(y) : "s"(0x7fffffffu), "v"(b), "v"(a));
+    const uint32_t mag = (uint32_t)((int32_t)(b << 31) >> 31) & 0x9908b0dfu;
+    return m ^ (y >> 1) ^ mag;
 }
 
-__device__ __forceinline__ void lrng_prefetch(LRng &r) {
-    const int32_t p = r.wrel + 192 + (int32_t)lane_id();
-    r.ia = r.lds[r.slot(p - 624)];
-    r.ib = r.lds[r.slot(p - 623)];
-    r.im = r.lds[r.slot(p - 227)];
+// the draws of the four words at slot q (a multiple of 4), a byte each; the first 64 repeated
+__device__ __forceinline__ void lrng_put_draws(const LRng &r, uint32_t q, uint32_t x0, uint32_t x1, uint32_t x2,
+                                               uint32_t x3) {
+    const uint32_t d = mt_draw3(x0) | (mt_draw3(x1) << 8) | (mt_draw3(x2) << 16) | (mt_draw3(x3) << 24);
+    *(uint32_t *)(r.draw() + q) = d;
+    if (q < (uint32_t)kWin) *(uint32_t *)(r.draw() + kLRingWords + q) = d;
 }
 
-// Generate absolute words [g, end) in the ring, 64 at a time (every input is >= 227 older).
-__device__ __forceinline__ void lrng_generate_abs(uint32_t *lds, uint64_t g, uint64_t end) {
+// One refill step: the words [G, G + 224) and their draws, G = org + grel().  Lane l's words
+// are p .. p+3 with p = grel() + 4l: x[p+j-624] and x[p+j-623] come from the quad at p - 624
+// and the word after it, x[p+j-227] from the last three words of the quad at p - 228 and the
+// word after it.  (Word by word, which the compiler pairs up: this toolchain's register
+// allocator crashes on the 16-byte form of these accesses under the ILP scheduler.)
+__device__ __forceinline__ void lrng_refill(LRng &r) {
+    const uint32_t lane = lane_id();
+    const uint32_t p = (uint32_t)r.grel() + 4u * lane;
+    const uint32_t *pa = r.lds + ((p - 624u) & kLRingMask), *pm = r.lds + ((p - 228u) & kLRingMask);
+    const uint32_t a0 = pa[0], a1 = pa[1], a2 = pa[2], a3 = pa[3], a4 = r.lds[(p - 620u) & kLRingMask];
+    const uint32_t m1 = pm[1], m2 = pm[2], m3 = pm[3], m4 = r.lds[(p - 224u) & kLRingMask];
+    const uint32_t x0 = mt_twist(a0, a1, m1), x1 = mt_twist(a1, a2, m2), x2 = mt_twist(a2, a3, m3),
+                   x3 = mt_twist(a3, a4, m4);
+    if (lane < (uint32_t)kLStepLanes) {  // the lanes past the step read words not yet generated
+        uint32_t *px = r.lds + (p & kLRingMask);
+        px[0] = x0;
+        px[1] = x1;
+        px[2] = x2;
+        px[3] = x3;
+        lrng_put_draws(r, p & kLRingMask, x0, x1, x2, x3);
+    }
+    r.lim += kLStep;
+    wave_mem_order();
+}
+
+// Generate the words [g, end) in the ring (positions relative to org), 64 at a time (every
+// input is >= 227 older); raw words only.
+__device__ __forceinline__ void lrng_generate(uint32_t *lds, int64_t g, int64_t end) {
     const uint32_t lane = lane_id();
     for (; g < end; g += 64) {
         const uint32_t p = (uint32_t)g + lane;
@@ -331,85 +417,100 @@ __device__ __forceinline__ void lrng_generate_abs(uint32_t *lds, uint64_t g, uin
 
 // use0 / gen0: absolute positions (words consumed / generated) from the game's rngpos.
 // Words already generated (and the seeded block 0..623, which no recurrence produces) are
-// kept: an advance inside them re-reads the ring instead of generating (hrel).
+// kept: the refill starts at the generated mark, and the draws of the loaded words are made here.
+// lds: kLRingBytes + kLDrawBytes of this wave's LDS, 16-byte aligned.
 __device__ __forceinline__ void lrng_open(LRng &r, uint32_t *lds, const uint32_t *ring, uint64_t use0, uint64_t gen0) {
     const uint32_t lane = lane_id();
+    const uint64_t org = use0 & ~(uint64_t)3;
     r.lds = lds;
-    r.base = (uint32_t)use0;
-    r.off = (uint32_t)use0 & (uint32_t)(kWin - 1);
-    r.wrel = -(int32_t)r.off;
-    const uint64_t w0 = use0 - r.off, target = w0 + 192;
+    r.dl = r.draw() + lane;
+    r.uoff = (int32_t)(use0 - org);
+    r.urel = r.uoff;
+    const uint64_t w0 = use0 & ~(uint64_t)(kWin - 1), target = w0 + 192;
     // the ring can take every word up to gen0 when gen0 - w0 <= 960 (always after this
-    // kernel's own close: <= 879); an HBM kernel's lookahead may go further, and then its
+    // kernel's own close: <= 686); an HBM kernel's lookahead may go further, and then its
     // ring is valid throughout, so the words past the first window are generated again
-    const uint64_t g = gen0 <= w0 + 960 ? gen0 : (target < 624 ? 624 : target);
+    uint64_t g = gen0 <= w0 + 960 ? gen0 : (target < 624 ? 624 : target);
     for (uint32_t i = lane; i < (uint32_t)kLRingWords; i += 64) {
         const uint32_t p = (uint32_t)g - (uint32_t)kLRingWords + i;
-        lds[p & kLRingMask] = ring[p & kRingMask];
+        lds[(p - (uint32_t)org) & kLRingMask] = ring[p & kRingMask];
     }
     wave_mem_order();
-    lrng_generate_abs(lds, g, target);
-    r.hrel = (int32_t)(g - use0);
-    r.wa = temper(lds[r.slot(r.wrel + (int32_t)lane)]);
-    r.wb = temper(lds[r.slot(r.wrel + kWin + (int32_t)lane)]);
-    r.ph = 0;
-    r.wx = lds[r.slot(r.wrel + 2 * kWin + (int32_t)lane)];
-    lrng_prefetch(r);
-}
-
-// rng_view for the LDS stream: source lane s gives the second window when s < off, the
-// first otherwise, and which of wa / wb that is flips with ph
-__device__ __forceinline__ uint32_t rng_view(const LRng &r) {
-    const uint32_t lane = lane_id();
-    const uint32_t src = mask_sel(__ballot(lane < r.off) ^ r.ph, r.wa, r.wb);
-    return (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane + r.off) << 2), (int)src);
-}
-
-// Move the windows on by 64 words (precondition: off >= 64); one recurrence step.
-__device__ __forceinline__ void rng_advance(LRng &r) {
-    r.wrel += kWin;
-    r.off -= (uint32_t)kWin;
-    const uint32_t t = temper(r.wx);  // the new second window replaces the old first one
-    const uint32_t na = mask_sel(r.ph, t, r.wa), nb = mask_sel(r.ph, r.wb, t);
-    r.wa = na;
-    r.wb = nb;
-    r.ph = ~r.ph;
-    const int32_t p = r.wrel + 128 + (int32_t)lane_id();
-    uint32_t x = mt_twist(r.ia, r.ib, r.im);
-    if (r.wrel + 128 < r.hrel) {  // only inside the seeded block: words already in the ring
-        const uint32_t old = r.lds[r.slot(p)];
-        x = p < r.hrel ? old : x;
+    // the first view's words, and a generated mark that is a multiple of 4 for the refill (every
+    // writer of rngpos leaves one: 624, an HBM chunk of 192, a window of 64 or a refill step;
+    // not assumed)
+    if (g < use0 + kWin || (g & 3u)) {
+        const uint64_t ge = ((g < use0 + kWin ? use0 + kWin : g) + 3u) & ~(uint64_t)3u;
+        lrng_generate(lds, (int64_t)(g - org), (int64_t)(ge - org));
+        g = ge;
     }
-    r.lds[r.slot(p)] = x;
-    r.wx = x;
-    lrng_prefetch(r);
+    // the draws of all 1024 words in the ring, four per lane and pass ([use0, g) is what the views read)
+    for (uint32_t q = 4u * lane; q < (uint32_t)kLRingWords; q += 256u)
+        lrng_put_draws(r, q, lds[q], lds[q + 1], lds[q + 2], lds[q + 3]);
+    wave_mem_order();
+    r.lim = (int32_t)(int64_t)(g - org) - kWin;
 }
+
+// The next 64 words' draws, lane l = temper(word next + l) >> 29: one byte read per lane at a
+// uniform offset (precondition: urel <= lim, what rng_need establishes).
+__device__ __forceinline__ uint32_t rng_view(const LRng &r) { return r.dl[(uint32_t)r.urel & kLRingMask]; }
 
 // Consume w words without reading them (the walk-replay diagnostic: a flush's recorded
-// rollout words), window by window.
+// rollout words), then refill until a view can be taken again.
 __device__ __forceinline__ void lrng_skip(LRng &r, uint32_t w) {
-    r.off += w;
-    while (r.off >= (uint32_t)kWin) rng_advance(r);
+    r.urel += (int32_t)w;
+    while (r.urel > r.lim) lrng_refill(r);
+}
+
+// What the code shared by the two streams (select_flush, c4_rollouts) asks of either:
+//   rng_need(r)       make a view available (at most 64 words were consumed since the last call)
+//   rng_view(r)       lane l: word `next + l`, as its top ViewBits<R>::kBits tempered bits
+//   rng_eat(r, w)     consume w <= 64 words of the view
+//   draw_shift<R>(n)  a view value >> this = getrandbits(n.bit_length()); n >= 1 (n <= 7 for the LDS stream)
+__device__ __forceinline__ void rng_need(Rng &r) {
+    if (r.off >= (uint32_t)kWin) rng_advance(r);
+}
+__device__ __forceinline__ void rng_need(LRng &r) {
+    if (r.urel > r.lim) lrng_refill(r);
+}
+__device__ __forceinline__ void rng_eat(Rng &r, uint32_t w) { r.off += w; }
+__device__ __forceinline__ void rng_eat(LRng &r, uint32_t w) { r.urel += (int32_t)w; }
+template <class R>
+struct ViewBits {
+    static constexpr uint32_t kBits = 32;  // whole tempered words
+};
+template <>
+struct ViewBits<LRng> {
+    static constexpr uint32_t kBits = 3;  // the draw ring's bytes
+};
+template <class R>
+__device__ __forceinline__ uint32_t draw_shift(uint32_t n) {
+    return (uint32_t)__builtin_clz(n) - (32u - ViewBits<R>::kBits);
 }
 
 // Write the stream back to the game's HBM ring and rngpos (see above).
 __device__ __forceinline__ void lrng_close(const LRng &r, uint32_t *ring, uint64_t use0, uint64_t *rngpos) {
     const uint32_t lane = lane_id();
-    const uint64_t U = use0 + (uint64_t)(int64_t)r.use();
-    uint64_t G = use0 + (uint64_t)(int64_t)max(r.wrel + 192, r.hrel);
+    const uint64_t org = use0 & ~(uint64_t)3;
+    const uint64_t U = org + (uint64_t)(int64_t)r.urel;
+    uint64_t G = org + (uint64_t)(int64_t)r.grel();
     const uint64_t blk = U ? (U - 1) / 624 : 0;
     const uint64_t bend = (blk + 1) * 624;
     wave_mem_order();
     if (G < bend) {
-        lrng_generate_abs(r.lds, G, bend);
+        lrng_generate(r.lds, (int64_t)(G - org), (int64_t)(bend - org));
         G = bend;
     }
     // what rng_open reads (the window of U), what zc_rng_get_state reads (U-1's block) and
-    // what the recurrence reads next (the last 624 words); at most 815 words
+    // what the recurrence reads next (the last 624 words).  All of it is in the ring [G - 1024,
+    // G): G = the block's end gives at most 623 + 63 words; a G past it was left by a refill
+    // (G <= U + 287) or loaded at the start from an HBM kernel (rng_fill: G < U + 384), and the
+    // start is >= U - 624: at most 911 (1007) words
     const uint64_t wu = U & ~(uint64_t)(kWin - 1);
     uint64_t start = wu < blk * 624 ? wu : blk * 624;
     start = start < G - 624 ? start : G - 624;
-    for (uint64_t q = start + lane; q < G; q += 64) ring[(uint32_t)q & kRingMask] = r.lds[(uint32_t)q & kLRingMask];
+    for (uint64_t q = start + lane; q < G; q += 64)
+        ring[(uint32_t)q & kRingMask] = r.lds[((uint32_t)q - (uint32_t)org) & kLRingMask];
     if (lane == 0) {
         rngpos[0] = U;
         rngpos[1] = G;
@@ -752,8 +853,8 @@ __device__ __forceinline__ void select_flush(const Tree &t, Fresh *fresh, Leaf *
         {
             int done = 0;
             for (;;) {  // one 64-word view per pass
-                if (rng.off >= (uint32_t)kWin) rng_advance(rng);
-                const uint32_t w = rng_view(rng);  // lane l: word off + l
+                rng_need(rng);
+                const uint32_t w = rng_view(rng);  // lane l: the next unconsumed word + l
                 const int rem = m - done;
                 // acceptance masks of the next (up to 7) draws, n = cnt - done - i: independent
                 // of each other, issued back to back
@@ -761,7 +862,7 @@ __device__ __forceinline__ void select_flush(const Tree &t, Fresh *fresh, Leaf *
 #pragma unroll
                 for (int i = 0; i < 7; ++i) {
                     const uint32_t n = (uint32_t)max((int)cnt - done - i, 1);
-                    A[i] = __ballot((w >> __clz(n)) < n);
+                    A[i] = __ballot((w >> draw_shift<RNG>(n)) < n);
                 }
                 // the draws, a branch-free scalar chain: each takes the lowest accepted word
                 // after the last one (lb = acc & -acc); a draw without one zeroes `gt`, and with
@@ -780,15 +881,15 @@ __device__ __forceinline__ void select_flush(const Tree &t, Fresh *fresh, Leaf *
                 // its value goes to lane di (a forward permute; lanes outside [done, done + nd)
                 // keep theirs)
                 const uint32_t di = (uint32_t)done + mbcnt64(F);
-                const uint32_t rl = w >> __clz(max((int)cnt - (int)di, 1));
+                const uint32_t rl = w >> draw_shift<RNG>((uint32_t)max((int)cnt - (int)di, 1));
                 const uint32_t got = (uint32_t)__builtin_amdgcn_ds_permute((int)(mask_sel(F, 63u, di) << 2), (int)rl);
                 rr = mask_sel(((1ull << nd) - 1ull) << done, rr, got);  // lanes done .. done + nd - 1
                 done += nd;
                 if (done < m) {  // the view ran out: all of it is consumed
-                    rng.off += (uint32_t)kWin;
+                    rng_eat(rng, (uint32_t)kWin);
                     continue;
                 }
-                rng.off += (uint32_t)f + 1u;
+                rng_eat(rng, (uint32_t)f + 1u);
                 break;
             }
         }

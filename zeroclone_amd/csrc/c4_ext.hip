@@ -397,7 +397,9 @@ void launch_c4_ext_begin(const ExtParams &p, hipStream_t s) {
 }
 
 void launch_c4_ext_select(const ExtParams &p, hipStream_t s) {
-    hipLaunchKernelGGL(c4_ext_select_kernel, dim3(p.n_games), dim3(kBlock), c4_search_lds_bytes(p.bs), s, p);
+    // the tables, then per leaf a fresh node, a leaf record and a path (the last path's spill after them)
+    const size_t lds = kTabBytes + (sizeof(Fresh) + sizeof(Leaf) + sizeof(uint16_t) * kMaxDepth) * (size_t)p.bs + kPathSpill;
+    hipLaunchKernelGGL(c4_ext_select_kernel, dim3(p.n_games), dim3(kBlock), lds, s, p);
 }
 
 void launch_c4_ext_backup(const ExtParams &p, hipStream_t s) {

@@ -96,7 +96,10 @@ __device__ __forceinline__ uint32_t ff1(uint64_t m) {
 // Plies are simulated a BLOCK at a time over a 64-word view of the stream that starts at the
 // next unconsumed word (rng_view).  While the legal set is unchanged, the draws are exactly
 // the view words w with (w >> (32-k)) < n, in stream order — so one ballot yields the moves
-// of every ply the view covers.  Lane k (an accepted word) is ply q_k = #accepted lanes below
+// of every ply the view covers.  (k <= 3: the test and the move index need only the word's top
+// three tempered bits t, which is all the LDS stream keeps; with the legal set's draw_order
+// word, t < threshold is the test and bits 3t.. the column, no shift by 3 - k in between.)
+// Lane k (an accepted word) is ply q_k = #accepted lanes below
 // it; its column comes from the move order, its row from the column height plus #earlier
 // accepted lanes in the same column (packed 4-bit per-column prefix sums).
 //
@@ -152,6 +155,11 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
     uint64_t t_ = ZC_RSTAMP && sub ? __builtin_amdgcn_s_memtime() : 0;
     const uint32_t lane = lane_id();
     const uint32_t lrow = lane >> 4;
+    // a view's value >> kTop3 = the word's top three tempered bits t; the legal sets' order words
+    // come from the draw_order table (load_tables), which t indexes as it stands: `thr` below
+    // is a set's acceptance threshold for t, bits 3t.. of its word the accepted t's column
+    constexpr uint32_t kTop3 = ViewBits<R>::kBits - 3u;
+    const uint32_t *const s_dorder = draw_order_table(s_order);
     // rows 1, 3 test the block's second mover (rows 0, 2 its first), as a wave mask: XORed with
     // the side to move it says which lanes take p1 for their stones (`S1` below)
     const uint64_t second_rows = __ballot((lrow & 1u) != 0);
@@ -175,7 +183,7 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
         const int jj = g + (int)lane;
         if (jj < nb) {
             lm_v = L[jj].meta;
-            ow_v = L[jj].ow;
+            ow_v = s_dorder[lm_v >> 25];
             const uint64_t x0 = L[jj].p0, x1 = L[jj].p1;
             const uint64_t op_v = (lm_v >> 24) & 1u ? x0 : x1;
             room_v = has_four(op_v) ? -2 : 41 - __popcll(x0 | x1);
@@ -209,11 +217,10 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
             int room = room0;
             int mask = (int)(lm >> 25);
             uint32_t ow = low0;
-            uint32_t n = (ow >> 24) & 15u;
-            uint32_t sh = (uint32_t)__builtin_clz(n);  // n >= 1 (room >= 0)
+            uint32_t thr = (ow >> 24) & 15u;
             // order words of the legal set minus the columns of `pairbits`, for the fills
             // (read as soon as the legal set is known, well before a fill needs it)
-            uint32_t owp = s_order[(uint32_t)mask & ~pairbits];
+            uint32_t owp = s_dorder[(uint32_t)mask & ~pairbits];
             // One block of plies.  What it leaves for the steps after it: ew, the block's first
             // winning lane (0xFFFFFFFF: none), and l0, its last lane otherwise; the lane and ply it
             // ended at; every lane's column, the prefix sums of the plies per column, the fills,
@@ -224,27 +231,25 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
             uint64_t F, mine;
             auto block = [&]() __attribute__((always_inline)) {
                 RMARK(6);
-                uint32_t wv, v;
+                uint32_t wv;
                 uint64_t A;  // accepted words
                 // a view without an accepted word (2^-64 at worst) is consumed whole, in a loop
                 // of its own off the common path (no loop-carried copies of the stream position)
-                if (rng.off >= (uint32_t)kWin) rng_advance(rng);
-                wv = rng_view(rng);  // lane l: word off + l
-                v = wv >> sh;
-                A = __ballot(v < n);
+                rng_need(rng);
+                wv = rng_view(rng) >> kTop3;  // lane l: the next unconsumed word + l
+                A = __ballot(wv < thr);
                 if (__builtin_expect(A == 0ull, 0)) {
                     do {
-                        rng.off += (uint32_t)kWin;
-                        rng_advance(rng);
-                        wv = rng_view(rng);
-                        v = wv >> sh;
-                        A = __ballot(v < n);
+                        rng_eat(rng, (uint32_t)kWin);
+                        rng_need(rng);
+                        wv = rng_view(rng) >> kTop3;
+                        A = __ballot(wv < thr);
                     } while (A == 0ull);
                 }
                 RMARK(2);
                 const uint32_t cap_r = min((uint32_t)room, 30u);  // last ply index the board allows
                 uint32_t qk = mbcnt(A);                            // this lane's ply in the block
-                col = (ow >> (3 * v)) & 7u;  // its column (if accepted; v < 8 as n < 8)
+                col = (ow >> (3 * wv)) & 7u;  // its column (if accepted)
                 // the ply's row: the column's height (hp, 4 bits per column, carried from block
                 // to block) + earlier plies in the same column (4-bit per-column counters,
                 // prefix-summed).  A nibble only overflows into the next column's after its own
@@ -277,12 +282,11 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
                 if (lf == l0) {  // a fill with room for more plies
                     const uint32_t cf = (uint32_t)__builtin_amdgcn_readlane((int)col, (int)lf);
                     const uint32_t ow2 = (uint32_t)__builtin_amdgcn_readlane((int)owp, (int)(8u * cf));
-                    const uint32_t n2 = (ow2 >> 24) & 15u;
-                    const uint32_t v2 = wv >> __clz(n2);
+                    const uint32_t thr2 = (ow2 >> 24) & 15u;
                     const uint64_t high = ~1ull << lf;  // the lanes after lf
-                    A = (A & ~high) | (__ballot(v2 < n2) & high);
+                    A = (A & ~high) | (__ballot(wv < thr2) & high);
                     qk = mbcnt(A);
-                    col = mask_sel(high, col, (ow2 >> (3 * v2)) & 7u);  // lanes after lf: the new order
+                    col = mask_sel(high, col, (ow2 >> (3 * wv)) & 7u);  // lanes after lf: the new order
                     one = mask_sel0(A, 1u << (4 * col));
                     sc = scan_add32(one);
                     row = ((sc - one + hp) >> (4 * col)) & 15u;
@@ -353,13 +357,12 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
                 if (lf == l0) {  // a fill with room for more plies
                     const uint32_t cf = (uint32_t)__builtin_amdgcn_readlane((int)col, (int)lf);
                     const uint32_t ow2 = (uint32_t)__builtin_amdgcn_readlane((int)owp, (int)(8u * cf));
-                    const uint32_t n2 = (ow2 >> 24) & 15u;
-                    const uint32_t v2 = wv >> __clz(n2);
+                    const uint32_t thr2 = (ow2 >> 24) & 15u;
                     const uint64_t high = ~1ull << lf;  // the lanes after lf
                     if (ZC_RV & 1) Ew1 = win_test(A, qk, col, row, mine1) & ~high;
-                    A = (A & ~high) | (__ballot(v2 < n2) & high);
+                    A = (A & ~high) | (__ballot(wv < thr2) & high);
                     qk = mbcnt(A);
-                    col = mask_sel(high, col, (ow2 >> (3 * v2)) & 7u);  // lanes after lf: the new order
+                    col = mask_sel(high, col, (ow2 >> (3 * wv)) & 7u);  // lanes after lf: the new order
                     one = mask_sel0(A, 1u << (4 * col));
                     sc = scan_add32(one);
                     row = ((sc - one + hp) >> (4 * col)) & 15u;
@@ -383,7 +386,7 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
                 ew = ff1(Ew);
                 endlane = min(ew, l0);
                 endply = (uint32_t)__builtin_amdgcn_readlane((int)qk, (int)endlane);
-                rng.off += endlane + 1u;  // words through the block's last ply are consumed
+                rng_eat(rng, endlane + 1u);  // words through the block's last ply are consumed
 #ifdef ZC_DIAG_WASTE
                 cn.add(cn.blocks, lf == l0f && endlane < lf ? 1 : 0);
                 cn.add(cn.plies, lf == l0f ? 1 : 0);
@@ -422,10 +425,9 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
                     mask = ff ? mask & ~((1 << ca) | (1 << ce)) : mask;
                     const uint32_t ownew = (uint32_t)__builtin_amdgcn_readlane((int)owp, (int)((7u * ca + ce) & 63u));
                     ow = ff ? ownew : ow;
-                    owp = s_order[(uint32_t)mask & ~pairbits];
+                    owp = s_dorder[(uint32_t)mask & ~pairbits];
                 }
-                n = (ow >> 24) & 15u;
-                sh = (uint32_t)__builtin_clz(n);
+                thr = (ow >> 24) & 15u;
             };
             // Most rollouts end in their first block, so that one stands alone, in line, and only
             // the others enter the loop: every branch the compiler emits is structured, and a
@@ -663,9 +665,9 @@ __device__ __forceinline__ void select_flush_plan(const Tree &t, Fresh *fresh, L
     int d = 0, i = 0, T = -1;  // draws so far, chain node, the terminal chain node (full board)
     uint64_t Sm = 0;           // bit s: a chain node's first draw
     uint32_t raw = 0;          // lane d: the accepted word of draw d
-    if (rng.off >= (uint32_t)kWin) rng_advance(rng);
-    uint32_t w = rng_view(rng);  // lane l: word off + l
-    uint32_t t3 = w >> 29;
+    rng_need(rng);
+    uint32_t w = rng_view(rng);  // lane l: the next unconsumed word + l
+    uint32_t t3 = w >> (ViewBits<RNG>::kBits - 3u);
     uint64_t gt = ~0ull, Fv = 0;  // the view: lanes after the last accepted word; accepted words
     int dv0 = 0;                  // first draw of the view
     for (;;) {
@@ -709,10 +711,10 @@ __device__ __forceinline__ void select_flush_plan(const Tree &t, Fresh *fresh, L
                 const uint32_t got =
                     (uint32_t)__builtin_amdgcn_ds_permute((int)(mask_sel(Fv, 63u, di) << 2), (int)w);
                 raw = mask_sel(lanes_in(dv0, d), raw, got);
-                rng.off += (uint32_t)kWin;
-                rng_advance(rng);
+                rng_eat(rng, (uint32_t)kWin);
+                rng_need(rng);
                 w = rng_view(rng);
-                t3 = w >> 29;
+                t3 = w >> (ViewBits<RNG>::kBits - 3u);
                 gt = ~0ull;
                 Fv = 0;
                 dv0 = d;
@@ -742,7 +744,7 @@ __device__ __forceinline__ void select_flush_plan(const Tree &t, Fresh *fresh, L
         const uint32_t di = (uint32_t)dv0 + mbcnt64(Fv);
         const uint32_t got = (uint32_t)__builtin_amdgcn_ds_permute((int)(mask_sel(Fv, 63u, di) << 2), (int)w);
         raw = mask_sel(lanes_in(dv0, d), raw, got);
-        rng.off += (uint32_t)(63 - __clzll(Fv | 1ull)) + 1u;
+        rng_eat(rng, (uint32_t)(63 - __clzll(Fv | 1ull)) + 1u);
     }
     const int D = d;  // fresh nodes f0 .. f0 + D - 1
     wave_mem_order();
@@ -754,7 +756,7 @@ __device__ __forceinline__ void select_flush_plan(const Tree &t, Fresh *fresh, L
     const ChainNode e = chain[seg];
     const uint32_t s_i = (e.info >> 8) & 0xFFu;
     const uint32_t dd = lane - s_i;  // the draw's index inside its node
-    const uint32_t r = raw >> __clz(act ? (e.info & 15u) - dd : 1u);
+    const uint32_t r = raw >> draw_shift<RNG>(act ? (e.info & 15u) - dd : 1u);
     // draw dd's position in the node's untried list as it was before the node's draws
     // (select_flush's Lehmer decode, each lane against its own node's earlier draws)
     uint32_t rp[6];
@@ -846,10 +848,10 @@ __device__ __forceinline__ uint32_t draw_class_bfe(uint32_t cnt) {  // c = T(cnt
     return (6u << 16) | (((0xE480u >> (2u * cnt)) & 3u) << 3);
 }
 
-// The view's next-draw table (1b).
-__device__ __forceinline__ uint32_t draw_table(uint32_t w) {
+// The view's next-draw table (1b); w3 = the view's words as their top three tempered bits.
+__device__ __forceinline__ uint32_t draw_table(uint32_t w3) {
     const uint32_t lane = lane_id();
-    const uint32_t t3 = lane < 62u ? (w >> 29) : 7u;
+    const uint32_t t3 = lane < 62u ? w3 : 7u;
     uint32_t nx = 0;
 #pragma unroll
     for (uint32_t c = 0; c < 4; ++c) {
@@ -976,9 +978,9 @@ __device__ __forceinline__ void select_flush_plan2(const Tree &t, Fresh *fresh, 
     // ---- (1b, 1c) the draws: raw (lane d: the accepted word of draw d)
     uint32_t raw = 0;
     {
-        if (rng.off >= (uint32_t)kWin) rng_advance(rng);
+        rng_need(rng);
         uint32_t w = rng_view(rng);
-        uint32_t nx = draw_table(w);
+        uint32_t nx = draw_table(w >> (ViewBits<RNG>::kBits - 3u));
         int V = 0;  // draws done
         uint64_t F = draw_chase_fixed<32>(nx, clsv);
         for (;;) {
@@ -994,22 +996,22 @@ __device__ __forceinline__ void select_flush_plan2(const Tree &t, Fresh *fresh, 
             V += take;
             if (nv >= need) {  // done: the stream goes on after draw D-1's word
                 const uint64_t lastw = __ballot(((G >> lane) & 1ull) && (int)rank == take - 1);
-                rng.off += (uint32_t)__builtin_ctzll(lastw) + 1u;
+                rng_eat(rng, (uint32_t)__builtin_ctzll(lastw) + 1u);
                 break;
             }
             uint32_t q;
             if (F >> 63) {  // ran out: the failed draw rejected words q..61 and goes on at word 62
-                rng.off += 62u;
-                if (rng.off >= (uint32_t)kWin) rng_advance(rng);
+                rng_eat(rng, 62u);
+                rng_need(rng);
                 w = rng_view(rng);
-                nx = draw_table(w);
+                nx = draw_table(w >> (ViewBits<RNG>::kBits - 3u));
                 q = 0;
             } else {  // (nb > 32) the fixed chase ended with the view left: go on in it
                 q = nv ? 64u - (uint32_t)__clzll(G) : 0u;
-                rng.off += q;
-                if (rng.off >= (uint32_t)kWin) rng_advance(rng);
+                rng_eat(rng, q);
+                rng_need(rng);
                 w = rng_view(rng);
-                nx = draw_table(w);
+                nx = draw_table(w >> (ViewBits<RNG>::kBits - 3u));
                 q = 0;
             }
             // the rest of the draws from V, one at a time, in this view
@@ -1030,7 +1032,7 @@ __device__ __forceinline__ void select_flush_plan2(const Tree &t, Fresh *fresh, 
                           (uint32_t)__builtin_amdgcn_ds_bpermute(sa, v_b0l);
     const uint64_t e_p1 = ((uint64_t)(uint32_t)__builtin_amdgcn_ds_bpermute(sa, v_b1h) << 32) |
                           (uint32_t)__builtin_amdgcn_ds_bpermute(sa, v_b1l);
-    const uint32_t r = raw >> __clz(cnt);
+    const uint32_t r = raw >> draw_shift<RNG>(cnt);
     // draw dd's position in the node's untried list as it was before the node's draws
     // (select_flush's Lehmer decode, each lane against its own node's earlier draws)
     uint32_t rp[6];
@@ -1108,18 +1110,26 @@ __device__ __forceinline__ void select_flush_plan2(const Tree &t, Fresh *fresh, 
 
 // ------------------------------------------------------------------ the search kernel
 constexpr int kSearchWaves = 4;  // games (waves) per workgroup
+// The rollout search records no leaf paths (select_flush gets nullptr), so its per-wave block
+// has no path area: after the leaves comes only the chain table of select_flush_plan (A/B
+// builds with ZC_PLAN2=0), one entry per chain node — at most a node per leaf and a terminal one.
 __host__ __device__ constexpr size_t c4_search_wave_lds(int bs) {
-    return ((size_t)kLRingBytes + (sizeof(Leaf) + sizeof(Fresh) + sizeof(uint16_t) * kMaxDepth) * (size_t)bs +
-            kPathSpill + 15) & ~(size_t)15;
+    return ((size_t)kLRingBytes + (size_t)kLDrawBytes + (sizeof(Leaf) + sizeof(Fresh)) * (size_t)bs +
+            sizeof(ChainNode) * ((size_t)bs + 1) + 15) & ~(size_t)15;
 }
+// batch 32: 8,800 B a wave (9,536 before the draw ring took the path area's place), 37,248 B a
+// workgroup with the tables: four workgroups per CU fit the 160 KB as before
+static_assert(c4_search_wave_lds(32) == 8800 && c4_search_wave_lds(32) <= 9536, "per-wave LDS at batch 32");
+static_assert(4 * (kTabBytes + kSearchWaves * c4_search_wave_lds(32)) <= 160 * 1024, "four workgroups per CU");
 
-// Per-wave LDS of the search: the MT ring, fresh nodes, pending leaves, their paths.
+// Per-wave LDS of the search: the MT rings (raw words, draws), fresh nodes, pending leaves,
+// the chain table.  The rings come first: their place does not depend on the batch size.
 struct SearchLds {
     uint32_t *s_order;  // the workgroup's tables: order[128] u32 + sel[128][8]
-    uint32_t *ring;
+    uint32_t *ring;     // kLRingBytes raw words, then kLDrawBytes draws (LRng)
     Fresh *fresh;
     Leaf *leaves;
-    uint16_t *paths;
+    ChainNode *chain;
 };
 
 __device__ __forceinline__ SearchLds search_lds(uint8_t *s_dyn, int bs) {
@@ -1128,9 +1138,10 @@ __device__ __forceinline__ SearchLds search_lds(uint8_t *s_dyn, int bs) {
     SearchLds L;
     L.s_order = (uint32_t *)s_dyn;
     L.ring = (uint32_t *)s_wave;
-    L.fresh = (Fresh *)(s_wave + kLRingBytes);
-    L.leaves = (Leaf *)(s_wave + kLRingBytes + sizeof(Fresh) * (size_t)bs);
-    L.paths = (uint16_t *)(s_wave + kLRingBytes + (sizeof(Fresh) + sizeof(Leaf)) * (size_t)bs);
+    constexpr size_t kRings = (size_t)kLRingBytes + (size_t)kLDrawBytes;
+    L.fresh = (Fresh *)(s_wave + kRings);
+    L.leaves = (Leaf *)(s_wave + kRings + sizeof(Fresh) * (size_t)bs);
+    L.chain = (ChainNode *)(s_wave + kRings + (sizeof(Fresh) + sizeof(Leaf)) * (size_t)bs);
     return L;
 }
 
@@ -1179,8 +1190,7 @@ __device__ __forceinline__ void search_move(const SearchParams &p, const SearchL
 #ifndef ZC_NO_PLAN
 #define ZC_NO_PLAN 0
 #endif
-            // one lane per draw and lane 63 free as the permutes' discard slot (bs < 64); the chain
-            // table lives in the leaf-path area, which this search does not use
+            // one lane per draw and lane 63 free as the permutes' discard slot (bs < 64)
 #ifndef ZC_PLAN2
 #define ZC_PLAN2 1  // 0: the chain's draws node by node (select_flush_plan), for A/B runs
 #endif
@@ -1189,7 +1199,7 @@ __device__ __forceinline__ void search_move(const SearchParams &p, const SearchL
                                           uni64(root.stones[0]), uni64(root.stones[1]), uni(root.turn), done, nb,
                                           p.c, fs);
             else if (!ZC_NO_PLAN && p.bs < 64)
-                select_flush_plan<STAMP>(t, fresh, leaves, (ChainNode *)L.paths, s_order, logtab, rng, cn, stamp,
+                select_flush_plan<STAMP>(t, fresh, leaves, L.chain, s_order, logtab, rng, cn, stamp,
                                          nnodes, status, uni64(root.stones[0]), uni64(root.stones[1]),
                                          uni(root.turn), done, nb, p.c, fs);
             else
@@ -1726,7 +1736,7 @@ __global__ void uct_debug_kernel(int n, const double *logn, const int32_t *na, c
 
 }  // namespace
 
-// Games per workgroup: up to kSearchWaves share the tables (4 x ~9.3 KB + 1.5 KB at bs 32, so
+// Games per workgroup: up to kSearchWaves share the tables (4 x ~8.6 KB + 2 KB at bs 32, so
 // four workgroups = 16 waves per CU fit the CU's 160 KB of LDS); fewer when a large batch
 // would not fit one workgroup (sharing only lowers the LDS per game).
 static int c4_search_wpg(int bs) {
