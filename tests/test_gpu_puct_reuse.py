@@ -65,9 +65,19 @@ def _is_fresh(d, state):
     assert (d["child"][0] == 0xFFFF).all() and (d["na"][0] == 0).all()
 
 
-@pytest.mark.parametrize("plies", [1, 2])
-@pytest.mark.parametrize("sims,bs", [(65, 8), (200, 32)])
-def test_reroot_is_exactly_the_subtree(eng, sims, bs, plies):
+def _subtree_ids(d, r):
+    """The old ids of r's subtree in a dump, ascending (a parent's id is below its child's)."""
+    ids = []
+    for i in range(r, len(d)):
+        if i == r or int(d["parent"][i]) in ids:
+            ids.append(i)
+    return ids
+
+
+def _check_reroot(eng, sims, bs, plies, next_sims):
+    """A search of POSITIONS * 2, then the re-root alone (for a search of next_sims) at the chosen
+    column's child, or at that child's most visited reply: the trees against spec.compact.
+    Returns the nodes kept per game and the old ids they span."""
     from zeroclone_amd.valued import C4PuctSearch
     pos = POSITIONS * 2
     n = len(pos)
@@ -85,8 +95,8 @@ def test_reroot_is_exactly_the_subtree(eng, sims, bs, plies):
             if ch:
                 t = max(ch)[2]
         targets.append(t)
-    kept = _begin_reuse(eng, ps, _rows([_state(d, t) for d, t in zip(dumps, targets)]), sims)
-    moved = 0
+    kept = _begin_reuse(eng, ps, _rows([_state(d, t) for d, t in zip(dumps, targets)]), next_sims)
+    moved, span = 0, []
     for g, (d, t) in enumerate(zip(dumps, targets)):
         after = eng.debug_c4_puct_tree(g)
         r = spec.find(d, *_state(d, t))
@@ -96,11 +106,33 @@ def test_reroot_is_exactly_the_subtree(eng, sims, bs, plies):
             continue
         assert r == t and int(d["depth"][t]) == plies
         want = spec.compact(d, r)
-        assert len(want) + sims - 1 <= M
+        assert len(want) + next_sims - 1 <= M
         assert kept[g] == len(want)
         _same_records(after, want)
         moved += len(want) > 1
+        span.append(_subtree_ids(d, r)[-1] - r)
     assert moved >= 6   # most games kept a real subtree
+    return kept, span
+
+
+@pytest.mark.parametrize("plies", [1, 2])
+@pytest.mark.parametrize("sims,bs", [(65, 8), (200, 32)])
+def test_reroot_is_exactly_the_subtree(eng, sims, bs, plies):
+    """By the spec on the CPU (c_puct 1.5, uniform priors) the searches of 200 simulations keep 58,
+    43, 72, 25 and 58 nodes one ply down and 22, 18, 30, 0 and 11 two plies down, from old ids
+    that span 83 or more: the kept records come from more than one 64-node chunk of the old tree."""
+    kept, span = _check_reroot(eng, sims, bs, plies, sims)
+    if sims == 200:
+        assert max(span) > 64
+
+
+def test_reroot_of_more_than_64_kept_nodes(eng):
+    """A full tree (sims = max_sims = 400) re-rooted for a search of 2 simulations, so that the
+    room rule lets a subtree of more than 64 nodes through: more than one chunk of new ids in the
+    record move and the link pass.  By the spec on the CPU (c_puct 1.5, uniform priors) the five
+    positions keep 109, 166, 184, 103 and 176 nodes one ply down."""
+    kept, _ = _check_reroot(eng, 400, 32, 1, 2)
+    assert max(kept) > 64
 
 
 @pytest.mark.parametrize("start", [0, 1])

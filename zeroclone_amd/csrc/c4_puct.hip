@@ -11,15 +11,18 @@
 //           (the child is created and is the leaf), at a terminal position (four in a row
 //           for the last mover, or a full board) or at a node still waiting for its
 //           evaluation; virtual loss on every edge walked (N += 1, W -= 1) until backup;
-//   backup  per leaf in pending order: a first evaluation sets the node's priors = softmax
-//           of the policy head's 7 column logits over the legal columns (Dirichlet(alpha)
-//           noise of weight eps at the root, Philox keyed by (seed, game)); every edge then
-//           takes W += 1 - r with r = the leaf value, alternating in sign (N already
-//           counted); a terminal leaf's value is -1 (the side to move has lost) or 0;
-//   root    flush 0 evaluates the root alone.
+//   backup  per leaf in pending order: a first evaluation sets the node's priors from the
+//           policy head's 7 column logits over the legal columns; every edge then takes
+//           W += 1 - r with r = the leaf value, alternating in sign (N already counted); a
+//           terminal leaf's value is -1 (the side to move has lost) or 0;
 //   reuse   (opt-in, zc_c4_puct_begin_reuse) the subtree of the position now at the root, one
 //           or two plies below the last search's root, is compacted in place into the next
-//           tree; such a search has no flush-0 leaf and adds sims - 1 visits.
+//           tree.
+//
+// What the search shares with the chess one is in puct_common.h, each rule beside its code:
+// the flush schedule (flush 0 evaluates the root alone), the control words, the softmax of
+// the priors, the root noise, the temperature sample and the re-root's numbering and record
+// move.  This file holds the game: the node, the walk, the planes and the columns.
 //
 // Node = one 192-byte record, slot k (a move, in the node's move-list order) in lane k:
 // everything a selection step reads is one coalesced load per field.  One wave per game.
@@ -34,17 +37,12 @@ namespace {
 
 static_assert(sizeof(C4PNode) == 192, "C4PNode is 192 bytes");
 
-// pDone: the game's last search ran to end with status 0 (its tree may be re-rooted);
-// pReused: the search in progress started from a kept subtree (flush 0 has no leaf)
-enum : int { pNodes = 0, pStatus = 1, pNb = 2, pExp = 3, pDepth = 4, pDone = 5, pReused = 6 };
+// the search's control words (puct_common.h) in this game's ctl block
+struct PCtl {
+    static constexpr int nodes = 0, status = 1, nb = 2, exp = 3, depth = 4, done = 5, reused = 6;
+};
 
 __device__ __forceinline__ C4PNode *pnodes(const C4PuctParams &p, int g) { return p.nodes + (size_t)g * p.M; }
-
-// flushes: 0 = the root alone, then batches of bs
-__device__ __forceinline__ int pflush_leaves(const C4PuctParams &p, int f) {
-    if (f == 0) return 1;
-    return max(0, min(p.bs, p.sims - 1 - (f - 1) * p.bs));
-}
 
 // Node(state): move list in CPython set order (c4_backend.get_legal_moves), none at a
 // terminal position (the last mover has four, or the board is full).
@@ -93,23 +91,12 @@ __global__ __launch_bounds__(64) void c4_puct_begin_kernel(C4PuctParams p) {
         wave_mem_order();
         if (uni((int)N->nmoves) == 0) status = ZC_STATUS_NO_MOVES;
     }
-    if (lane_id() == 0) {
-        ctl[pNodes] = 1;
-        ctl[pStatus] = status;
-        ctl[pNb] = 0;
-        ctl[pExp] = 0;
-        ctl[pDepth] = 0;
-        ctl[pDone] = 0;
-        ctl[pReused] = 0;
-    }
+    search_reset<PCtl>(p, ctl, gl, 0, status);
 }
 
 // ---- tree reuse: the subtree of the position now at the root becomes the next tree ----
-// Node ids are in creation order (a parent's id is below its child's), so one ascending pass
-// over the ids decides which nodes descend from the new root and numbers them, a second one
-// moves the records down in place (new id <= old id, and a chunk's stores land only on
-// records that this or an earlier chunk has already loaded), and a third renumbers the moved
-// records' parent and child links.
+// reroot_find names the new root, reroot_number and puct_common.h's reroot_move_records
+// compact its subtree, and reroot_link renumbers the moved records' parent and child links.
 
 // The node holding (s0, s1, turn) one ply below the old root, else two plies below it; the
 // first in slot order (slot of the child, then slot of the grandchild), or -1.
@@ -139,57 +126,21 @@ __device__ int reroot_number(const C4PNode *T, uint16_t *remap, int n, int r) {
         const int i = base + (int)lane;
         const bool valid = i < n;
         const int par = valid ? (int)T[i].parent : 0xFFFF;
-        // a parent in an earlier chunk: its entry is final
-        bool k = valid && (i == r || (par >= r && par < base && remap[par] != 0xFFFF));
-        const bool inpar = valid && par >= base && par < i;
-        const int pl = inpar ? par - base : 0;  // the parent's lane
-        uint64_t b = __ballot(k);
-        for (;;) {  // parents in this chunk: at most one round per level of the tree
-            k = k || (inpar && ((b >> pl) & 1ull));
-            const uint64_t nb = __ballot(k);
-            if (nb == b) break;
-            b = nb;
-        }
+        const uint64_t b = reroot_mark(i, valid, par, r, base, remap);
+        const bool k = (b >> lane) & 1ull;
         const int id = cnt + __popcll(b & ((1ull << lane) - 1ull));
         if (valid) remap[i] = k ? (uint16_t)id : (uint16_t)0xFFFF;
         cnt += __popcll(b);
-        wave_mem_order();
-        __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next chunk's lanes read these entries
+        vm_drain();  // the next chunk's lanes read these entries
     }
     return cnt;
 }
 
-// Pass 2: the kept records move to their new ids, 64 ids a chunk as 12 x 64 16-byte pieces.
-__device__ void reroot_move(C4PNode *T, const uint16_t *remap, int n, int r) {
-    const uint32_t lane = lane_id();
-    constexpr int kPieces = (int)sizeof(C4PNode) / 16;
-    for (int base = r; base < n; base += 64) {
-        const int rows = min(64, n - base);
-        const uint4 *src = reinterpret_cast<const uint4 *>(T + base);
-        uint4 v[kPieces];
-        uint32_t dst[kPieces];
-#pragma unroll
-        for (int it = 0; it < kPieces; ++it) {
-            const int q = it * 64 + (int)lane, rec = q / kPieces;
-            const bool valid = rec < rows;
-            v[it] = valid ? src[q] : make_uint4(0, 0, 0, 0);
-            dst[it] = valid ? (uint32_t)remap[base + rec] : 0xFFFFu;
-        }
-        // every load of the chunk has returned before any of its stores is issued
-        wave_mem_order();
-        __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int it = 0; it < kPieces; ++it)
-            if (dst[it] != 0xFFFFu) reinterpret_cast<uint4 *>(T + dst[it])[(it * 64 + (int)lane) % kPieces] = v[it];
-        wave_mem_order();
-    }
-    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// Pass 3: the moved records' links, one node a lane: parent and children through the table
-// (they still hold old ids, all >= r: a kept node's parent and children are kept), depth
-// counted from the new root.  Piece 1 of a record holds parent / pact / depth, piece 2 its
-// eight children; the nine table reads of a node are independent loads.
+// Pass 2 is reroot_move_records.  Pass 3: the moved records' links, one node a lane: parent
+// and children through the table (they still hold old ids, all >= r: a kept node's parent and
+// children are kept), depth counted from the new root.  Piece 1 of a record holds parent /
+// pact / depth, piece 2 its eight children; the nine table reads of a node are independent
+// loads.
 __device__ void reroot_link(C4PNode *T, const uint16_t *remap, int kept, int n, int r, int rdepth) {
     for (int id = (int)lane_id(); id < kept; id += 64) {
         uint4 *rec = reinterpret_cast<uint4 *>(T + id);
@@ -210,8 +161,7 @@ __device__ void reroot_link(C4PNode *T, const uint16_t *remap, int kept, int n, 
         reinterpret_cast<uint32_t *>(rec + 1)[2] =
             id == 0 ? 0x00FFFFFFu : now[8] | (pact << 16) | ((dep - (uint32_t)rdepth) << 24);
     }
-    wave_mem_order();
-    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_drain();
 }
 
 __global__ __launch_bounds__(64) void c4_puct_reroot_kernel(C4PuctParams p) {
@@ -229,9 +179,9 @@ __global__ __launch_bounds__(64) void c4_puct_reroot_kernel(C4PuctParams p) {
     if (!valid_state(s0, s1, turn)) {
         status = ZC_STATUS_BAD_STATE;
     } else {
-        const int n = uni(ctl[pNodes]);
+        const int n = uni(ctl[PCtl::nodes]);
         int r = -1;
-        if (uni(ctl[pDone]) == 1 && n >= 2 && n <= p.M) r = uni(reroot_find(T, n, s0, s1, turn));
+        if (uni(ctl[PCtl::done]) == 1 && n >= 2 && n <= p.M) r = uni(reroot_find(T, n, s0, s1, turn));
         if (r > 0 && (!uni((int)T[r].evaluated) || uni((int)T[r].nmoves) == 0)) r = -1;
         if (r > 0) {
             kept = reroot_number(T, remap, n, r);
@@ -239,16 +189,12 @@ __global__ __launch_bounds__(64) void c4_puct_reroot_kernel(C4PuctParams p) {
         }
         if (kept) {
             const int rdepth = uni((int)T[r].depth);
-            reroot_move(T, remap, n, r);
+            reroot_move_records(T, remap, n, r);
             reroot_link(T, remap, kept, n, r, rdepth);
-            if (p.dir_eps > 0.0f) {  // the fresh path's root noise (backup kernel), on the kept priors
-                const uint2 key = make_uint2((uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-                const bool valid = (int)lane < uni((int)T[0].nmoves);
-                float pr = valid ? T[0].pr[lane] : 0.0f;
-                const float gm = valid ? gamma_draw(p.dir_alpha, key, (uint32_t)g, lane, search_number(p, gl)) : 0.0f;
-                const float gs = wave_sum_f(gm);
-                pr = (1.0f - p.dir_eps) * pr + p.dir_eps * (gs > 0.0f ? gm / gs : 0.0f);
-                if (valid) T[0].pr[lane] = pr;
+            if (p.dir_eps > 0.0f) {  // on the kept priors
+                const int nm = uni((int)T[0].nmoves);
+                const MoveRegs<1> pr = mix_root_noise(p, g, gl, nm, MoveRegs<1>{{(int)lane < nm ? T[0].pr[lane] : 0.0f}});
+                if ((int)lane < nm) T[0].pr[lane] = pr.v[0];
             }
         } else {
             pnode_init(T, s0, s1, turn, 0xFFFF, 0xFF, 0);
@@ -256,21 +202,7 @@ __global__ __launch_bounds__(64) void c4_puct_reroot_kernel(C4PuctParams p) {
             if (uni((int)T->nmoves) == 0) status = ZC_STATUS_NO_MOVES;
         }
     }
-    if (lane == 0) {
-        ctl[pNodes] = kept ? kept : 1;
-        ctl[pStatus] = status;
-        ctl[pNb] = 0;
-        ctl[pExp] = 0;
-        ctl[pDepth] = 0;
-        ctl[pDone] = 0;
-        ctl[pReused] = kept ? 1 : 0;
-        if (p.out_kept) p.out_kept[gl] = kept;
-    }
-}
-
-__global__ void c4_puct_forget_kernel(C4PuctParams p) {
-    const int gl = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gl < p.n_games) p.ctl[(size_t)(p.first_game + gl) * kCtlWords + pDone] = 0;
+    search_reset<PCtl>(p, ctl, gl, kept, status);
 }
 
 // One PUCT walk + expansion; returns the leaf and its depth, the edges of its path in lanes
@@ -346,10 +278,9 @@ __global__ __launch_bounds__(64) void c4_puct_select_kernel(C4PuctParams p) {
     C4PNode *T = pnodes(p, g);
     int32_t *ctl = p.ctl + (size_t)g * kCtlWords;
     const uint32_t lane = lane_id();
-    int status = uni(ctl[pStatus]);
-    int nb = status ? 0 : pflush_leaves(p, p.flush);
-    if (p.flush == 0 && uni(ctl[pReused])) nb = 0;  // a kept root is evaluated already
-    int nnodes = uni(ctl[pNodes]);
+    int status = uni(ctl[PCtl::status]);
+    int nb = select_leaves<PCtl>(p, ctl, status);
+    int nnodes = uni(ctl[PCtl::nodes]);
     uint32_t *paths = p.paths + (size_t)g * p.max_batch * kMaxDepth;
     uint32_t *meta = p.meta + (size_t)g * p.max_batch;
     Counters cn;
@@ -360,16 +291,7 @@ __global__ __launch_bounds__(64) void c4_puct_select_kernel(C4PuctParams p) {
         if (lane < (uint32_t)kMaxDepth) paths[(size_t)j * kMaxDepth + lane] = pathv;
         if (lane == 0) meta[j] = (uint32_t)leaf | ((uint32_t)d << 16);
     }
-    if (status) nb = 0;
-    wave_mem_order();
-    if (lane == 0) {
-        ctl[pNodes] = nnodes;
-        ctl[pStatus] = status;
-        ctl[pNb] = nb;
-        ctl[pExp] += cn.expansions;
-        ctl[pDepth] += cn.depth_sum;
-        if (p.counts) p.counts[gl] = nb;
-    }
+    nb = select_done<PCtl>(p, ctl, gl, nnodes, status, nb, cn);
     // the pending flush's leaves: states, and state_to_tensor planes (c4_backend.py:52-61:
     // [2][6][7], plane 0 = the side to move's stones, row 0 = top = bit row 5 - r)
     const size_t obase = (size_t)gl * p.bs;
@@ -406,11 +328,10 @@ __global__ __launch_bounds__(64) void c4_puct_backup_kernel(C4PuctParams p) {
     C4PNode *T = pnodes(p, g);
     int32_t *ctl = p.ctl + (size_t)g * kCtlWords;
     const uint32_t lane = lane_id();
-    const int nb = uni(ctl[pNb]);
-    if (uni(ctl[pStatus]) || nb == 0) return;
+    const int nb = uni(ctl[PCtl::nb]);
+    if (uni(ctl[PCtl::status]) || nb == 0) return;
     const uint32_t *paths = p.paths + (size_t)g * p.max_batch * kMaxDepth;
     const uint32_t *meta = p.meta + (size_t)g * p.max_batch;
-    const uint2 key = make_uint2((uint32_t)p.seed, (uint32_t)(p.seed >> 32));
     for (int j = 0; j < nb; ++j) {
         const uint32_t mt = uni(meta[j]);
         const int node = (int)(mt & 0xFFFFu), d = (int)(mt >> 16);
@@ -423,33 +344,25 @@ __global__ __launch_bounds__(64) void c4_puct_backup_kernel(C4PuctParams p) {
         } else {
             v = __hiloint2double(uni(__double2hiint(p.values[li])), uni(__double2loint(p.values[li])));
             if (!(fabs(v) < INFINITY)) {  // a NaN or infinite value: the game's backup stops here
-                if (lane == 0) ctl[pStatus] = ZC_STATUS_INTERNAL;
+                if (lane == 0) ctl[PCtl::status] = ZC_STATUS_INTERNAL;
                 return;
             }
             if (!uni((int)N->evaluated)) {
-                // priors: softmax of the column logits over the node's legal columns, in
-                // move-list order (slot k = lane k)
+                // the logits of the node's legal columns, in move-list order (slot k = lane k)
                 const bool valid = lane < (uint32_t)nm;
                 const uint32_t col = (uni(N->order) >> (3 * (lane & 7u))) & 7u;
-                float lg = -INFINITY;
+                MoveRegs<1> lg{{-INFINITY}};
                 if (valid)
-                    lg = p.logits_f16 ? __half2float(((const __half *)p.logits)[li * 7 + col])
-                                      : ((const float *)p.logits)[li * 7 + col];
-                const float mx = wave_max_f(lg);
-                const float e = valid ? expf(lg - mx) : 0.0f;
-                const float sum = wave_sum_f(e);
-                // a NaN or +inf logit on a legal column, or -inf on all of them: no priors
-                if (__ballot(!(sum > 0.0f && sum < INFINITY))) {
-                    if (lane == 0) ctl[pStatus] = ZC_STATUS_INTERNAL;
+                    lg.v[0] = p.logits_f16 ? __half2float(((const __half *)p.logits)[li * 7 + col])
+                                           : ((const float *)p.logits)[li * 7 + col];
+                const Priors<1> sm = softmax_priors(lg, nm);
+                if (!sm.ok) {
+                    if (lane == 0) ctl[PCtl::status] = ZC_STATUS_INTERNAL;
                     return;
                 }
-                float pr = e / sum;
-                if (node == 0 && p.dir_eps > 0.0f) {  // Dirichlet(alpha) noise on the root priors
-                    const float gm = valid ? gamma_draw(p.dir_alpha, key, (uint32_t)g, lane, search_number(p, gl)) : 0.0f;
-                    const float gs = wave_sum_f(gm);
-                    pr = (1.0f - p.dir_eps) * pr + p.dir_eps * (gs > 0.0f ? gm / gs : 0.0f);
-                }
-                if (valid) N->pr[lane] = pr;
+                MoveRegs<1> pr = sm.pr;
+                if (node == 0 && p.dir_eps > 0.0f) pr = mix_root_noise(p, g, gl, nm, pr);
+                if (valid) N->pr[lane] = pr.v[0];
                 if (lane == 0) N->evaluated = 1;
             }
         }
@@ -474,7 +387,7 @@ __global__ __launch_bounds__(64) void c4_puct_end_kernel(C4PuctParams p) {
     int32_t *ctl = p.ctl + (size_t)g * kCtlWords;
     const uint32_t lane = lane_id();
     const uint32_t k = lane & 7u;
-    const int status = uni(ctl[pStatus]);
+    const int status = uni(ctl[PCtl::status]);
     const int nm = status ? 0 : uni((int)R->nmoves);
     const uint32_t ow = status ? 0u : uni(R->order);
     const int32_t na = (int)k < nm ? R->na[k] : -1;
@@ -498,9 +411,7 @@ __global__ __launch_bounds__(64) void c4_puct_end_kernel(C4PuctParams p) {
             const int kb = count_bits(top);
             double tot = 0.0;
             for (int j = 0; j < nm; ++j) tot += temperature_weight(uni(R->na[j]), kb, inv_t);
-            const uint4 r = philox(make_uint4((uint32_t)g, 0x5BE0CD19u, search_number(p, gl), 0),
-                                   make_uint2((uint32_t)p.seed, (uint32_t)(p.seed >> 32)));
-            const double target = (double)u01(r.x) * tot;
+            const double target = temperature_target(p, g, gl, tot);
             double run = 0.0;
             best = nm - 1;
             for (int j = 0; j < nm; ++j) {
@@ -513,15 +424,8 @@ __global__ __launch_bounds__(64) void c4_puct_end_kernel(C4PuctParams p) {
         }
     }
     if (lane == 0) {
-        if (p.search_no) p.search_no[gl] = (int32_t)(search_number(p, gl) + 1);
         p.out_move[gl] = best >= 0 ? (int)((ow >> (3 * best)) & 7u) : -1;
-        zc_game_stats st{};
-        st.status = status;
-        st.expansions = ctl[pExp];
-        st.depth_sum = ctl[pDepth];
-        st.leaves = ctl[pReused] ? p.sims - 1 : p.sims;
-        p.out_stats[gl] = st;
-        ctl[pDone] = status == 0 ? 1 : 0;
+        search_done<PCtl>(p, ctl, gl, status);
     }
 }
 
@@ -534,7 +438,7 @@ void launch_c4_puct_reroot(const C4PuctParams &p, hipStream_t s) {
     hipLaunchKernelGGL(c4_puct_reroot_kernel, dim3(p.n_games), dim3(64), 0, s, p);
 }
 void launch_c4_puct_forget(const C4PuctParams &p, hipStream_t s) {
-    hipLaunchKernelGGL(c4_puct_forget_kernel, dim3((p.n_games + 63) / 64), dim3(64), 0, s, p);
+    launch_puct_forget(p.ctl, p.first_game, p.n_games, PCtl::done, s);
 }
 void launch_c4_puct_select(const C4PuctParams &p, hipStream_t s) {
     hipLaunchKernelGGL(c4_puct_select_kernel, dim3(p.n_games), dim3(64), 0, s, p);

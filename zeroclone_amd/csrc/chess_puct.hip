@@ -10,16 +10,19 @@
 //   virtual loss: every edge of a pending leaf's path counts as one visit lost by the
 //           parent's mover (N += 1, W -= 1) until the flush is backed up, so the leaves of a
 //           flush spread over the tree instead of repeating one path;
-//   backup  per leaf in pending order: the node's priors = softmax of the policy logits over
-//           its legal moves (first evaluation only), then each edge undoes its virtual loss
-//           and takes the value (W += 1 - r, N already counted), r alternating in sign;
-//           a terminal leaf's value is -1 (side to move mated) or 0 (no moves otherwise);
-//   root    flush 0 evaluates the root alone; its priors get Dirichlet(alpha) noise with
-//           weight eps, drawn with a counter-based Philox4x32-10 stream keyed by (seed, game).
+//   backup  per leaf in pending order: the node's priors from the policy logits of its legal
+//           moves (first evaluation only), then each edge undoes its virtual loss and takes
+//           the value (W += 1 - r, N already counted), r alternating in sign; a terminal
+//           leaf's value is -1 (side to move mated) or 0 (no moves otherwise);
 //   reuse   (opt-in, zc_chess_puct_begin_reuse) the subtree of the position now at the root, one
 //           or two plies below the last search's root, is compacted in place into the next
-//           tree, node records and child slots; such a search has no flush-0 leaf and adds
-//           sims - 1 visits.
+//           tree, node records and child slots.
+//
+// What the search shares with the Connect4 one is in puct_common.h, each rule beside its code:
+// the flush schedule (flush 0 evaluates the root alone), the control words, the softmax of the
+// priors, the root noise, the temperature sample and the re-root's numbering and record move.
+// This file holds the game: the walk over a node's 4 x 64 slots, the deferred expansion, the
+// slots' part of the re-root and the planes.
 //
 // Launches (one wave per game): begin or re-root (root node), select (flush f's leaves, planes),
 // backup (priors + values), end (move by visits or temperature sampling, visit counts).
@@ -34,11 +37,11 @@ namespace {
 // meta[j] bit 31: leaf j's walk created its node (its moves are generated after the walks)
 constexpr uint32_t kMetaCreated = 0x80000000u;
 
-// flushes: 0 = the root alone, then batches of bs
-__device__ __forceinline__ int flush_leaves(const ChessParams &p, int f) {
-    if (f == 0) return 1;
-    return max(0, min(p.bs, p.sims - 1 - (f - 1) * p.bs));
-}
+// the search's control words (puct_common.h) among the chess searches' (chess_tree.h)
+struct PCtl {
+    static constexpr int nodes = cNodes, status = cStatus, nb = cNb, exp = cExp, depth = cDepth, done = cDone,
+                         reused = cReused;
+};
 
 // One PUCT walk + expansion; returns the leaf, its depth, and the edge slots of its path
 // in lanes 1..depth of pathv.  Applies the virtual loss on every edge it takes.
@@ -180,31 +183,18 @@ __global__ __launch_bounds__(64) void puct_begin_kernel(ChessParams p) {
     int slots = 0, status = 0;
     create_node(t, L, 0, 0xFFFF, 0xFFFF, 0, slots, status);
     if (!status && uni((int)t.nodes[0].nmoves) == 0) status = ZC_STATUS_NO_MOVES;
-    if (lane == 0) {
-        ctl[cNodes] = 1;
-        ctl[cSlots] = slots;
-        ctl[cStatus] = status;
-        ctl[cNb] = 0;
-        ctl[cExp] = 0;
-        ctl[cDepth] = 0;
-        ctl[cDone] = 0;
-        ctl[cReused] = 0;
-    }
+    if (lane == 0) ctl[cSlots] = slots;
+    search_reset<PCtl>(p, ctl, gl, 0, status);
 }
 
 // ---- tree reuse: the subtree of the position now at the root becomes the next tree ----
-// (c4_puct.hip's re-root on the chess tree's two address spaces.)  Node ids are in creation
-// order and so are the slot ranges (puct_commit_kernel hands them out in creation order), so a
-// kept node's new id is <= its old id and its new first slot <= its old one: one ascending pass
-// numbers the kept nodes and sums their move counts into the new bases, the node records and
-// then the slots move down in place, 64 at a time with every load of a chunk returned before
-// any of its stores is issued, and a last pass renumbers the parents.  Every index read from
-// the arena is bounded before it is used: a tree that fails a bound is not kept.
-
-__device__ __forceinline__ void vm_drain() {
-    wave_sync_mem();
-    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
+// The re-root of puct_common.h on the chess tree's two address spaces.  The slot ranges are in
+// creation order as the node ids are (puct_commit_kernel hands them out in creation order), so
+// a kept node's new first slot is <= its old one: the numbering pass also sums the kept nodes'
+// move counts into the new bases, and after the node records the slots move down in place, 64
+// at a time with every load of a step returned before any of its stores is issued; a last pass
+// renumbers the parents.  Every index read from the arena is bounded before it is used: a tree
+// that fails a bound is not kept.
 
 // Whether node id (0 < id < n) holds the position in tgt[0..16]: board, turn, fifty, castle
 // (word 16's low three bytes; the reserved bytes are not compared).
@@ -263,10 +253,10 @@ __device__ int reroot_find(const CTree &t, const uint32_t *tgt, int n, int s) {
     return -1;
 }
 
-// Pass 1 (c4_puct.hip reroot_number, plus the slots): remap[i] = the new id of node i of r's
-// subtree, 0xFFFF for any other node i >= r; rbase[new id] = the node's new first slot, the
-// running sum of the kept nodes' move counts.  Returns the nodes kept and, in `kslots`, their
-// slots; 0 when a kept node's slot range fails a bound.
+// Pass 1: remap[i] = the new id of node i of r's subtree, 0xFFFF for any other node i >= r;
+// rbase[new id] = the node's new first slot, the running sum of the kept nodes' move counts.
+// Returns the nodes kept and, in `kslots`, their slots; 0 when a kept node's slot range fails a
+// bound.
 __device__ int reroot_number(const CTree &t, uint16_t *remap, uint32_t *rbase, int n, int s, int r, int &kslots) {
     const uint32_t lane = lane_id();
     int cnt = 0, tot = 0;
@@ -277,17 +267,8 @@ __device__ int reroot_number(const CTree &t, uint16_t *remap, uint32_t *rbase, i
         const int par = valid ? (int)t.nodes[i].parent : 0xFFFF;
         const int nm = valid ? (int)t.nodes[i].nmoves : 0;
         const uint32_t ob = valid ? t.nodes[i].base : 0u;
-        // a parent in an earlier chunk: its entry is final
-        bool k = valid && (i == r || (par >= r && par < b0 && remap[par] != 0xFFFF));
-        const bool inpar = valid && par >= b0 && par < i;
-        const int pl = inpar ? par - b0 : 0;  // the parent's lane
-        uint64_t b = __ballot(k);
-        for (;;) {  // parents in this chunk: at most one round per level of the tree
-            k = k || (inpar && ((b >> pl) & 1ull));
-            const uint64_t nb = __ballot(k);
-            if (nb == b) break;
-            b = nb;
-        }
+        const uint64_t b = reroot_mark(i, valid, par, r, b0, remap);
+        const bool k = (b >> lane) & 1ull;
         const int id = cnt + __popcll(b & ((1ull << lane) - 1ull));
         // exclusive prefix sum of the kept nodes' move counts over the chunk, plus the carry
         const int mine = k ? nm : 0;
@@ -310,32 +291,7 @@ __device__ int reroot_number(const CTree &t, uint16_t *remap, uint32_t *rbase, i
     return __ballot(bad) ? 0 : cnt;
 }
 
-// Pass 2: the kept records move to their new ids, 64 ids a chunk as 6 x 64 16-byte pieces.
-__device__ void reroot_move_nodes(ChessNode *T, const uint16_t *remap, int n, int r) {
-    const uint32_t lane = lane_id();
-    constexpr int kPieces = (int)sizeof(ChessNode) / 16;
-    for (int b0 = r; b0 < n; b0 += 64) {
-        const int rows = min(64, n - b0);
-        const uint4 *src = reinterpret_cast<const uint4 *>(T + b0);
-        uint4 v[kPieces];
-        uint32_t dst[kPieces];
-#pragma unroll
-        for (int it = 0; it < kPieces; ++it) {
-            const int q = it * 64 + (int)lane, rec = q / kPieces;
-            const bool valid = rec < rows;
-            v[it] = valid ? src[q] : make_uint4(0, 0, 0, 0);
-            dst[it] = valid ? (uint32_t)remap[b0 + rec] : 0xFFFFu;
-        }
-        vm_drain();  // every load of the chunk has returned before any of its stores is issued
-#pragma unroll
-        for (int it = 0; it < kPieces; ++it)
-            if (dst[it] != 0xFFFFu) reinterpret_cast<uint4 *>(T + dst[it])[(it * 64 + (int)lane) % kPieces] = v[it];
-        wave_sync_mem();
-    }
-    vm_drain();
-}
-
-// Pass 3: the kept slots move to [0, kslots) by flat slot index, 64 slots a step: a window of
+// Pass 2 is reroot_move_records.  Pass 3: the kept slots move to [0, kslots) by flat slot index, 64 slots a step: a window of
 // 64 kept nodes (new ids; a moved record still holds its old base) gives, per slot, its node by
 // a search over the window's new bases in registers, and so its old slot.  New slot d comes from
 // an old slot >= d, so a step's stores land only on slots that this or an earlier step has
@@ -443,49 +399,26 @@ __global__ __launch_bounds__(64) void puct_reroot_kernel(ChessParams p) {
     int slots = 0, status = 0;
     if (kept) {
         const int rdepth = uni((int)t.nodes[r].depth);
-        reroot_move_nodes(t.nodes, remap, n, r);
+        reroot_move_records(t.nodes, remap, n, r);
         reroot_move_slots(t, remap, rbase, kept, n, r);
         reroot_link(t.nodes, remap, rbase, kept, n, r, rdepth);
         slots = kslots;
-        if (p.dir_eps > 0.0f) {  // the fresh path's root noise (backup kernel), on the kept priors
-            const uint2 key = make_uint2((uint32_t)p.seed, (uint32_t)(p.seed >> 32));
+        if (p.dir_eps > 0.0f) {  // on the kept priors
             const int nm = uni((int)t.nodes[0].nmoves);
-            float pr[4], gm[4], gs = 0.0f;
+            MoveRegs<4> pr;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int k = q * 64 + (int)lane;
-                pr[q] = k < nm ? t.pr[k] : 0.0f;
-                gm[q] = k < nm ? gamma_draw(p.dir_alpha, key, (uint32_t)g, (uint32_t)k, search_number(p, gl)) : 0.0f;
-                gs += gm[q];
-            }
-            gs = wave_sum_f(gs);
+            for (int q = 0; q < 4; ++q) pr.v[q] = q * 64 + (int)lane < nm ? t.pr[q * 64 + (int)lane] : 0.0f;
+            pr = mix_root_noise(p, g, gl, nm, pr);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int k = q * 64 + (int)lane;
-                pr[q] = (1.0f - p.dir_eps) * pr[q] + p.dir_eps * (gs > 0.0f ? gm[q] / gs : 0.0f);
-                if (k < nm) t.pr[k] = pr[q];
-            }
+            for (int q = 0; q < 4; ++q)
+                if (q * 64 + (int)lane < nm) t.pr[q * 64 + (int)lane] = pr.v[q];
         }
     } else {  // as puct_begin_kernel
         create_node(t, L, 0, 0xFFFF, 0xFFFF, 0, slots, status);
         if (!status && uni((int)t.nodes[0].nmoves) == 0) status = ZC_STATUS_NO_MOVES;
     }
-    if (lane == 0) {
-        ctl[cNodes] = kept ? kept : 1;
-        ctl[cSlots] = slots;
-        ctl[cStatus] = status;
-        ctl[cNb] = 0;
-        ctl[cExp] = 0;
-        ctl[cDepth] = 0;
-        ctl[cDone] = 0;
-        ctl[cReused] = kept ? 1 : 0;
-        if (p.out_kept) p.out_kept[gl] = kept;
-    }
-}
-
-__global__ void puct_forget_kernel(ChessParams p) {
-    const int gl = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gl < p.n_games) p.ca.ctl[(size_t)(p.first_game + gl) * kCtlWords + cDone] = 0;
+    if (lane == 0) ctl[cSlots] = slots;
+    search_reset<PCtl>(p, ctl, gl, kept, status);
 }
 
 __global__ __launch_bounds__(64) void puct_select_kernel(ChessParams p) {
@@ -497,8 +430,7 @@ __global__ __launch_bounds__(64) void puct_select_kernel(ChessParams p) {
     int32_t *ctl = p.ca.ctl + (size_t)g * kCtlWords;
     const uint32_t lane = lane_id();
     int status = uni(ctl[cStatus]);
-    int nb = status ? 0 : flush_leaves(p, p.flush);
-    if (p.flush == 0 && uni(ctl[cReused])) nb = 0;  // a kept root is evaluated already
+    int nb = select_leaves<PCtl>(p, ctl, status);
     int nnodes = uni(ctl[cNodes]), slots = uni(ctl[cSlots]);
     uint32_t *paths = p.ca.paths + (size_t)g * p.max_batch * kChessPath;
     uint32_t *meta = p.ca.meta + (size_t)g * p.max_batch;
@@ -512,19 +444,10 @@ __global__ __launch_bounds__(64) void puct_select_kernel(ChessParams p) {
         if (lane < (uint32_t)kChessPath) paths[(size_t)j * kChessPath + lane] = pathv;
         if (lane == 0) meta[j] = (uint32_t)leaf | ((uint32_t)d << 16) | (created ? kMetaCreated : 0u);
     }
-    if (status) nb = 0;
-    wave_sync_mem();
-    if (lane == 0) {
-        ctl[cNodes] = nnodes;
-        ctl[cStatus] = status;
-        ctl[cNb] = nb;
-        ctl[cExp] += cn.expansions;
-        ctl[cDepth] += cn.depth_sum;
-        // the slots in use before this flush, for puct_commit_kernel: its blocks must not read
-        // cSlots, which the block of the flush's last created node rewrites in the same grid
-        ctl[cSlots0] = slots;
-        if (p.counts) p.counts[gl] = nb;
-    }
+    nb = select_done<PCtl>(p, ctl, gl, nnodes, status, nb, cn);
+    // the slots in use before this flush, for puct_commit_kernel: its blocks must not read
+    // cSlots, which the block of the flush's last created node rewrites in the same grid
+    if (lane == 0) ctl[cSlots0] = slots;
     const size_t obase = (size_t)gl * p.bs;
     for (int k = 0; k < nb; ++k) {
         const ChessNode *N = &t.nodes[uni(meta[k]) & 0xFFFFu];  // (the position is in the record already)
@@ -668,7 +591,6 @@ __global__ __launch_bounds__(64) void puct_backup_kernel(ChessParams p) {
     if (uni(ctl[cStatus]) || nb == 0) return;
     const uint32_t *paths = p.ca.paths + (size_t)g * p.max_batch * kChessPath;
     const uint32_t *meta = p.ca.meta + (size_t)g * p.max_batch;
-    const uint2 key = make_uint2((uint32_t)p.seed, (uint32_t)(p.seed >> 32));
     for (int j = 0; j < nb; ++j) {
         const uint32_t mt = uni(meta[j]);
         const int node = (int)(mt & 0xFFFFu), d = (int)((mt >> 16) & 0xFFu);
@@ -685,55 +607,30 @@ __global__ __launch_bounds__(64) void puct_backup_kernel(ChessParams p) {
                 return;
             }
             if (!uni((int)N->evaluated)) {
-                // priors: softmax of the logits of this node's legal moves (from*64 + to)
+                // the logits of this node's legal moves (from*64 + to)
                 const uint32_t base = uni(N->base);
-                float lg[4];
-                float mx = -INFINITY;
+                MoveRegs<4> lg;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int k = q * 64 + (int)lane;
-                    lg[q] = -INFINITY;
+                    lg.v[q] = -INFINITY;
                     if (k < nm) {
                         const uint32_t m = t.mv[base + k];
                         const size_t o = li * 4096 + (m & 63u) * 64 + ((m >> 6) & 63u);
-                        lg[q] = p.logits_f16 ? __half2float(((const __half *)p.logits)[o]) : ((const float *)p.logits)[o];
-                        mx = fmaxf(mx, lg[q]);
+                        lg.v[q] = p.logits_f16 ? __half2float(((const __half *)p.logits)[o]) : ((const float *)p.logits)[o];
                     }
                 }
-                mx = wave_max_f(mx);
-                float e[4], sum = 0.0f;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    e[q] = q * 64 + (int)lane < nm ? expf(lg[q] - mx) : 0.0f;
-                    sum += e[q];
-                }
-                sum = wave_sum_f(sum);
-                // a NaN or +inf logit on a legal move, or -inf on all of them: no priors
-                if (__ballot(!(sum > 0.0f && sum < INFINITY))) {
+                const Priors<4> sm = softmax_priors(lg, nm);
+                if (!sm.ok) {
                     if (lane == 0) ctl[cStatus] = ZC_STATUS_INTERNAL;
                     return;
                 }
-                float pr[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) pr[q] = e[q] / sum;
-                if (node == 0 && p.dir_eps > 0.0f) {
-                    // Dirichlet(alpha) noise on the root priors
-                    float gm[4], gs = 0.0f;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int k = q * 64 + (int)lane;
-                        gm[q] = k < nm ? gamma_draw(p.dir_alpha, key, (uint32_t)g, (uint32_t)k, search_number(p, gl)) : 0.0f;
-                        gs += gm[q];
-                    }
-                    gs = wave_sum_f(gs);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        pr[q] = (1.0f - p.dir_eps) * pr[q] + p.dir_eps * (gs > 0.0f ? gm[q] / gs : 0.0f);
-                }
+                MoveRegs<4> pr = sm.pr;
+                if (node == 0 && p.dir_eps > 0.0f) pr = mix_root_noise(p, g, gl, nm, pr);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int k = q * 64 + (int)lane;
-                    if (k < nm) t.pr[base + k] = pr[q];
+                    if (k < nm) t.pr[base + k] = pr.v[q];
                 }
                 if (lane == 0) N->evaluated = 1;
             }
@@ -798,9 +695,7 @@ __global__ __launch_bounds__(64) void puct_end_kernel(ChessParams p) {
                 tot += j < nm ? temperature_weight(t.na[base + j], kb, inv_t) : 0.0;
             }
             tot = wave_sum_d(tot);
-            const uint4 r = philox(make_uint4((uint32_t)g, 0x5BE0CD19u, search_number(p, gl), 0),
-                                   make_uint2((uint32_t)p.seed, (uint32_t)(p.seed >> 32)));
-            const double target = (double)u01(r.x) * tot;
+            const double target = temperature_target(p, g, gl, tot);
             double run = 0.0;
             best = nm - 1;
             for (int j = 0; j < nm; ++j) {  // serial scan in move order (<= 256 steps, once per move)
@@ -813,15 +708,8 @@ __global__ __launch_bounds__(64) void puct_end_kernel(ChessParams p) {
         }
     }
     if (lane == 0) {
-        if (p.search_no) p.search_no[gl] = (int32_t)(search_number(p, gl) + 1);
         p.out_move[gl] = (best >= 0 && !status) ? t.mv[base + best] : (uint16_t)0xFFFF;
-        zc_game_stats st{};
-        st.status = status;
-        st.expansions = ctl[cExp];
-        st.depth_sum = ctl[cDepth];
-        st.leaves = ctl[cReused] ? p.sims - 1 : p.sims;
-        p.out_stats[gl] = st;
-        ctl[cDone] = status == 0 ? 1 : 0;
+        search_done<PCtl>(p, ctl, gl, status);
     }
 }
 
@@ -834,7 +722,7 @@ void launch_chess_puct_reroot(const ChessParams &p, hipStream_t s) {
     hipLaunchKernelGGL(puct_reroot_kernel, dim3(p.n_games), dim3(64), 0, s, p);
 }
 void launch_chess_puct_forget(const ChessParams &p, hipStream_t s) {
-    hipLaunchKernelGGL(puct_forget_kernel, dim3((p.n_games + 63) / 64), dim3(64), 0, s, p);
+    launch_puct_forget(p.ca.ctl, p.first_game, p.n_games, PCtl::done, s);
 }
 void launch_chess_puct_select(const ChessParams &p, hipStream_t s) {
     hipLaunchKernelGGL(puct_select_kernel, dim3(p.n_games), dim3(64), 0, s, p);

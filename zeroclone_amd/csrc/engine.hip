@@ -71,6 +71,13 @@ void free_chess(zc::ChessArena &c) {
     c = zc::ChessArena{};
 }
 
+void free_c4p(zc::C4PuctArena &c) {
+    void *ptrs[] = {c.nodes, c.ctl, c.paths, c.meta, c.remap};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    c = zc::C4PuctArena{};
+}
+
 void free_gen(zc_engine *e) {
     zc::GenArena &g = e->ga;
     void *ptrs[] = {g.nodes, g.na, g.wa, g.qa, g.child, g.untried, g.ctl, g.pending};
@@ -292,12 +299,13 @@ int check_hp(const StepSearch &s, int32_t game, int32_t flush, int32_t leaf) {
     return ZC_OK;
 }
 
-// The frame of a step over games [first, first + n) of `search` (a zc_engine member): the
-// arguments (`cond`: the buffers n > 0 needs), the lock, the range and the flush, the device.
+// The frame of a step over games [first, first + n) of `search` (eng's record of it, evaluated
+// once eng is known not to be null): the arguments (`cond`: the buffers n > 0 needs), the
+// lock, the range and the flush, the device.
 #define ZC_STEP_ENTRY(search, flush, need_flush, cond)                                          \
     if (!eng || (n && !(cond))) return fail(ZC_EINVAL, "null argument");                        \
     std::lock_guard<std::mutex> lk(eng->mu);                                                    \
-    if (int r = check_step(eng->search, first, n, flush, need_flush)) return r;                 \
+    if (int r = check_step(search, first, n, flush, need_flush)) return r;                      \
     if (!n) return ZC_OK;                                                                       \
     ZC_HIP(hipSetDevice(eng->cfg.device));
 
@@ -400,9 +408,7 @@ int zc_engine_destroy(zc_engine *eng) {
         free_arena(eng);
         free_chess(eng->ca);
         free_gen(eng);
-        void *c4p[] = {eng->c4p_nodes, eng->c4p_ctl, eng->c4p_paths, eng->c4p_meta, eng->c4p_remap};
-        for (void *q : c4p)
-            if (q) (void)hipFree(q);
+        free_c4p(eng->c4p);
         give_stream(eng->cfg.device, eng->stream);
     }
     delete eng;
@@ -755,7 +761,7 @@ int zc_c4_ext_begin(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state 
 int zc_c4_ext_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, zc_c4_state *d_leaves, void *d_planes,
                      int32_t planes_dtype, int32_t *d_counts, void *hip_stream) {
     if (int r = check_planes_dtype(planes_dtype)) return r;
-    ZC_STEP_ENTRY(c4_value, flush, true, true)
+    ZC_STEP_ENTRY(eng->c4_value, flush, true, true)
     zc::ExtParams p = ext_params(eng, first, n);
     p.flush = flush;
     p.leaves = d_leaves;
@@ -769,7 +775,7 @@ int zc_c4_ext_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, zc
 
 int zc_c4_ext_backup(zc_engine *eng, int32_t first, int32_t n, int32_t flush, const double *d_values,
                      void *hip_stream) {
-    ZC_STEP_ENTRY(c4_value, flush, true, d_values)
+    ZC_STEP_ENTRY(eng->c4_value, flush, true, d_values)
     zc::ExtParams p = ext_params(eng, first, n);
     p.flush = flush;
     p.values = d_values;
@@ -780,7 +786,7 @@ int zc_c4_ext_backup(zc_engine *eng, int32_t first, int32_t n, int32_t flush, co
 
 int zc_c4_ext_end(zc_engine *eng, int32_t first, int32_t n, int32_t *d_move, int32_t *d_na, zc_game_stats *d_stats,
                   void *hip_stream) {
-    ZC_STEP_ENTRY(c4_value, 0, false, d_move && d_na && d_stats)
+    ZC_STEP_ENTRY(eng->c4_value, 0, false, d_move && d_na && d_stats)
     zc::ExtParams p = ext_params(eng, first, n);
     p.out_move = d_move;
     p.out_na = d_na;
@@ -1221,7 +1227,7 @@ int zc_chess_ext_begin(zc_engine *eng, int32_t first, int32_t n, const zc_chess_
 int zc_chess_ext_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, zc_chess_state *d_leaves,
                         void *d_planes, int32_t planes_dtype, int32_t *d_counts, void *hip_stream) {
     if (int r = check_planes_dtype(planes_dtype)) return r;
-    ZC_STEP_ENTRY(chess_value, flush, true, true)
+    ZC_STEP_ENTRY(eng->chess_value, flush, true, true)
     zc::ChessParams p = chess_value_params(eng, first, n);
     p.flush = flush;
     p.leaves = d_leaves;
@@ -1235,7 +1241,7 @@ int zc_chess_ext_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush,
 
 int zc_chess_ext_backup(zc_engine *eng, int32_t first, int32_t n, int32_t flush, const double *d_values,
                         void *hip_stream) {
-    ZC_STEP_ENTRY(chess_value, flush, true, d_values)
+    ZC_STEP_ENTRY(eng->chess_value, flush, true, d_values)
     zc::ChessParams p = chess_value_params(eng, first, n);
     p.flush = flush;
     p.values = d_values;
@@ -1246,7 +1252,7 @@ int zc_chess_ext_backup(zc_engine *eng, int32_t first, int32_t n, int32_t flush,
 
 int zc_chess_ext_end(zc_engine *eng, int32_t first, int32_t n, uint16_t *d_move, int32_t *d_na, zc_game_stats *d_stats,
                      void *hip_stream) {
-    ZC_STEP_ENTRY(chess_value, 0, false, d_move && d_na && d_stats)
+    ZC_STEP_ENTRY(eng->chess_value, 0, false, d_move && d_na && d_stats)
     zc::ChessParams p = chess_value_params(eng, first, n);
     p.out_move = d_move;
     p.out_na = d_na;
@@ -1316,7 +1322,7 @@ int zc_chess_ext_rollouts(zc_engine *eng, int32_t first, int32_t n, int32_t flus
                           const int32_t *d_hist_len, int32_t hist_cap, double *d_values, int32_t *d_status,
                           void *hip_stream) {
     if (hist_cap < 1) return fail(ZC_EINVAL, "hist_cap must be >= 1");
-    ZC_STEP_ENTRY(chess_value, flush, true, d_hist && d_hist_len && d_values)
+    ZC_STEP_ENTRY(eng->chess_value, flush, true, d_hist && d_hist_len && d_values)
     zc::ChessParams p = chess_value_params(eng, first, n);
     p.flush = flush;
     p.rhist = d_hist;
@@ -1331,7 +1337,7 @@ int zc_chess_ext_rollouts(zc_engine *eng, int32_t first, int32_t n, int32_t flus
 
 int zc_chess_ext_leaf_moves(zc_engine *eng, int32_t first, int32_t n, int32_t flush, uint16_t *d_moves,
                             int32_t *d_depth, void *hip_stream) {
-    ZC_STEP_ENTRY(chess_value, flush, true, d_moves && d_depth)
+    ZC_STEP_ENTRY(eng->chess_value, flush, true, d_moves && d_depth)
     zc::ChessParams p = chess_value_params(eng, first, n);
     p.flush = flush;
     p.path_moves = d_moves;
@@ -1341,7 +1347,7 @@ int zc_chess_ext_leaf_moves(zc_engine *eng, int32_t first, int32_t n, int32_t fl
     return ZC_OK;
 }
 
-// ---------------------------------------------------------------- chess PUCT search
+// ---------------------------------------------------------------- PUCT searches (chess, Connect4)
 int zc_chess_puct_flushes(int32_t sims, int32_t bs) {
     if (sims < 2 || bs < 1) return fail(ZC_EINVAL, "PUCT search needs sims >= 2 and batch_size >= 1");
     return puct_flushes(sims, bs);
@@ -1350,26 +1356,20 @@ int zc_chess_puct_flushes(int32_t sims, int32_t bs) {
 }  // extern "C"
 
 namespace {
-// What zc_chess_puct_begin and zc_c4_puct_begin(_reuse) share: the checks, and the search
-// recorded in *s, a copy of the engine's that the caller stores back once its arena exists.
-int puct_begin(const zc_engine *eng, int32_t first, int32_t n, const void *d_roots, int32_t sims, double c_puct,
-               int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no, PuctSearch *s) {
-    if (n && !d_roots) return fail(ZC_EINVAL, "null argument");
-    if (int r = check_search(eng, first, n, sims, c_puct, bs)) return r;
-    if (sims < 2) return fail(ZC_EINVAL, "PUCT search needs sims >= 2 (flush 0 evaluates the root)");
-    if (!(alpha > 0.0f) || !(eps >= 0.0f && eps <= 1.0f)) return fail(ZC_EINVAL, "need alpha > 0 and 0 <= eps <= 1");
-    set_step(*s, first, n, sims, c_puct, bs, puct_flushes(sims, bs));
-    s->alpha = alpha;
-    s->eps = eps;
-    s->seed = seed;
-    s->search_no = d_search_no;
-    return ZC_OK;
-}
-
-int check_puct_backup(int32_t flush, int32_t logits_dtype, int32_t rows_per_game) {
-    if (logits_dtype != ZC_F32 && logits_dtype != ZC_F16) return fail(ZC_EINVAL, "logits_dtype must be ZC_F32 or ZC_F16");
-    if (rows_per_game < 0 || (rows_per_game > 0 && flush != 0))
-        return fail(ZC_EINVAL, "rows_per_game must be 0 (batch_size rows), or >= 1 for flush 0 (the roots)");
+int ensure_c4p(zc_engine *e) {
+    if (e->c4p.nodes) return ZC_OK;
+    const size_t G = (size_t)e->cfg.max_games, M = (size_t)e->M;
+    zc::C4PuctArena n{};
+    int rc = dalloc(e, &n.nodes, G * M);
+    if (!rc) rc = dalloc(e, &n.ctl, G * zc::kCtlWords);
+    if (!rc) rc = dalloc(e, &n.paths, G * (size_t)e->cfg.max_batch * zc::kMaxDepth);
+    if (!rc) rc = dalloc(e, &n.meta, G * (size_t)e->cfg.max_batch);
+    if (!rc && hipMemset(n.ctl, 0, G * zc::kCtlWords * sizeof(int32_t)) != hipSuccess) rc = fail(ZC_EHIP, "memset failed");
+    if (rc) {
+        free_c4p(n);
+        return rc;
+    }
+    e->c4p = n;
     return ZC_OK;
 }
 
@@ -1379,43 +1379,172 @@ int32_t *search_no_at(const PuctSearch &s, int32_t first) {
     return s.search_no ? s.search_no + (first - s.first) : nullptr;
 }
 
-zc::ChessParams puct_params(zc_engine *e, int32_t first, int32_t n) {
-    const PuctSearch &s = e->chess_puct;
-    zc::ChessParams p = chess_params(e, first, n, s.sims, s.c, s.bs, 0, 0.0);
-    p.dir_alpha = s.alpha;
-    p.dir_eps = s.eps;
-    p.seed = s.seed;
-    p.search_no = search_no_at(s, first);
-    return p;
-}
+// The two games of the PUCT search, as the steps below need them: the engine's record of the
+// search, the arena (`ensure`: with the re-root's scratch for a begin_reuse), the kernel
+// parameters of a step over games [first, first + n), the planes formats of select
+// (ZC_EINVAL, or the kernel's code in *fmt) and the launchers.
+struct ChessPuct {
+    using State = zc_chess_state;
+    using Move = uint16_t;
+    static PuctSearch &search(zc_engine *e) { return e->chess_puct; }
+    static bool has_tree(const zc_engine *e) { return e->ca.nodes != nullptr; }
+    static int ensure(zc_engine *e, bool reuse) {
+        if (int r = ensure_chess(e)) return r;
+        const size_t GM = (size_t)e->cfg.max_games * (size_t)e->M;
+        if (reuse && !e->ca.remap)
+            if (int r = dalloc(e, &e->ca.remap, GM)) return r;
+        if (reuse && !e->ca.rbase)
+            if (int r = dalloc(e, &e->ca.rbase, GM)) return r;
+        return ZC_OK;
+    }
+    static zc::ChessParams params(zc_engine *e, int32_t first, int32_t n) {
+        const PuctSearch &s = e->chess_puct;
+        zc::ChessParams p = chess_params(e, first, n, s.sims, s.c, s.bs, 0, 0.0);
+        p.dir_alpha = s.alpha;
+        p.dir_eps = s.eps;
+        p.seed = s.seed;
+        p.search_no = search_no_at(s, first);
+        return p;
+    }
+    static int planes_format(int32_t dtype, int *fmt) {
+        if (dtype != ZC_F32 && dtype != ZC_F16 && dtype != ZC_F16_NHWC32)
+            return fail(ZC_EINVAL, "planes_dtype must be ZC_F32, ZC_F16 or ZC_F16_NHWC32");
+        *fmt = dtype == ZC_F16 ? 1 : dtype == ZC_F16_NHWC32 ? 2 : 0;
+        return ZC_OK;
+    }
+    static constexpr auto begin = zc::launch_chess_puct_begin, reroot = zc::launch_chess_puct_reroot,
+                          forget = zc::launch_chess_puct_forget, select = zc::launch_chess_puct_select,
+                          backup = zc::launch_chess_puct_backup, end = zc::launch_chess_puct_end;
+};
 
-// zc_chess_puct_begin / zc_chess_puct_begin_reuse: the same validation and search parameters;
-// the reuse form launches the re-root kernel in place of the begin kernel.
-int chess_puct_begin(zc_engine *eng, int32_t first, int32_t n, const zc_chess_state *d_roots, int32_t sims,
-                     double c_puct, int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no, bool reuse,
-                     int32_t *d_kept, void *hip_stream) {
+struct C4Puct {
+    using State = zc_c4_state;
+    using Move = int32_t;
+    static PuctSearch &search(zc_engine *e) { return e->c4_puct; }
+    static bool has_tree(const zc_engine *e) { return e->c4p.nodes != nullptr; }
+    static int ensure(zc_engine *e, bool reuse) {
+        if (int r = ensure_c4p(e)) return r;
+        if (reuse && !e->c4p.remap) return dalloc(e, &e->c4p.remap, (size_t)e->cfg.max_games * (size_t)e->M);
+        return ZC_OK;
+    }
+    static zc::C4PuctParams params(zc_engine *e, int32_t first, int32_t n) {
+        const PuctSearch &s = e->c4_puct;
+        zc::C4PuctParams p{};
+        p.first_game = first;
+        p.n_games = n;
+        p.sims = s.sims;
+        p.bs = s.bs;
+        p.M = e->M;
+        p.max_batch = e->cfg.max_batch;
+        p.c = s.c;
+        p.nodes = e->c4p.nodes;
+        p.ctl = e->c4p.ctl;
+        p.paths = e->c4p.paths;
+        p.meta = e->c4p.meta;
+        p.remap = e->c4p.remap;
+        p.dir_alpha = s.alpha;
+        p.dir_eps = s.eps;
+        p.seed = s.seed;
+        p.search_no = search_no_at(s, first);
+        return p;
+    }
+    static int planes_format(int32_t dtype, int *fmt) {
+        *fmt = dtype == ZC_F16;
+        return check_planes_dtype(dtype);
+    }
+    static constexpr auto begin = zc::launch_c4_puct_begin, reroot = zc::launch_c4_puct_reroot,
+                          forget = zc::launch_c4_puct_forget, select = zc::launch_c4_puct_select,
+                          backup = zc::launch_c4_puct_backup, end = zc::launch_c4_puct_end;
+};
+
+// begin / begin_reuse: the same validation and search parameters; the reuse form launches the
+// re-root kernel in place of the begin kernel.  The search is recorded once its arena exists.
+template <class G>
+int puct_begin(zc_engine *eng, int32_t first, int32_t n, const typename G::State *d_roots, int32_t sims, double c_puct,
+               int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no, bool reuse, int32_t *d_kept,
+               void *hip_stream) {
     if (!eng) return fail(ZC_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(eng->mu);
-    PuctSearch s = eng->chess_puct;
-    if (int r = puct_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, &s)) return r;
+    if (n && !d_roots) return fail(ZC_EINVAL, "null argument");
+    if (int r = check_search(eng, first, n, sims, c_puct, bs)) return r;
+    if (sims < 2) return fail(ZC_EINVAL, "PUCT search needs sims >= 2 (flush 0 evaluates the root)");
+    if (!(alpha > 0.0f) || !(eps >= 0.0f && eps <= 1.0f)) return fail(ZC_EINVAL, "need alpha > 0 and 0 <= eps <= 1");
     ZC_HIP(hipSetDevice(eng->cfg.device));
-    if (int r = ensure_chess(eng)) return r;
-    if (reuse && !eng->ca.rbase) {  // the re-root's scratch, with the arena from now on
-        const size_t GM = (size_t)eng->cfg.max_games * (size_t)eng->M;
-        if (!eng->ca.remap)
-            if (int r = dalloc(eng, &eng->ca.remap, GM)) return r;
-        if (int r = dalloc(eng, &eng->ca.rbase, GM)) return r;
-    }
-    eng->chess_puct = s;
+    if (int r = G::ensure(eng, reuse)) return r;
+    PuctSearch &s = G::search(eng);
+    set_step(s, first, n, sims, c_puct, bs, puct_flushes(sims, bs));
+    s.alpha = alpha;
+    s.eps = eps;
+    s.seed = seed;
+    s.search_no = d_search_no;
     if (!n) return ZC_OK;
-    zc::ChessParams p = puct_params(eng, first, n);
+    auto p = G::params(eng, first, n);
     p.roots = d_roots;
-    if (reuse) {
-        p.out_kept = d_kept;
-        zc::launch_chess_puct_reroot(p, (hipStream_t)hip_stream);
-    } else {
-        zc::launch_chess_puct_begin(p, (hipStream_t)hip_stream);
-    }
+    p.out_kept = reuse ? d_kept : nullptr;
+    (reuse ? G::reroot : G::begin)(p, (hipStream_t)hip_stream);
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+
+template <class G>
+int puct_forget(zc_engine *eng, int32_t first, int32_t n, void *hip_stream) {
+    if (!eng) return fail(ZC_EINVAL, "null argument");
+    if (int r = check_games(eng, first, n)) return r;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    if (!n || !G::has_tree(eng)) return ZC_OK;  // no tree yet: nothing is kept
+    ZC_HIP(hipSetDevice(eng->cfg.device));
+    G::forget(G::params(eng, first, n), (hipStream_t)hip_stream);
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+
+template <class G>
+int puct_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, typename G::State *d_leaves, void *d_planes,
+                int32_t planes_dtype, int32_t *d_counts, void *hip_stream) {
+    int fmt = 0;
+    if (int r = G::planes_format(planes_dtype, &fmt)) return r;
+    ZC_STEP_ENTRY(G::search(eng), flush, true, true)
+    auto p = G::params(eng, first, n);
+    p.flush = flush;
+    p.leaves = d_leaves;
+    p.planes = d_planes;
+    p.planes_f16 = fmt;
+    p.counts = d_counts;
+    G::select(p, (hipStream_t)hip_stream);
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+
+template <class G>
+int puct_backup(zc_engine *eng, int32_t first, int32_t n, int32_t flush, const double *d_values, const void *d_logits,
+                int32_t logits_dtype, int32_t rows_per_game, void *hip_stream) {
+    if (logits_dtype != ZC_F32 && logits_dtype != ZC_F16) return fail(ZC_EINVAL, "logits_dtype must be ZC_F32 or ZC_F16");
+    if (rows_per_game < 0 || (rows_per_game > 0 && flush != 0))
+        return fail(ZC_EINVAL, "rows_per_game must be 0 (batch_size rows), or >= 1 for flush 0 (the roots)");
+    ZC_STEP_ENTRY(G::search(eng), flush, true, d_values && d_logits)
+    auto p = G::params(eng, first, n);
+    p.flush = flush;
+    p.values = d_values;
+    p.logits = d_logits;
+    p.logits_f16 = logits_dtype == ZC_F16;
+    p.leaf_rows = rows_per_game;
+    G::backup(p, (hipStream_t)hip_stream);
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+
+template <class G>
+int puct_end(zc_engine *eng, int32_t first, int32_t n, float temperature, typename G::Move *d_move, int32_t *d_na,
+             float *d_prior, zc_game_stats *d_stats, void *hip_stream) {
+    if (!(temperature >= 0.0f)) return fail(ZC_EINVAL, "temperature must be >= 0");
+    ZC_STEP_ENTRY(G::search(eng), 0, false, d_move && d_na && d_stats)
+    auto p = G::params(eng, first, n);
+    p.temperature = temperature;
+    p.out_move = d_move;
+    p.out_na = d_na;
+    p.out_prior = d_prior;
+    p.out_stats = d_stats;
+    G::end(p, (hipStream_t)hip_stream);
     ZC_HIP(hipGetLastError());
     return ZC_OK;
 }
@@ -1426,234 +1555,65 @@ extern "C" {
 int zc_chess_puct_begin(zc_engine *eng, int32_t first, int32_t n, const zc_chess_state *d_roots, int32_t sims,
                         double c_puct, int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no,
                         void *hip_stream) {
-    return chess_puct_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, false, nullptr,
-                            hip_stream);
+    return puct_begin<ChessPuct>(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, false,
+                                 nullptr, hip_stream);
 }
-
 int zc_chess_puct_begin_reuse(zc_engine *eng, int32_t first, int32_t n, const zc_chess_state *d_roots, int32_t sims,
                               double c_puct, int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no,
                               int32_t *d_kept, void *hip_stream) {
-    return chess_puct_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, true, d_kept,
-                            hip_stream);
+    return puct_begin<ChessPuct>(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, true, d_kept,
+                                 hip_stream);
 }
-
 int zc_chess_puct_forget(zc_engine *eng, int32_t first, int32_t n, void *hip_stream) {
-    if (!eng) return fail(ZC_EINVAL, "null argument");
-    if (int r = check_games(eng, first, n)) return r;
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (!n || !eng->ca.nodes) return ZC_OK;  // no tree yet: nothing is kept
-    ZC_HIP(hipSetDevice(eng->cfg.device));
-    zc::ChessParams p{};
-    p.first_game = first;
-    p.n_games = n;
-    p.ca = eng->ca;
-    zc::launch_chess_puct_forget(p, (hipStream_t)hip_stream);
-    ZC_HIP(hipGetLastError());
-    return ZC_OK;
+    return puct_forget<ChessPuct>(eng, first, n, hip_stream);
 }
-
 int zc_chess_puct_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, zc_chess_state *d_leaves,
                          void *d_planes, int32_t planes_dtype, int32_t *d_counts, void *hip_stream) {
-    if (planes_dtype != ZC_F32 && planes_dtype != ZC_F16 && planes_dtype != ZC_F16_NHWC32)
-        return fail(ZC_EINVAL, "planes_dtype must be ZC_F32, ZC_F16 or ZC_F16_NHWC32");
-    ZC_STEP_ENTRY(chess_puct, flush, true, true)
-    zc::ChessParams p = puct_params(eng, first, n);
-    p.flush = flush;
-    p.leaves = d_leaves;
-    p.planes = d_planes;
-    p.planes_f16 = planes_dtype == ZC_F16 ? 1 : planes_dtype == ZC_F16_NHWC32 ? 2 : 0;
-    p.counts = d_counts;
-    zc::launch_chess_puct_select(p, (hipStream_t)hip_stream);
-    ZC_HIP(hipGetLastError());
-    return ZC_OK;
+    return puct_select<ChessPuct>(eng, first, n, flush, d_leaves, d_planes, planes_dtype, d_counts, hip_stream);
 }
-
 int zc_chess_puct_backup_ex(zc_engine *eng, int32_t first, int32_t n, int32_t flush, const double *d_values,
                             const void *d_logits, int32_t logits_dtype, int32_t rows_per_game, void *hip_stream) {
-    if (int r = check_puct_backup(flush, logits_dtype, rows_per_game)) return r;
-    ZC_STEP_ENTRY(chess_puct, flush, true, d_values && d_logits)
-    zc::ChessParams p = puct_params(eng, first, n);
-    p.flush = flush;
-    p.values = d_values;
-    p.logits = d_logits;
-    p.logits_f16 = logits_dtype == ZC_F16;
-    p.leaf_rows = rows_per_game;
-    zc::launch_chess_puct_backup(p, (hipStream_t)hip_stream);
-    ZC_HIP(hipGetLastError());
-    return ZC_OK;
+    return puct_backup<ChessPuct>(eng, first, n, flush, d_values, d_logits, logits_dtype, rows_per_game, hip_stream);
 }
-
 int zc_chess_puct_backup(zc_engine *eng, int32_t first, int32_t n, int32_t flush, const double *d_values,
                          const void *d_logits, int32_t logits_dtype, void *hip_stream) {
-    return zc_chess_puct_backup_ex(eng, first, n, flush, d_values, d_logits, logits_dtype, 0, hip_stream);
+    return puct_backup<ChessPuct>(eng, first, n, flush, d_values, d_logits, logits_dtype, 0, hip_stream);
 }
-
 int zc_chess_puct_end(zc_engine *eng, int32_t first, int32_t n, float temperature, uint16_t *d_move, int32_t *d_na,
                       float *d_prior, zc_game_stats *d_stats, void *hip_stream) {
-    if (!(temperature >= 0.0f)) return fail(ZC_EINVAL, "temperature must be >= 0");
-    ZC_STEP_ENTRY(chess_puct, 0, false, d_move && d_na && d_stats)
-    zc::ChessParams p = puct_params(eng, first, n);
-    p.temperature = temperature;
-    p.out_move = d_move;
-    p.out_na = d_na;
-    p.out_prior = d_prior;
-    p.out_stats = d_stats;
-    zc::launch_chess_puct_end(p, (hipStream_t)hip_stream);
-    ZC_HIP(hipGetLastError());
-    return ZC_OK;
+    return puct_end<ChessPuct>(eng, first, n, temperature, d_move, d_na, d_prior, d_stats, hip_stream);
 }
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- Connect4 PUCT search
-namespace {
-int ensure_c4p(zc_engine *e) {
-    if (e->c4p_nodes) return ZC_OK;
-    const size_t G = (size_t)e->cfg.max_games, M = (size_t)e->M;
-    int rc = dalloc(e, &e->c4p_nodes, G * M);
-    if (!rc) rc = dalloc(e, &e->c4p_ctl, G * zc::kCtlWords);
-    if (!rc) rc = dalloc(e, &e->c4p_paths, G * (size_t)e->cfg.max_batch * zc::kMaxDepth);
-    if (!rc) rc = dalloc(e, &e->c4p_meta, G * (size_t)e->cfg.max_batch);
-    if (!rc && hipMemset(e->c4p_ctl, 0, G * zc::kCtlWords * sizeof(int32_t)) != hipSuccess)
-        rc = fail(ZC_EHIP, "memset failed");
-    if (rc) {
-        void *q[] = {e->c4p_nodes, e->c4p_ctl, e->c4p_paths, e->c4p_meta};
-        for (void *x : q)
-            if (x) (void)hipFree(x);
-        e->c4p_nodes = nullptr;
-        e->c4p_ctl = nullptr;
-        e->c4p_paths = e->c4p_meta = nullptr;
-    }
-    return rc;
-}
-zc::C4PuctParams c4p_params(zc_engine *e, int32_t first, int32_t n) {
-    const PuctSearch &s = e->c4_puct;
-    zc::C4PuctParams p{};
-    p.first_game = first;
-    p.n_games = n;
-    p.sims = s.sims;
-    p.bs = s.bs;
-    p.M = e->M;
-    p.max_batch = e->cfg.max_batch;
-    p.c = s.c;
-    p.nodes = e->c4p_nodes;
-    p.ctl = e->c4p_ctl;
-    p.paths = e->c4p_paths;
-    p.meta = e->c4p_meta;
-    p.dir_alpha = s.alpha;
-    p.dir_eps = s.eps;
-    p.seed = s.seed;
-    p.search_no = search_no_at(s, first);
-    return p;
-}
-// zc_c4_puct_begin / zc_c4_puct_begin_reuse: the same validation and search parameters; the
-// reuse form launches the re-root kernel in place of the begin kernel.
-int c4p_begin(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state *d_roots, int32_t sims, double c_puct,
-              int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no, bool reuse, int32_t *d_kept,
-              void *hip_stream) {
-    if (!eng) return fail(ZC_EINVAL, "null argument");
-    std::lock_guard<std::mutex> lk(eng->mu);
-    PuctSearch s = eng->c4_puct;
-    if (int r = puct_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, &s)) return r;
-    ZC_HIP(hipSetDevice(eng->cfg.device));
-    if (int r = ensure_c4p(eng)) return r;
-    if (reuse && !eng->c4p_remap)
-        if (int r = dalloc(eng, &eng->c4p_remap, (size_t)eng->cfg.max_games * (size_t)eng->M)) return r;
-    eng->c4_puct = s;
-    if (!n) return ZC_OK;
-    zc::C4PuctParams p = c4p_params(eng, first, n);
-    p.roots = d_roots;
-    if (reuse) {
-        p.remap = eng->c4p_remap;
-        p.out_kept = d_kept;
-        zc::launch_c4_puct_reroot(p, (hipStream_t)hip_stream);
-    } else {
-        zc::launch_c4_puct_begin(p, (hipStream_t)hip_stream);
-    }
-    ZC_HIP(hipGetLastError());
-    return ZC_OK;
-}
-}  // namespace
-
-extern "C" {
 
 int zc_c4_puct_begin(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state *d_roots, int32_t sims,
                      double c_puct, int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no,
                      void *hip_stream) {
-    return c4p_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, false, nullptr,
-                     hip_stream);
+    return puct_begin<C4Puct>(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, false, nullptr,
+                              hip_stream);
 }
-
 int zc_c4_puct_begin_reuse(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state *d_roots, int32_t sims,
                            double c_puct, int32_t bs, float alpha, float eps, uint64_t seed, int32_t *d_search_no,
                            int32_t *d_kept, void *hip_stream) {
-    return c4p_begin(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, true, d_kept,
-                     hip_stream);
+    return puct_begin<C4Puct>(eng, first, n, d_roots, sims, c_puct, bs, alpha, eps, seed, d_search_no, true, d_kept,
+                              hip_stream);
 }
-
 int zc_c4_puct_forget(zc_engine *eng, int32_t first, int32_t n, void *hip_stream) {
-    if (!eng) return fail(ZC_EINVAL, "null argument");
-    if (int r = check_games(eng, first, n)) return r;
-    std::lock_guard<std::mutex> lk(eng->mu);
-    if (!n || !eng->c4p_nodes) return ZC_OK;  // no tree yet: nothing is kept
-    ZC_HIP(hipSetDevice(eng->cfg.device));
-    zc::C4PuctParams p{};
-    p.first_game = first;
-    p.n_games = n;
-    p.ctl = eng->c4p_ctl;
-    zc::launch_c4_puct_forget(p, (hipStream_t)hip_stream);
-    ZC_HIP(hipGetLastError());
-    return ZC_OK;
+    return puct_forget<C4Puct>(eng, first, n, hip_stream);
 }
-
 int zc_c4_puct_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, zc_c4_state *d_leaves, void *d_planes,
                       int32_t planes_dtype, int32_t *d_counts, void *hip_stream) {
-    if (int r = check_planes_dtype(planes_dtype)) return r;
-    ZC_STEP_ENTRY(c4_puct, flush, true, true)
-    zc::C4PuctParams p = c4p_params(eng, first, n);
-    p.flush = flush;
-    p.leaves = d_leaves;
-    p.planes = d_planes;
-    p.planes_f16 = planes_dtype == ZC_F16;
-    p.counts = d_counts;
-    zc::launch_c4_puct_select(p, (hipStream_t)hip_stream);
-    ZC_HIP(hipGetLastError());
-    return ZC_OK;
+    return puct_select<C4Puct>(eng, first, n, flush, d_leaves, d_planes, planes_dtype, d_counts, hip_stream);
 }
-
 int zc_c4_puct_backup_ex(zc_engine *eng, int32_t first, int32_t n, int32_t flush, const double *d_values,
                          const void *d_logits, int32_t logits_dtype, int32_t rows_per_game, void *hip_stream) {
-    if (int r = check_puct_backup(flush, logits_dtype, rows_per_game)) return r;
-    ZC_STEP_ENTRY(c4_puct, flush, true, d_values && d_logits)
-    zc::C4PuctParams p = c4p_params(eng, first, n);
-    p.flush = flush;
-    p.values = d_values;
-    p.logits = d_logits;
-    p.logits_f16 = logits_dtype == ZC_F16;
-    p.leaf_rows = rows_per_game;
-    zc::launch_c4_puct_backup(p, (hipStream_t)hip_stream);
-    ZC_HIP(hipGetLastError());
-    return ZC_OK;
+    return puct_backup<C4Puct>(eng, first, n, flush, d_values, d_logits, logits_dtype, rows_per_game, hip_stream);
 }
-
 int zc_c4_puct_backup(zc_engine *eng, int32_t first, int32_t n, int32_t flush, const double *d_values,
                       const void *d_logits, int32_t logits_dtype, void *hip_stream) {
-    return zc_c4_puct_backup_ex(eng, first, n, flush, d_values, d_logits, logits_dtype, 0, hip_stream);
+    return puct_backup<C4Puct>(eng, first, n, flush, d_values, d_logits, logits_dtype, 0, hip_stream);
 }
-
 int zc_c4_puct_end(zc_engine *eng, int32_t first, int32_t n, float temperature, int32_t *d_move, int32_t *d_na,
                    float *d_prior, zc_game_stats *d_stats, void *hip_stream) {
-    if (!(temperature >= 0.0f)) return fail(ZC_EINVAL, "temperature must be >= 0");
-    ZC_STEP_ENTRY(c4_puct, 0, false, d_move && d_na && d_stats)
-    zc::C4PuctParams p = c4p_params(eng, first, n);
-    p.temperature = temperature;
-    p.out_move = d_move;
-    p.out_na = d_na;
-    p.out_prior = d_prior;
-    p.out_stats = d_stats;
-    zc::launch_c4_puct_end(p, (hipStream_t)hip_stream);
-    ZC_HIP(hipGetLastError());
-    return ZC_OK;
+    return puct_end<C4Puct>(eng, first, n, temperature, d_move, d_na, d_prior, d_stats, hip_stream);
 }
 #undef ZC_STEP_ENTRY
 
@@ -1662,12 +1622,13 @@ int zc_debug_c4_puct_tree(zc_engine *eng, int32_t game, int32_t max_nodes, void 
     if (int r = check_games(eng, game, 1)) return r;
     std::lock_guard<std::mutex> lk(eng->mu);
     ZC_HIP(hipSetDevice(eng->cfg.device));
-    if (!eng->c4p_nodes) return fail(ZC_EINVAL, "no Connect4 PUCT tree (no PUCT search has run)");
+    const zc::C4PuctArena &c = eng->c4p;
+    if (!c.nodes) return fail(ZC_EINVAL, "no Connect4 PUCT tree (no PUCT search has run)");
     ZC_HIP(hipDeviceSynchronize());
     int32_t nn = 0;
-    ZC_HIP(hipMemcpy(&nn, eng->c4p_ctl + (size_t)game * zc::kCtlWords, sizeof nn, hipMemcpyDeviceToHost));
+    ZC_HIP(hipMemcpy(&nn, c.ctl + (size_t)game * zc::kCtlWords, sizeof nn, hipMemcpyDeviceToHost));
     if (nn > max_nodes) return fail(ZC_ECAPACITY, "tree has %d nodes (buffer: %d)", nn, max_nodes);
-    ZC_HIP(hipMemcpy(out_nodes, eng->c4p_nodes + (size_t)game * eng->M, (size_t)nn * sizeof(zc::C4PNode),
+    ZC_HIP(hipMemcpy(out_nodes, c.nodes + (size_t)game * eng->M, (size_t)nn * sizeof(zc::C4PNode),
                      hipMemcpyDeviceToHost));
     *out_count = nn;
     return ZC_OK;

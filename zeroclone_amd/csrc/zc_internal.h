@@ -243,6 +243,14 @@ struct C4PNode {
     uint8_t pad1[16];
 };
 
+struct C4PuctArena {
+    C4PNode *nodes = nullptr;   // [G][M]
+    int32_t *ctl = nullptr;     // [G][kCtlWords]
+    uint32_t *paths = nullptr;  // [G][max_batch][kMaxDepth]
+    uint32_t *meta = nullptr;   // [G][max_batch]
+    uint16_t *remap = nullptr;  // [G][M] the re-root's scratch, allocated on the first zc_c4_puct_begin_reuse
+};
+
 struct C4PuctParams {
     int first_game, n_games, sims, bs, M, max_batch, flush;
     double c;                 // c_puct
@@ -428,11 +436,7 @@ struct zc_engine {
     uint64_t rollout_seed = 0;
     int carry_lo = 0, carry_hi = 0;  // games that may hold a carried self-play move (engine.hip check_carry)
     zc::ChessArena ca;  // allocated on the first chess search
-    // the Connect4 PUCT tree (allocated on the first zc_c4_puct_begin)
-    zc::C4PNode *c4p_nodes = nullptr;
-    int32_t *c4p_ctl = nullptr;
-    uint32_t *c4p_paths = nullptr, *c4p_meta = nullptr;
-    uint16_t *c4p_remap = nullptr;  // [G][M], allocated on the first zc_c4_puct_begin_reuse
+    zc::C4PuctArena c4p;  // allocated on the first zc_c4_puct_begin
     // A stepwise search in progress (begin .. end), as its begin call gave it: the entry points'
     // prefix (for messages), the games [first, first + n), the search parameters and the
     // number of flushes they make (engine.hip check_step).
