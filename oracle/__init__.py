@@ -340,6 +340,14 @@ def chess_get_move(s: ZccState, mt: MT, sims: int, c: float, bs: int, policy: st
     return best, moves, list(na[:n.value])
 
 
+def chess_last_tree():
+    """The tree the calling thread's last chess_get_move built: (nodes, the legal moves of its
+    expanded nodes summed, the level of its deepest node)."""
+    n, s, d = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    _chess_lib().zcc_last_tree(ctypes.byref(n), ctypes.byref(s), ctypes.byref(d))
+    return n.value, s.value, d.value
+
+
 def chess_selfplay_batch(rows, mts: list["MT"], moves: int, sims: int, c: float = 1.4, bs: int = 32,
                          policy: str = "immediate_value", freedom: float = 3.0, threads: int = 1):
     """zcc_selfplay_batch: crude-score self-play, each game `moves` moves (search, play, judge,

@@ -482,6 +482,17 @@ static void cbackprop(cnode *P, int node, double v) {   /* mcts.cpp:80-100 */
 }
 
 static __thread int t_chess_nodes;   /* nodes the calling thread's last zcc_get_move created */
+static __thread int t_chess_slots;   /* ... the legal moves of those it expanded at least once, summed */
+static __thread int t_chess_depth;   /* ... and the level of its deepest node (the root is level 0) */
+
+/* Shape of the tree the calling thread's last zcc_get_move built: what a search that stores
+ * uint16 node ids, one child slot per legal move of an expanded node and a bounded path has
+ * to hold. */
+void zcc_last_tree(int *nodes, int *slots, int *depth) {
+    if (nodes) *nodes = t_chess_nodes;
+    if (slots) *slots = t_chess_slots;
+    if (depth) *depth = t_chess_depth;
+}
 
 int zcc_get_move(const zcc_light *root, void *rv, int sims, double c, int bs, int policy, double freedom,
                  zcc_value_fn vfn, void *ctx, int *root_na, zcc_move *root_moves, int *n_root) {
@@ -520,6 +531,12 @@ int zcc_get_move(const zcc_light *root, void *rv, int sims, double c, int bs, in
         if (root_moves) root_moves[i] = P[0].mv[i];
     }
     t_chess_nodes = np;
+    t_chess_slots = t_chess_depth = 0;
+    for (int i = 0; i < np; i++) {   /* a parent precedes its children: pact holds the level from here on */
+        P[i].pact = P[i].parent < 0 ? 0 : P[P[i].parent].pact + 1;
+        if (P[i].pact > t_chess_depth) t_chess_depth = P[i].pact;
+        if (P[i].nu < P[i].n) t_chess_slots += P[i].n;
+    }
     for (int i = 0; i < np; i++) {
         free(P[i].mv);
         free(P[i].untried);

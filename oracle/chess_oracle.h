@@ -52,6 +52,9 @@ double   zcc_crude_score(const zcc_light *l);
 typedef void (*zcc_value_fn)(void *ctx, int n, const zcc_light *leaves, double *out);
 int      zcc_get_move(const zcc_light *root, void *r, int sims, double c, int bs, int policy, double freedom,
                       zcc_value_fn vfn, void *ctx, int *root_na, zcc_move *root_moves, int *n_root);
+/* the tree the calling thread's last zcc_get_move built: its nodes, the legal moves of the
+ * nodes it expanded (summed) and the level of its deepest node (root = 0) */
+void     zcc_last_tree(int *nodes, int *slots, int *depth);
 /* crude-score self-play of n games from roots on their streams (bench.py's CPU baseline) */
 int      zcc_selfplay_batch(int n, const zcc_light *roots, void *mts, int moves, int sims, double c, int bs, int policy,
                             double freedom, int n_threads, uint64_t *out_expansions);

@@ -60,7 +60,19 @@ def test_state_to_tensor(golden):
 
 def test_chess_search_matches_reference(golden):
     """Chess get_move (crude_chess_score, immediate_value / random policy) vs the reference."""
-    for case in golden("chess_get_move.json")["cases"]:
+    _check_get_move(golden("chess_get_move.json")["cases"])
+
+
+def test_chess_search_at_the_engine_limits(golden):
+    """The reference at the limits the engine declares (tests/golden/gen_golden_limits.py):
+    flushes of 129 and 256 leaves, and 65533 simulations, where node ids pass 15 bits."""
+    cases = golden("chess_get_move_limits.json")["cases"]
+    assert {(c["sims"], c["bs"]) for c in cases} >= {(400, 129), (400, 256), (65533, 64), (65533, 256)}
+    _check_get_move(cases)
+
+
+def _check_get_move(cases):
+    for case in cases:
         s = oracle.chess_from_fen(case["fen"])
         mt = oracle.MT(case["seed"])
         best, moves, na = oracle.chess_get_move(s, mt, case["sims"], case["c"], case["bs"], case["policy"],

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import oracle
+from c4_positions import deep_leaning_roots, opening
 
 pytestmark = pytest.mark.gpu
 
@@ -160,14 +161,7 @@ def test_full_size_batch_matches_oracle(eng):
     """C2 shape: 4096 games x 800 sims, bs 32 — every game compared with the oracle."""
     n, sims = 4096, 800
     rng = random.Random(11)
-    boards = []
-    for g in range(n):
-        b, t = "." * 42, 0
-        for _ in range(rng.randint(0, 6)):
-            legal = [col for col in range(7) if b[col] == "."]
-            b, t = oracle.play(b, t, rng.choice(legal))
-        boards.append((b, t))
-    # drop positions that are already won (still legal for get_move, but keep the mix simple)
+    boards = [opening(rng, 6) for _ in range(n)]
     seeds = [1_000_003 * g + 17 for g in range(n)]
     eng.seed(0, seeds)
     from zeroclone_amd._native import C4_STATE_DTYPE
@@ -190,21 +184,7 @@ def test_planned_flush_deep_roots_match_oracle(eng, bs):
     flush's leaves), nodes with one to seven moves, fills on the chain, draws spanning views.
     Every game's move, root visits and stream words equal the oracle's."""
     n, sims = 768, 240
-    rng = random.Random(500 + bs)
-    boards = []
-    while len(boards) < n:
-        b, t = "." * 42, 0
-        lean = rng.sample(range(7), rng.randint(1, 3))  # columns filled first: chains hit full columns
-        ok = True
-        for _ in range(rng.randint(18, 41)):
-            legal = [col for col in range(7) if b[col] == "."]
-            pref = [col for col in legal if col in lean]
-            b, t = oracle.play(b, t, rng.choice(pref if pref and rng.random() < 0.7 else legal))
-            if oracle.check_win(b, t):
-                ok = rng.random() < 0.1  # a few already-won roots stay (get_move still searches them)
-                break
-        if ok and not oracle.check_draw(b):
-            boards.append((b, t))
+    boards = deep_leaning_roots(random.Random(500 + bs), n)
     seeds = [7919 * g + bs for g in range(n)]
     eng.seed(0, seeds)
     from zeroclone_amd._native import C4_STATE_DTYPE

@@ -225,17 +225,38 @@ def _rep_sequences(rng, count, cap):
         else:
             s = rng.integers(0, 2, n)
         out.append(np.asarray(s, np.uint16))
+    if cap > 3000:   # the kernel's whole LDS copy: full-length histories and long periods
+        for i in range(count):
+            p = int(rng.integers(1001, cap // 3 + 1))          # a period past 1000 that fits three times
+            block = rng.integers(0, 50, p)
+            if i % 8 == 1:     # exactly cap long, no structure
+                s = rng.integers(0, 3, cap)
+            elif i % 8 == 3:   # three copies of a long block at the recent end: a repeat
+                s = np.concatenate([rng.integers(0, 50, cap - 3 * p), np.tile(block, 3)])
+            elif i % 8 == 5:   # ... with one move of the middle copy changed: none through that period
+                s = np.concatenate([rng.integers(0, 50, int(rng.integers(0, cap - 3 * p + 1))), np.tile(block, 3)])
+                s[len(s) - p - 1 - int(rng.integers(0, p))] = 99
+            elif i % 8 == 7:   # exactly cap long and periodic throughout (the oldest copy cut short)
+                s = np.tile(block, cap // p + 1)[-cap:]
+            else:
+                continue
+            out[i] = np.asarray(s, np.uint16)
     return out
 
 
-def test_repetition_matches_has_repeated_prefix():
+@pytest.mark.parametrize("cap", [300, 4096])
+def test_repetition_matches_has_repeated_prefix(cap):
     """zc_chess_repetition_async against chess_backend.has_repeated_prefix (the KMP of
-    chess_backend.cpp:148-180) on 1,200 histories per side, most recent move first."""
+    chess_backend.cpp:148-180) on 1,200 histories per side of up to 300 moves, most recent move
+    first; and on 300 per side at the kernel's capacity of 4096 moves (kMaxHistory, the whole
+    8 KB LDS copy), some exactly 4096 long, some repeating a block of more than 1000 moves."""
     from zeroclone_amd import _native
     from zeroclone_amd.engine.games.chess.chess_backend import has_repeated_prefix
     rng = np.random.default_rng(5)
-    cap, G = 300, 1200
+    G = 1200 if cap == 300 else 300
     seqs = _rep_sequences(rng, 2 * G, cap)
+    if cap == 4096:
+        assert sum(len(s) == cap for s in seqs) >= G // 4
     hist = np.zeros((G, 2, cap), np.uint16)
     ln = np.zeros((G, 2), np.int32)
     for k, s in enumerate(seqs):
@@ -250,7 +271,8 @@ def test_repetition_matches_has_repeated_prefix():
         want = has_repeated_prefix([int(x) for x in s[::-1]])
         hits += want
         assert bool((got[k // 2] >> (k % 2)) & 1) == want, (k, s.tolist())
-    assert hits > 100   # the cases exercise both answers
+    # the cases exercise both answers (the guard scales with the number of histories)
+    assert hits > 100 * G // 1200 and len(seqs) - hits > 100 * G // 1200
 
 
 def _dense_boards(n=400, seed=23):

@@ -47,6 +47,23 @@ def test_get_move_root_visits(golden):
         assert used == c["consumed"]
 
 
+def test_get_move_at_the_engine_limits(golden):
+    """The reference at the limits the engine declares (tests/golden/gen_golden_limits.py):
+    batch sizes 128 to 512, either side of the search kernel's 314 / 315 workgroup boundary, and
+    65533 simulations, where node ids pass 15 bits."""
+    cases = golden("c4_get_move_limits.json")["cases"]
+    shapes = {(c["sims"], c["bs"]) for c in cases}
+    assert shapes >= {(1100, 128), (1100, 314), (1100, 315), (1100, 512), (65533, 32), (65533, 512)}
+    for c in cases:
+        mt = oracle.MT(c["seed"])
+        col, na, order = oracle.get_move_mt(c["board"], c["turn"], mt, c["sims"], c["c"], c["bs"])
+        assert order == c["order"]
+        assert na == c["root_na"], (c["seed"], c["sims"], c["bs"])
+        assert col == c["move"]
+        assert mt.drawn == c["consumed"]
+        assert mt.u32() == c["next_word"]
+
+
 def test_batch_matches_single(golden):
     cases = [c for c in golden("c4_get_move.json")["cases"] if c["sims"] == 100][:16]
     mv, na, cons = oracle.get_move_batch([c["board"] for c in cases], [c["turn"] for c in cases],

@@ -1739,6 +1739,12 @@ __global__ void uct_debug_kernel(int n, const double *logn, const int32_t *na, c
 // Games per workgroup: up to kSearchWaves share the tables (4 x ~8.6 KB + 2 KB at bs 32, so
 // four workgroups = 16 waves per CU fit the CU's 160 KB of LDS); fewer when a large batch
 // would not fit one workgroup (sharing only lowers the LDS per game).
+// Regimes over the engine's batch range [1, 512]: four waves up to batch 314 (163,584 of the
+// 163,840 bytes), two from 315 to 512; one wave would be needed from 676 only, past max_batch.
+// A change of the Leaf / Fresh / ChainNode or ring sizes that moves a boundary stops here.
+static_assert(kTabBytes + kSearchWaves * c4_search_wave_lds(314) <= 160 * 1024, "batch 314: the last with four waves");
+static_assert(kTabBytes + kSearchWaves * c4_search_wave_lds(315) > 160 * 1024, "batch 315: the first with two waves");
+static_assert(kTabBytes + 2 * c4_search_wave_lds(512) <= 160 * 1024, "batch 512 (max_batch) fits two waves");
 static int c4_search_wpg(int bs) {
     int w = kSearchWaves;
     while (w > 1 && kTabBytes + (size_t)w * c4_search_wave_lds(bs) > (size_t)(160 * 1024)) w >>= 1;
