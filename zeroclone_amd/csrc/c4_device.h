@@ -667,7 +667,7 @@ struct FlushSel {
     uint32_t ppath;  // lane l (l <= d0): level l of root..X0 = node | slot << 16
     bool x0_dirty;   // X0 expanded during the flush (its record must be rewritten)
     uint32_t x_u, x_ch;  // X0's untried word / child slot `lane & 7` as last seen
-    // select_flush_plan2 only (planned = true): the fresh nodes are the draws 0..D-1; bit j of
+    // select_flush_plan only (planned = true): the fresh nodes are the draws 0..D-1; bit j of
     // Sm: draw j is a chain node's first draw; bit j of Z: draw j created the next chain node
     bool planned = false;
     int D = 0;
@@ -721,20 +721,9 @@ __device__ __forceinline__ WalkEnd walk_hbm(const Tree &t, ConstDouble *logtab, 
             // UCT (mcts.cpp:41-45) = fma(c, sqrt(log(N)/Na), Qa), first max in slot order
             const double q = valid ? qw / (double)na : 0.0;
             const double v = valid ? fma(c, sqrt(lg / (double)na), q) : -INFINITY;
-#ifndef ZC_MAX8
-#define ZC_MAX8 1  // 0: the compare-and-swap argmax8 (A/B runs)
-#endif
             int bi;
-            if (ZC_MAX8) {
-                const double mx = max8_first(v, &bi);
-                if ((__ballot(mx == -INFINITY) & 1ull) != 0) break;  // no child: terminal leaf
-            } else {
-                double vv = v;
-                bi = (int)k;
-                argmax8(vv, bi);
-                if ((__ballot(vv == -INFINITY) & 1ull) != 0) break;
-                bi = uni(bi);
-            }
+            const double mx = max8_first(v, &bi);
+            if ((__ballot(mx == -INFINITY) & 1ull) != 0) break;  // no child: terminal leaf
             best = bi;
         }
         const int nxt = __builtin_amdgcn_readlane((int)ch, best);

@@ -125,9 +125,6 @@ __device__ __forceinline__ uint32_t ff1(uint64_t m) {
 #ifndef ZC_RV
 #define ZC_RV 0  // experiment switches (tools/rv_libs.sh); 0 = the product kernel
 #endif
-#ifndef ZC_LAG_MODE
-#define ZC_LAG_MODE 3  // free runs' pace balancing (A/B builds): 0 off, 1 per move, 2/3 per flush (2/3 levels)
-#endif
 // wave priority from a uniform level 0..3 (s_setprio takes an immediate)
 __device__ __forceinline__ void set_prio(int lvl) {
     if (lvl >= 3) __builtin_amdgcn_s_setprio(3);
@@ -277,7 +274,6 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
 #ifdef ZC_DIAG_WASTE
                 const uint32_t l0f = l0;
 #endif
-#if !(ZC_RV & 1)
                 RMARK(3);
                 if (lf == l0) {  // a fill with room for more plies
                     const uint32_t cf = (uint32_t)__builtin_amdgcn_readlane((int)col, (int)lf);
@@ -320,69 +316,6 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
                 // back to word order: the accepted lane of ply qk won if its compacted lane did
                 const uint32_t W32 = (uint32_t)W | (uint32_t)(W >> 32);
                 const uint64_t Ew = A & __ballot(((W32 >> (c & 31u)) & 1u) != 0u);
-#else
-                // compact EVERY accepted word's ply by parity: ply q < 32 to lane (q & 1)*16 + q/2
-                // (a forward lane permute; the other lanes, and plies >= 32, land in lanes 32..63),
-                // then copy lanes 0..31 up over lanes 32..63.  No ply past the block's last one (at
-                // lane l0) needs masking: each row's plies ascend along its lanes, so a later ply's
-                // stones only reach its own prefix, and its win can only show up in a word lane
-                // beyond l0 (the end is min(first win, l0) below).  Returns the accepted word lanes
-                // whose ply completed four; mine_ = each row's stones so far.
-                auto win_test = [&](uint64_t A_, uint32_t qk_, uint32_t col_, uint32_t row_, uint64_t &mine_) {
-                    const uint32_t c = ((qk_ & 1u) << 4) | ((qk_ >> 1) & 15u) | (qk_ & 32u);
-                    const uint32_t b = __umul24(col_, 7u) + row_;  // the ply's cell (a 24-bit mad, not a 64-bit one)
-                    const uint32_t pl = (uint32_t)__builtin_amdgcn_ds_permute((int)(mask_sel(A_, 63u, c) << 2), (int)b);
-                    const uint32_t pb = __builtin_amdgcn_permlane32_swap(pl, pl, false, false)[0];
-                    const uint64_t bit = 1ull << (pb & 63u);
-                    uint32_t blo = (uint32_t)bit, bhi = (uint32_t)(bit >> 32);
-                    scan_or16x2(blo, bhi);
-                    mine_ = ((uint64_t)bhi << 32) | blo;  // this row's stones so far
-                    x0 = in_vgpr(x0);
-                    x1 = in_vgpr(x1);
-                    const uint64_t bd = (((uint64_t)mask_sel(S1, (uint32_t)(x0 >> 32), (uint32_t)(x1 >> 32)) << 32) |
-                                         mask_sel(S1, (uint32_t)x0, (uint32_t)x1)) | mine_;
-                    const uint64_t m1 = bd & (bd >> d1), m2 = bd & (bd >> d2);
-                    const uint64_t f4 = (m1 & (m1 >> (2 * d1))) | (m2 & (m2 >> (2 * d2)));
-                    const uint64_t W = __ballot(f4 != 0ull);
-                    // back to word order: the accepted lane of ply qk won if its compacted lane did
-                    const uint32_t W32 = (uint32_t)W | (uint32_t)(W >> 32);
-                    return A_ & __ballot(((W32 >> (c & 31u)) & 1u) != 0u);
-                };
-                // ZC_RV & 1 (experiment): an absorbed fill's first segment (plies through the fill,
-                // the same before and after the re-draw) is win-tested on the pre-re-draw plies,
-                // independent of the re-draw, so the two chains can overlap; a win there ends the
-                // block without the second test
-                uint64_t Ew1 = 0, mine1 = 0;
-                RMARK(3);
-                if (lf == l0) {  // a fill with room for more plies
-                    const uint32_t cf = (uint32_t)__builtin_amdgcn_readlane((int)col, (int)lf);
-                    const uint32_t ow2 = (uint32_t)__builtin_amdgcn_readlane((int)owp, (int)(8u * cf));
-                    const uint32_t thr2 = (ow2 >> 24) & 15u;
-                    const uint64_t high = ~1ull << lf;  // the lanes after lf
-                    if (ZC_RV & 1) Ew1 = win_test(A, qk, col, row, mine1) & ~high;
-                    A = (A & ~high) | (__ballot(wv < thr2) & high);
-                    qk = mbcnt(A);
-                    col = mask_sel(high, col, (ow2 >> (3 * wv)) & 7u);  // lanes after lf: the new order
-                    one = mask_sel0(A, 1u << (4 * col));
-                    sc = scan_add32(one);
-                    row = ((sc - one + hp) >> (4 * col)) & 15u;
-                    nacc = (uint32_t)__popcll(A);
-                    F = __ballot(row == 5u) & high;  // the absorbed fill no longer ends the block
-                    E0 = A & (F | __ballot(qk >= min(cap_r, nacc - 1u)));
-                    l0 = (uint32_t)__builtin_ctzll(E0);
-                }
-                RMARK(4);
-                uint64_t Ew;
-                if ((ZC_RV & 1) && Ew1 != 0ull) {  // the win precedes the fill (l0 >= lf after the re-draw)
-                    Ew = Ew1;
-                    mine = mine1;
-                } else {
-                    Ew = win_test(A, qk, col, row, mine);
-                }
-                // (the merge of the two tests' masks can end up in VGPRs, which ff1's scalar
-                // operand does not take)
-                if (ZC_RV & 1) Ew = uni64(Ew);
-#endif
                 ew = ff1(Ew);
                 endlane = min(ew, l0);
                 endply = (uint32_t)__builtin_amdgcn_readlane((int)qk, (int)endlane);
@@ -516,24 +449,29 @@ __device__ void c4_rollouts_philox(Leaf *L, int nb, const uint8_t *s_sel, uint2 
 // +inf; old children have Na >= 1), whatever the draws were — for X0 the lowest untried
 // slot, for a fresh node slot 0.  So the chain of nodes X0 = C0, C1, ... (boards, move
 // counts, draws per node) is known before any draw is decoded; only the node IDS on the chain
-// (C_{i+1} = the child of the draw that took that slot) depend on the draws.
-// select_flush_plan therefore (1) walks the chain on the scalar unit, running each node's
-// draws (the same ballots + branch-free chain as select_flush) over a shared view and
-// recording the node in an LDS table; (2) builds every fresh node and leaf in ONE
-// lane-parallel pass, lane d = draw d = node f0 + d: its node's table entry, its r value, the
-// Lehmer decode inside its node's draws, its parent id (the draw of the previous chain node
-// that took position 0 of that node's untried list), its child's board, order word and
-// records; (3) patches the chain nodes' child slots and untried words (LDS atomics) and
-// X0's.  Same tree, same leaves, same stream consumption as select_flush (nb < 64: one lane
-// per draw; the rollout search only — select_flush records leaf paths for the stepwise search).
-struct ChainNode {
-    uint64_t p0, p1;  // the node's stones
-    uint32_t ow;      // its move-list order word
-    uint32_t info;    // n (draws are over n, n-1, ...) | m << 4 | first draw << 8 | depth << 16 | turn << 24 | legal << 25
-    uint32_t ul;      // its untried list (move indices in list order, 3 bits each)
-    uint32_t pad;
-};
-static_assert(sizeof(ChainNode) == 32, "chain table entry");
+// (C_{i+1} = the child of the draw that took that slot) depend on the draws.  With the chain
+// the whole flush's sequence of draw counts is known too: draw d of chain node i is over
+// n_i - (d - d_i) moves.  _randbelow(cnt) accepts a word when its top three bits t3 are below
+// T(cnt) (4, 4, 6, 4, 5, 6, 7 for cnt = 1..7): four acceptance classes c = T - 4.
+// select_flush_plan therefore
+//   (1a) walks the chain's shape on the scalar unit (boards, counts, first draws; each node's
+//        fields go to VGPR lane i by v_writelane, no LDS table, no exec juggling);
+//   (1b) builds, lane-parallel, a NEXT table over the 64-word view: lane l, byte c = 1 + the
+//        first word >= l (of words 0..61) that a class-c draw accepts, or 63 (none; lanes 62
+//        and 63 hold 63 in every byte, so the chase stays there);
+//   (1c) chases it: draw d is q_{d+1} = byte c_d of readlane(table, q_d), one v_readlane and
+//        one s_bfe_u32 per draw, and s_bitset1 records bit q of F; 63 -> bit 63 = the view ran
+//        out (the failed draw rejected words q..61 and goes on at word 62 of a fresh view);
+//   (2)  builds every fresh node and leaf in ONE lane-parallel pass, lane d = draw d = node
+//        f0 + d: its chain node's fields (ds_bpermute from that node's lane), its r value, the
+//        Lehmer decode inside its node's draws, its parent id (the draw of the previous chain
+//        node that took position 0 of that node's untried list), its child's board, order word
+//        and records; the leaves past the last draw all sit on the terminal chain node;
+//   (3)  patches the chain nodes' child slots and untried words (LDS atomics) and X0's.
+// Same tree, same leaves, same stream consumption as select_flush (nb < 64: one lane per draw
+// and lane 63 free as the permutes' discard slot; the rollout search only — select_flush
+// records leaf paths for the stepwise search).  The fresh in-edges' counters are not zeroed
+// here: the planned flush's backup (search_move, fs.planned) writes them from one prefix sum.
 
 __device__ __forceinline__ uint64_t lanes_in(int lo, int hi) {  // lanes lo .. hi-1 (0 <= lo <= hi <= 64)
     const uint64_t below_hi = hi >= 64 ? ~0ull : (1ull << hi) - 1ull;
@@ -587,16 +525,8 @@ __device__ __forceinline__ WalkEnd walk_hbm_prefetch(const Tree &t, ConstDouble 
             const double q = valid ? (double)wa / (double)na : 0.0;
             const double v = valid ? fma(c, sqrt(lg / (double)na), q) : -INFINITY;
             int bi;
-            if (ZC_MAX8) {
-                const double mx = max8_first(v, &bi);
-                if ((__ballot(mx == -INFINITY) & 1ull) != 0) break;  // no child: terminal leaf
-            } else {
-                double vv = v;
-                bi = (int)k;
-                argmax8(vv, bi);
-                if ((__ballot(vv == -INFINITY) & 1ull) != 0) break;
-                bi = uni(bi);
-            }
+            const double mx = max8_first(v, &bi);
+            if ((__ballot(mx == -INFINITY) & 1ull) != 0) break;  // no child: terminal leaf
             best = bi;
         }
         nN = __builtin_amdgcn_readlane(na, best);
@@ -616,233 +546,6 @@ __device__ __forceinline__ WalkEnd walk_hbm_prefetch(const Tree &t, ConstDouble 
     return WalkEnd{node, depth, turn, b0, b1, pathv, u, ow, ch};
 }
 
-template <bool STAMP, class RNG>
-__device__ __forceinline__ void select_flush_plan(const Tree &t, Fresh *fresh, Leaf *leaves, ChainNode *chain,
-                                                  const uint32_t *s_order, ConstDouble *logtab, RNG &rng,
-                                                  Counters &cn, Stamp<STAMP> &stamp, int &nnodes, int &status,
-                                                  uint64_t rp0, uint64_t rp1, int rturn, int done, int nb, double c,
-                                                  FlushSel &fs) {
-    const uint32_t lane = lane_id();
-    const int f0 = nnodes;
-    for (int i = (int)lane; i < nb; i += 64) {  // fresh slots: no children, zero in-edge counters
-        fresh[i].na = 0;
-        fresh[i].w = 0;
-        *(uint4 *)fresh[i].ch = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-    }
-#ifndef ZC_WALK_PREFETCH
-#define ZC_WALK_PREFETCH 1
-#endif
-    const WalkEnd we = ZC_WALK_PREFETCH ? walk_hbm_prefetch(t, logtab, rp0, rp1, rturn, done, c, status)
-                                        : walk_hbm<false>(t, logtab, rp0, rp1, rturn, done, c, status);
-    fs.f0 = f0;
-    fs.x0node = we.node;
-    fs.d0 = we.depth;
-    fs.ppath = we.pathv;
-    fs.x_u = we.u;
-    fs.x_ch = we.ch;
-    fs.x0_dirty = false;
-    stamp.mark(1);
-    const uint32_t cnt0 = untried_count(we.u);
-    if (cnt0 == 0) {  // X0 has no move (full board): every leaf of the flush is X0
-        const uint32_t meta = (uint32_t)we.node | ((uint32_t)we.depth << 16) | ((uint32_t)we.turn << 24) |
-                              ((uint32_t)legal_mask(we.b0 | we.b1) << 25);
-        for (int i = (int)lane; i < nb; i += 64) leaves[i] = Leaf{we.b0, we.b1, meta, 0, we.ow, 0};
-        wave_mem_order();
-        stamp.mark(3);
-        return;
-    }
-
-    // ---- (1) the chain, its draws and its table
-    constexpr uint32_t kIdentList = 0x1AC688u;  // 0, 1, ..., 6
-    uint64_t b0 = we.b0, b1 = we.b1;
-    int turn = we.turn, depth = we.depth;
-    uint32_t ow = we.ow, cm = (uint32_t)legal_mask(b0 | b1), n = cnt0, ul = 0;
-    {
-        uint32_t k = 0;
-        for (uint32_t bb = 0; bb < 7; ++bb)
-            if ((we.u >> bb) & 1u) ul |= bb << (3 * k++);
-    }
-    int d = 0, i = 0, T = -1;  // draws so far, chain node, the terminal chain node (full board)
-    uint64_t Sm = 0;           // bit s: a chain node's first draw
-    uint32_t raw = 0;          // lane d: the accepted word of draw d
-    rng_need(rng);
-    uint32_t w = rng_view(rng);  // lane l: the next unconsumed word + l
-    uint32_t t3 = w >> (ViewBits<RNG>::kBits - 3u);
-    uint64_t gt = ~0ull, Fv = 0;  // the view: lanes after the last accepted word; accepted words
-    int dv0 = 0;                  // first draw of the view
-    for (;;) {
-        const int m = min((int)n, nb - d);
-        if (lane == 0)
-            chain[i] = ChainNode{b0, b1, ow,
-                                 n | ((uint32_t)m << 4) | ((uint32_t)d << 8) | ((uint32_t)depth << 16) |
-                                     ((uint32_t)turn << 24) | (cm << 25),
-                                 ul, 0u};
-        if (m == 0) {  // a chain node without moves: the flush's remaining leaves are all it
-            T = i;
-            break;
-        }
-        Sm |= 1ull << d;
-        int k = 0;
-        for (;;) {  // this node's draws over n - k, n - k - 1, ... (a view at a time)
-            const int rem = m - k, cnt = (int)n - k;  // rem: 1 .. 7
-            // _randbelow(nn) accepts a word when (w >> (32 - bit_length(nn))) < nn, i.e. when its
-            // top three bits t3 are below T(nn) = 4, 4, 6, 4, 5, 6, 7 for nn = 1 .. 7 (nn = 1, 2:
-            // the top bit / two bits; nn = 3: the top two bits < 3).  Step s draws over cnt - s
-            // moves: its threshold is nibble s of P (0 past rem: no word accepted).
-            const uint32_t P = (0x04464567u >> (4u * (uint32_t)(7 - cnt))) & ((1u << (4u * (uint32_t)rem)) - 1u);
-            uint64_t A[7];
-#pragma unroll
-            for (int s = 0; s < 7; ++s) A[s] = __ballot(t3 < ((P >> (4u * s)) & 15u));
-            // the draws, a scalar chain: each takes the lowest accepted word after the last one
-            // (s_ff1; none: -1, and gt = -2 << 63 = 0 stops the later steps), its bit = acc & ~gt
-            uint64_t F = 0;
-#pragma unroll
-            for (int s = 0; s < 7; ++s) {
-                const uint64_t acc = A[s] & gt;
-                gt = (~1ull) << (ff1(acc) & 63u);
-                F |= acc & ~gt;
-            }
-            Fv |= F;
-            const int nd = __popcll(F);
-            k += nd;
-            d += nd;
-            if (k < m) {  // the view ran out: all of it is consumed; its draws go to their lanes
-                const uint32_t di = (uint32_t)dv0 + mbcnt64(Fv);
-                const uint32_t got =
-                    (uint32_t)__builtin_amdgcn_ds_permute((int)(mask_sel(Fv, 63u, di) << 2), (int)w);
-                raw = mask_sel(lanes_in(dv0, d), raw, got);
-                rng_eat(rng, (uint32_t)kWin);
-                rng_need(rng);
-                w = rng_view(rng);
-                t3 = w >> (ViewBits<RNG>::kBits - 3u);
-                gt = ~0ull;
-                Fv = 0;
-                dv0 = d;
-                continue;
-            }
-            // the node's draws are done: the next node's start after its last word (the steps
-            // past rem zeroed gt)
-            gt = (~1ull) << (63 - __clzll(Fv));
-            break;
-        }
-        if (d >= nb) break;
-        // the next walk enters this node's lowest untried slot
-        const int col = (int)((ow >> (3 * (ul & 7u))) & 7u);
-        const uint64_t bit = drop_bit(b0 | b1, col);
-        if (turn) b1 |= bit; else b0 |= bit;
-        turn ^= 1;
-        ++depth;
-        if (bit & kTop) {
-            cm &= ~(1u << col);
-            ow = uni(s_order[cm]);
-        }
-        n = (ow >> 24) & 15u;
-        ul = kIdentList;
-        ++i;
-    }
-    {  // the last view's draws (it always has one: a view is only left once it ran out)
-        const uint32_t di = (uint32_t)dv0 + mbcnt64(Fv);
-        const uint32_t got = (uint32_t)__builtin_amdgcn_ds_permute((int)(mask_sel(Fv, 63u, di) << 2), (int)w);
-        raw = mask_sel(lanes_in(dv0, d), raw, got);
-        rng_eat(rng, (uint32_t)(63 - __clzll(Fv | 1ull)) + 1u);
-    }
-    const int D = d;  // fresh nodes f0 .. f0 + D - 1
-    wave_mem_order();
-    stamp.mark(2);
-
-    // ---- (2) every fresh node and leaf, lane d = draw d
-    const bool act = (int)lane < D;
-    const uint32_t seg = act ? mbcnt64(Sm) + (uint32_t)((Sm >> lane) & 1ull) - 1u : 0u;
-    const ChainNode e = chain[seg];
-    const uint32_t s_i = (e.info >> 8) & 0xFFu;
-    const uint32_t dd = lane - s_i;  // the draw's index inside its node
-    const uint32_t r = raw >> draw_shift<RNG>(act ? (e.info & 15u) - dd : 1u);
-    // draw dd's position in the node's untried list as it was before the node's draws
-    // (select_flush's Lehmer decode, each lane against its own node's earlier draws)
-    uint32_t rp[6];
-#pragma unroll
-    for (int s = 0; s < 6; ++s) rp[s] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((s_i + (uint32_t)s) << 2), (int)r);
-    uint32_t pl = r;
-#pragma unroll
-    for (int s = 5; s >= 0; --s) pl += (dd > (uint32_t)s && pl >= rp[s]) ? 1u : 0u;
-    const uint32_t mi = (e.ul >> (3 * (pl & 7u))) & 7u;
-    const uint64_t Z = __ballot(act && pl == 0);  // per chain node: the draw holding its lowest untried slot
-    const uint64_t zl = Z & ((1ull << s_i) - 1ull);
-    const int parent = seg == 0 ? we.node : f0 + 63 - __clzll(zl | 1ull);
-    {
-        const uint32_t col = (e.ow >> (3 * mi)) & 7u;
-        const uint64_t bit = drop_bit(e.p0 | e.p1, (int)col);
-        const uint32_t tn = (e.info >> 24) & 1u, ldepth = ((e.info >> 16) & 0xFFu) + 1u;
-        const bool filled = (bit & kTop) != 0;
-        const uint32_t c_lmask = (e.info >> 25) & ~(filled ? 1u << col : 0u);
-        uint32_t c_low = e.ow;
-        if (act && filled) c_low = s_order[c_lmask];
-        if (act) {
-            *(uint4 *)&fresh[lane] = make_uint4(untried_init((c_low >> 24) & 15u), c_low,
-                                                (uint32_t)parent | (mi << 16) | (ldepth << 24), c_lmask);
-            leaves[lane] = Leaf{tn ? e.p0 : (e.p0 | bit), tn ? (e.p1 | bit) : e.p1,
-                                ((uint32_t)f0 + lane) | (ldepth << 16) | ((tn ^ 1u) << 24) | (c_lmask << 25), 0,
-                                c_low, 0};
-        }
-    }
-    if (T >= 0) {  // the terminal chain node (entered from the full node before it)
-        const ChainNode et = chain[T];
-        const uint32_t meta = (uint32_t)(f0 + 63 - __clzll(Z | 1ull)) | (((et.info >> 16) & 0xFFu) << 16) |
-                              (((et.info >> 24) & 1u) << 24) | ((et.info >> 25) << 25);
-        for (int jj = D + (int)lane; jj < nb; jj += 64) leaves[jj] = Leaf{et.p0, et.p1, meta, 0, et.ow, 0};
-    }
-    wave_mem_order();
-    // ---- (3) the chain nodes' child slots and untried words; X0's
-    if (act && seg != 0) {
-        Fresh &P = fresh[parent - f0];
-        P.ch[mi] = (uint16_t)(f0 + (int)lane);
-        atomicAnd(&P.u, ~(1u << mi));
-    }
-    uint32_t slotbit = (act && seg == 0) ? 1u << mi : 0u;  // X0's draws are lanes 0 .. m0-1 (< 8)
-    slotbit |= (uint32_t)dpp<0xB1>((int)slotbit);
-    slotbit |= (uint32_t)dpp<0x4E>((int)slotbit);
-    slotbit |= (uint32_t)dpp<0x141>((int)slotbit);
-    const uint32_t ucl = uni(slotbit);
-    const uint32_t sent =
-        (uint32_t)__builtin_amdgcn_ds_permute((int)(((act && seg == 0) ? mi : 63u) << 2), (int)((uint32_t)f0 + lane));
-    fs.x_ch = ((ucl >> (lane & 7u)) & 1u) ? sent : we.ch;
-    fs.x_u = we.u & ~ucl;
-    fs.x0_dirty = true;
-    nnodes = f0 + D;
-    wave_mem_order();
-    {  // the flush's expansions and their depths (as select_flush)
-        int dsum = 0;
-        for (int base = 0; base < D; base += 64) {
-            const int q = base + (int)lane;
-            const uint32_t dep = q < D ? fresh[q].link >> 24 : 0u;
-#pragma unroll
-            for (int bit = 0; bit < 6; ++bit) dsum += __popcll(__ballot((dep >> bit) & 1u)) << bit;
-        }
-        cn.add(cn.expansions, D);
-        cn.add(cn.depth_sum, dsum);
-    }
-    stamp.mark(3);
-}
-
-// ------------------------------------------------------------------ the planned flush, draws as a table chase
-// select_flush_plan's step (1) spends ~110 scalar instructions per chain node (seven unrolled
-// draw steps of five to seven SALU each, whatever the node's draw count, the view bookkeeping,
-// the descent and the node's table entry written by lane 0) — about 26 SALU per simulation, the
-// largest scalar cost of the walk.  But the chain's shape is known before any draw (see above),
-// and with it the whole flush's sequence of draw counts: draw d of chain node i is over
-// n_i - (d - d_i) moves.  _randbelow(cnt) accepts a word when its top three bits t3 are below
-// T(cnt) (4, 4, 6, 4, 5, 6, 7 for cnt = 1..7): four acceptance classes c = T - 4.
-// select_flush_plan2 therefore
-//   (1a) walks the chain's shape on the scalar unit (boards, counts, first draws; each node's
-//        fields go to VGPR lane i by v_writelane, no LDS table, no exec juggling);
-//   (1b) builds, lane-parallel, a NEXT table over the 64-word view: lane l, byte c = 1 + the
-//        first word >= l (of words 0..61) that a class-c draw accepts, or 63 (none; lanes 62
-//        and 63 hold 63 in every byte, so the chase stays there);
-//   (1c) chases it: draw d is q_{d+1} = byte c_d of readlane(table, q_d), one v_readlane and
-//        one s_bfe_u32 per draw, and s_bitset1 records bit q of F; 63 -> bit 63 = the view ran
-//        out (the failed draw rejected words q..61 and goes on at word 62 of a fresh view);
-//   (2)  as select_flush_plan, the chain nodes' fields fetched by ds_bpermute.
-// Same draws, same tree, same leaves, same stream consumption as select_flush_plan.
 // s_bfe_u32 operand of a class-c draw: byte c of the table entry, 6 bits
 __device__ __forceinline__ uint32_t draw_class_bfe(uint32_t cnt) {  // c = T(cnt) - 4
     return (6u << 16) | (((0xE480u >> (2u * cnt)) & 3u) << 3);
@@ -891,22 +594,14 @@ __device__ __forceinline__ uint64_t draw_chase_fixed(uint32_t nx, uint32_t clsv)
 }
 
 template <bool STAMP, class RNG>
-__device__ __forceinline__ void select_flush_plan2(const Tree &t, Fresh *fresh, Leaf *leaves, const uint32_t *s_order,
-                                                   ConstDouble *logtab, RNG &rng, Counters &cn, Stamp<STAMP> &stamp,
-                                                   int &nnodes, int &status, uint64_t rp0, uint64_t rp1, int rturn,
-                                                   int done, int nb, double c, FlushSel &fs) {
+__device__ __forceinline__ void select_flush_plan(const Tree &t, Fresh *fresh, Leaf *leaves, const uint32_t *s_order,
+                                                  ConstDouble *logtab, RNG &rng, Counters &cn, Stamp<STAMP> &stamp,
+                                                  int &nnodes, int &status, uint64_t rp0, uint64_t rp1, int rturn,
+                                                  int done, int nb, double c, FlushSel &fs) {
     const uint32_t lane = lane_id();
     const int f0 = nnodes;
-#ifndef ZC_MERGED_BACKUP
-#define ZC_MERGED_BACKUP 1  // 0: the fresh edges by LDS atomics up the parent links (A/B runs)
-#endif
-    for (int i = (int)lane; i < nb; i += 64) {  // fresh slots: no children (the in-edge counters: the backup)
-        if (!ZC_MERGED_BACKUP) {
-            fresh[i].na = 0;
-            fresh[i].w = 0;
-        }
+    for (int i = (int)lane; i < nb; i += 64)  // fresh slots: no children (the in-edge counters: the backup)
         *(uint4 *)fresh[i].ch = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-    }
     const WalkEnd we = walk_hbm_prefetch(t, logtab, rp0, rp1, rturn, done, c, status);
     fs.f0 = f0;
     fs.x0node = we.node;
@@ -922,7 +617,7 @@ __device__ __forceinline__ void select_flush_plan2(const Tree &t, Fresh *fresh, 
                               ((uint32_t)legal_mask(we.b0 | we.b1) << 25);
         for (int i = (int)lane; i < nb; i += 64) leaves[i] = Leaf{we.b0, we.b1, meta, 0, we.ow, 0};
         wave_mem_order();
-        fs.planned = ZC_MERGED_BACKUP;  // D = 0: no fresh node
+        fs.planned = true;  // D = 0: no fresh node
         stamp.mark(3);
         return;
     }
@@ -1091,7 +786,7 @@ __device__ __forceinline__ void select_flush_plan2(const Tree &t, Fresh *fresh, 
     fs.x_ch = ((ucl >> (lane & 7u)) & 1u) ? sent : we.ch;
     fs.x_u = we.u & ~ucl;
     fs.x0_dirty = true;
-    fs.planned = ZC_MERGED_BACKUP;
+    fs.planned = true;
     fs.D = D;
     fs.Sm = Sm;
     fs.Z = Z;
@@ -1111,25 +806,29 @@ __device__ __forceinline__ void select_flush_plan2(const Tree &t, Fresh *fresh, 
 // ------------------------------------------------------------------ the search kernel
 constexpr int kSearchWaves = 4;  // games (waves) per workgroup
 // The rollout search records no leaf paths (select_flush gets nullptr), so its per-wave block
-// has no path area: after the leaves comes only the chain table of select_flush_plan (A/B
-// builds with ZC_PLAN2=0), one entry per chain node — at most a node per leaf and a terminal one.
+// has no path area.  After the leaves come kWaveSpare(bs) reserved bytes that nothing uses: they
+// were the chain table of the first planned flush (32 B per chain node, at most a node per leaf
+// and a terminal one).  They stay because reclaiming them would change behaviour: the
+// four-wave boundary below would move from batch 314/315 to 440/441, and with it the workgroup
+// shape, the occupancy and zc_c4_pooled_max_games for batches 315..440.
+__host__ __device__ constexpr size_t kWaveSpare(int bs) { return 32 * ((size_t)bs + 1); }
 __host__ __device__ constexpr size_t c4_search_wave_lds(int bs) {
     return ((size_t)kLRingBytes + (size_t)kLDrawBytes + (sizeof(Leaf) + sizeof(Fresh)) * (size_t)bs +
-            sizeof(ChainNode) * ((size_t)bs + 1) + 15) & ~(size_t)15;
+            kWaveSpare(bs) + 15) & ~(size_t)15;
 }
 // batch 32: 8,800 B a wave (9,536 before the draw ring took the path area's place), 37,248 B a
 // workgroup with the tables: four workgroups per CU fit the 160 KB as before
 static_assert(c4_search_wave_lds(32) == 8800 && c4_search_wave_lds(32) <= 9536, "per-wave LDS at batch 32");
 static_assert(4 * (kTabBytes + kSearchWaves * c4_search_wave_lds(32)) <= 160 * 1024, "four workgroups per CU");
 
-// Per-wave LDS of the search: the MT rings (raw words, draws), fresh nodes, pending leaves,
-// the chain table.  The rings come first: their place does not depend on the batch size.
+// Per-wave LDS of the search: the MT rings (raw words, draws), fresh nodes, pending leaves
+// (then the reserved kWaveSpare).  The rings come first: their place does not depend on the
+// batch size.
 struct SearchLds {
     uint32_t *s_order;  // the workgroup's tables: order[128] u32 + sel[128][8]
     uint32_t *ring;     // kLRingBytes raw words, then kLDrawBytes draws (LRng)
     Fresh *fresh;
     Leaf *leaves;
-    ChainNode *chain;
 };
 
 __device__ __forceinline__ SearchLds search_lds(uint8_t *s_dyn, int bs) {
@@ -1141,7 +840,6 @@ __device__ __forceinline__ SearchLds search_lds(uint8_t *s_dyn, int bs) {
     constexpr size_t kRings = (size_t)kLRingBytes + (size_t)kLDrawBytes;
     L.fresh = (Fresh *)(s_wave + kRings);
     L.leaves = (Leaf *)(s_wave + kRings + sizeof(Fresh) * (size_t)bs);
-    L.chain = (ChainNode *)(s_wave + kRings + (sizeof(Fresh) + sizeof(Leaf)) * (size_t)bs);
     return L;
 }
 
@@ -1187,21 +885,11 @@ __device__ __forceinline__ void search_move(const SearchParams &p, const SearchL
         FlushSel fs;
         {
             const zc_c4_state root = p.roots[gl];
-#ifndef ZC_NO_PLAN
-#define ZC_NO_PLAN 0
-#endif
             // one lane per draw and lane 63 free as the permutes' discard slot (bs < 64)
-#ifndef ZC_PLAN2
-#define ZC_PLAN2 1  // 0: the chain's draws node by node (select_flush_plan), for A/B runs
-#endif
-            if (!ZC_NO_PLAN && ZC_PLAN2 && p.bs < 64)
-                select_flush_plan2<STAMP>(t, fresh, leaves, s_order, logtab, rng, cn, stamp, nnodes, status,
-                                          uni64(root.stones[0]), uni64(root.stones[1]), uni(root.turn), done, nb,
-                                          p.c, fs);
-            else if (!ZC_NO_PLAN && p.bs < 64)
-                select_flush_plan<STAMP>(t, fresh, leaves, L.chain, s_order, logtab, rng, cn, stamp,
-                                         nnodes, status, uni64(root.stones[0]), uni64(root.stones[1]),
-                                         uni(root.turn), done, nb, p.c, fs);
+            if (p.bs < 64)
+                select_flush_plan<STAMP>(t, fresh, leaves, s_order, logtab, rng, cn, stamp, nnodes, status,
+                                         uni64(root.stones[0]), uni64(root.stones[1]), uni(root.turn), done, nb,
+                                         p.c, fs);
             else
                 select_flush<false, STAMP>(t, fresh, leaves, nullptr, s_order, logtab, rng, cn, stamp, nnodes,
                                            status, uni64(root.stones[0]), uni64(root.stones[1]), uni(root.turn),
@@ -1226,12 +914,10 @@ __device__ __forceinline__ void search_move(const SearchParams &p, const SearchL
             // chains (scalar-unit bound) first while the walk's and the backup's memory round
             // trips are in flight.  Priority 1, 2 or 3: 1.62 ms against 1.73 per 4096 x 800
             // lockstep search; the memory phases raised instead: 1.70 (profiles/r05_ab_c4_wave_priority.log).
-#ifndef ZC_ROLLOUT_PRIO
-#define ZC_ROLLOUT_PRIO 1  // A/B builds: the rollouts' wave priority
-#endif
+            constexpr int kRolloutPrio = 1;
             // `lag` (free runs): how far this game is behind the launch's average pace; its
             // phases run that many levels up, so the arbiter evens the games' paces out
-            set_prio(lag + ZC_ROLLOUT_PRIO);
+            set_prio(lag + kRolloutPrio);
             c4_rollouts(leaves, nb, rng, s_order, cn, STAMP ? &stamp.ph[7] : nullptr);
             set_prio(lag);
             if (WALK == 1) {
@@ -1259,13 +945,13 @@ __device__ __forceinline__ void search_move(const SearchParams &p, const SearchL
         // carry launches: the budget's state, read beside the prefix counters (one round trip);
         // free runs: the launch's finished moves (pace balancing)
         if (stop) spent_v = __hip_atomic_load(stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (ZC_LAG_MODE >= 2 && progress)
+        if (progress)
             spent_v = __hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (pre) {
             na0 = t.na(par)[act];
             w0 = t.w(par)[act];
         }
-        const int32_t spent = stop || (ZC_LAG_MODE >= 2 && progress) ? uni(spent_v) : 0;
+        const int32_t spent = stop || progress ? uni(spent_v) : 0;
         if (fs.planned) {
             // The planned flush's fresh nodes are the draws 0..D-1 (leaf j <-> node f0 + j for
             // j < D; the leaves D..nb-1 sit on the terminal chain node).  A fresh node's subtree is
@@ -1406,13 +1092,10 @@ __device__ __forceinline__ void search_move(const SearchParams &p, const SearchL
         stamp.mark(6);
         done += nb;
         if (stop && done < p.sims && status == 0 && uni(spent) >= budget) break;  // suspend
-        if (ZC_LAG_MODE >= 2 && progress) {  // behind the average (in simulations): 1; by a move or more: 2
+        if (progress) {  // behind the average (in simulations): 1; by a move or more: 2
             const int64_t own = ((int64_t)mv * p.sims + done) * p.n_games, avg = (int64_t)spent * p.sims;
             const int64_t mvn = (int64_t)p.sims * p.n_games;  // one move behind
-            if (ZC_LAG_MODE == 4)  // behind by < 1/2 move: 1, < 1 move: 2, more: 3
-                lag = own >= avg ? 0 : own + mvn / 2 > avg ? 1 : own + mvn > avg ? 2 : 3;
-            else
-                lag = own < avg ? (ZC_LAG_MODE == 3 && own + mvn <= avg ? 2 : ZC_LAG_MODE == 3 ? 1 : 2) : 0;
+            lag = own >= avg ? 0 : own + mvn <= avg ? 2 : 1;
             set_prio(lag);
         }
     }
@@ -1567,15 +1250,10 @@ __global__ __launch_bounds__(kSearchWaves * kBlock, 4) void c4_selfplay_kernel(S
         const uint32_t tag = resume ? cy.z : uni((uint32_t)(use0 + (uint64_t)(int64_t)rng.use()));
         const int done0 = done;
         // free runs (every game exactly p.moves moves, the launch waits for the slowest): a game
-        // whose moves so far are below the launch's average raises its priority for this move
-        if (ZC_LAG_MODE == 1 && p.progress) {
-            const int32_t tot = __hip_atomic_load(p.progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            lag = (int64_t)mv * p.n_games < (int64_t)uni(tot) ? 2 : 0;
-            set_prio(lag);
-        }
+        // behind the launch's average pace raises its priority, flush by flush (search_move)
         search_move<false, PHILOX>(p, L, gl, g, t, rng, tag, cn, status, done, nnodes, p.carry ? p.ticket : nullptr,
-                                   p.budget, &lag, ZC_LAG_MODE ? p.progress : nullptr, mv);
-        if (ZC_LAG_MODE && p.progress && lane == 0) atomicAdd(p.progress, 1);
+                                   p.budget, &lag, p.progress, mv);
+        if (p.progress && lane == 0) atomicAdd(p.progress, 1);
         leaves += done - done0;
         if (done < p.sims) {  // suspended (carry launch, budget spent): the next launch resumes it
             if (lane == 0) a.carry[g] = make_uint4((uint32_t)done, (uint32_t)nnodes, tag, 0u);
@@ -1741,7 +1419,7 @@ __global__ void uct_debug_kernel(int n, const double *logn, const int32_t *na, c
 // would not fit one workgroup (sharing only lowers the LDS per game).
 // Regimes over the engine's batch range [1, 512]: four waves up to batch 314 (163,584 of the
 // 163,840 bytes), two from 315 to 512; one wave would be needed from 676 only, past max_batch.
-// A change of the Leaf / Fresh / ChainNode or ring sizes that moves a boundary stops here.
+// A change of the Leaf / Fresh, kWaveSpare or ring sizes that moves a boundary stops here.
 static_assert(kTabBytes + kSearchWaves * c4_search_wave_lds(314) <= 160 * 1024, "batch 314: the last with four waves");
 static_assert(kTabBytes + kSearchWaves * c4_search_wave_lds(315) > 160 * 1024, "batch 315: the first with two waves");
 static_assert(kTabBytes + 2 * c4_search_wave_lds(512) <= 160 * 1024, "batch 512 (max_batch) fits two waves");

@@ -630,10 +630,6 @@ __device__ __forceinline__ int legal_moves_check(const uint8_t *b, int t, uint16
     return legal_moves_check(b, (uint32_t)b[lane()], t, out, ps, reg, check);
 }
 
-#ifndef ZC_CHESS_FREEPROBE
-#define ZC_CHESS_FREEPROBE 1  // legal_moves_probe tries has_free_move first (A/B: 0)
-#endif
-
 // A sufficient test for "the mover has a legal move" (legal_moves_probe's common case): the
 // mover's king (the first, as find_king) is not attacked, and some piece of the mover other than
 // a king, standing on none of the king's eight lines, has a pseudo-legal move.  Such a move
@@ -676,7 +672,7 @@ __device__ __forceinline__ int legal_moves_probe(const uint8_t *b, uint32_t pc, 
     if ((heavy || minor > 1) && make_bitview(pc, t, bv)) {
         const int s = (int)lane();
         const bool mine = !empty_sq(pc) && ((t == 0) == is_white(pc));
-        if (ZC_CHESS_FREEPROBE && has_free_move(bv, s, pc, mine)) {
+        if (has_free_move(bv, s, pc, mine)) {
             lazy = true;
             check = false;
             return 1;

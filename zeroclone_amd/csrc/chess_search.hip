@@ -117,11 +117,8 @@ struct Expansion {
     uint32_t base;   // X's first slot
 };
 
-#ifndef ZC_CHESS_LAZY
-#define ZC_CHESS_LAZY 1  // 1: crude-search nodes are created with a legal-move probe only (A/B: 0)
-#endif
-
-// The first expansion of a lazy node (created by create_child_gen<true>): its position into
+// Crude-search nodes are lazy: created with a legal-move probe only (create_child_gen).
+// The first expansion of such a node: its position into
 // L.st, the full get_legal_moves, and the node's move list committed as create_node_commit
 // would have at its creation (slots taken now, all moves untried, no children).  Returns the
 // list's length (nu == nmoves from here on) and its first slot in `base`.
@@ -170,7 +167,7 @@ __device__ __forceinline__ Expansion sim_front(const ChessParams &p, const CTree
     int nu = hit ? rs.nu : uni((int)N->nu);
     uint32_t lazy_base = 0;
     bool lazy_gen = false;
-    if (ZC_CHESS_LAZY && !hit && nu > 0 && !status && uni((int)N->nmoves) == (int)kChessLazy) {
+    if (!hit && nu > 0 && !status && uni((int)N->nmoves) == (int)kChessLazy) {
         nu = generate_lazy(t, L, N, slots, status, lazy_base);
         lazy_gen = true;
     }
@@ -315,7 +312,7 @@ __device__ void helper_loop(Helper &h) {
         __syncthreads();  // a command is posted
         if (uni(h.cmd) != 1) return;  // plain LDS accesses: the barriers order them
         const uint32_t stw = lane < 18 ? h.stw[lane] : 0u;
-        const NodeGen gen = create_child_gen<ZC_CHESS_LAZY != 0>(h.L, stw, uni(h.m));
+        const NodeGen gen = create_child_gen(h.L, stw, uni(h.m));
         if (lane == 0) h.gen = gen;
         __syncthreads();  // the generated child is in h
     }
@@ -460,7 +457,7 @@ __device__ __forceinline__ int chess_select_flush(const ChessParams &p, const CT
         if (ida >= p.M) status = ZC_STATUS_INTERNAL;
         CSTAMP_T(cs3);
         // play_move + Node(...) (mcts.cpp:74-76); its legal moves generated on its first expansion
-        const NodeGen ga = create_child_gen<ZC_CHESS_LAZY != 0>(L, a.stw, a.m);
+        const NodeGen ga = create_child_gen(L, a.stw, a.m);
         if (!status) commit_child(t, L, ga, a, ida, slots, status, cn);
         CSTAMP_ADD(3, cs3);
         record(ida, a.depth + 1, leaf_path(a));
@@ -520,10 +517,6 @@ __device__ __forceinline__ void chess_backup_flush(const ChessParams &p, const C
     }
 }
 
-#ifndef ZC_CHESS_AGG_BACKUP
-#define ZC_CHESS_AGG_BACKUP 1  // crude_backup_flush aggregates each flush's edges (A/B: 0)
-#endif
-
 // crude_chess_score's value.batch (mcts.cpp:116-118) and backprop (mcts.cpp:80-100) of one
 // flush, the backup aggregated per edge.  The crude values are integers (material; +-1000 for
 // a mate), so an edge's Na += its leaves and Wa -= the sum of their signed values equals the
@@ -568,7 +561,7 @@ __device__ __forceinline__ void crude_values_backup(const ChessParams &p, const 
     CSTAMP_T(cs5);
     int pairs = dj;
     for (int o = 32; o > 0; o >>= 1) pairs += __shfl_xor(pairs, o);
-    if (!ZC_CHESS_AGG_BACKUP || !T || nb > 64 || pairs > kBackupHash / 2) {
+    if (!T || nb > 64 || pairs > kBackupHash / 2) {
         chess_backup_flush(p, t, g, ctl, s_vals, nb);
         CSTAMP_ADD(5, cs5);
         return;
@@ -667,7 +660,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void c
     __builtin_amdgcn_s_setprio(1);
     int32_t *ctl = p.ca.ctl + (size_t)g * kCtlWords;
     CSTAMP_INIT();
-    if (ZC_CHESS_AGG_BACKUP) backup_table_clear(T);
+    backup_table_clear(T);
     crude_search(p, t, L, s_vals, gl, g, ctl, &H, &T);
     CSTAMP_FLUSH();
     finish(p, t, gl, g, ctl);
@@ -784,7 +777,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void c
         return;
     }
     __builtin_amdgcn_s_setprio(1);  // the leader first (chess_search_kernel)
-    if (ZC_CHESS_AGG_BACKUP) backup_table_clear(T);
+    backup_table_clear(T);
     const uint32_t lane = lane_id();
     int32_t *ctl = p.ca.ctl + (size_t)g * kCtlWords;
     const uint64_t use_start = uni64(p.a.rngpos[2 * (size_t)g]);

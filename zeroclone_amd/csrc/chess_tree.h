@@ -116,8 +116,8 @@ constexpr uint16_t kChessLazy = 0xFFFF;
 
 // The child of the position in `stw` (lanes 0..17: its zc_chess_state words) by move m, into
 // L.st, and its generation, with the child's squares kept in registers (one LDS round trip
-// fewer than staging the parent in L.st and applying the move there).
-template <bool PROBE = false>
+// fewer than staging the parent in L.st and applying the move there).  The generation is
+// legal_moves_probe's: a position with a legal move comes back lazy, its list not generated.
 __device__ __forceinline__ NodeGen create_child_gen(CLds &L, uint32_t stw, uint32_t m) {
     const uint32_t lane = lane_id();
     uint32_t w16;
@@ -128,10 +128,8 @@ __device__ __forceinline__ NodeGen create_child_gen(CLds &L, uint32_t stw, uint3
     wave_sync_mem();
     bool check, lazy = false;
     CSTAMP_T(cs8);
-    const int n = PROBE ? chessdev::legal_moves_probe(L.st.board, x, (int)(w16 & 0xFFu), L.s.legal, L.s.pseudo,
-                                                      L.s.region, check, lazy)
-                        : chessdev::legal_moves_check(L.st.board, x, (int)(w16 & 0xFFu), L.s.legal, L.s.pseudo,
-                                                      L.s.region, check);
+    const int n = chessdev::legal_moves_probe(L.st.board, x, (int)(w16 & 0xFFu), L.s.legal, L.s.pseudo, L.s.region,
+                                              check, lazy);
     CSTAMP_ADD(8, cs8);
     CSTAMP_T(cs9);
     const int32_t mat = chessdev::material(x);
