@@ -794,6 +794,15 @@ int zc_gen_end(zc_engine *eng, int32_t *d_out, int32_t *d_root_na, int32_t na_ca
  * DEVICE for n inputs: out[i] = na[i]==0 ? +inf : fma(c, sqrt(logn[i]/na[i]), q[i]). */
 int zc_debug_uct(zc_engine *eng, int32_t n, const double *logn, const int32_t *na, const double *q,
                  double c, double *out);
+/* The Connect4 rollout search's UCT choice (c4_search.hip uct_select8) ON THE DEVICE at n node
+ * records: child[8n] (0xFFFF = no child), na[8n], wa[8n] (0 <= Na <= N, |Wa| <= Na), big_n[n]
+ * (1 <= N <= max_sims + 1), with the margin the engine's searches use for this c.  out_slot[i] =
+ * the slot the walk enters (-1: no child; the first unvisited slot if there is one), out_how[i]
+ * = 0 a single fp32 candidate (or an unvisited slot), 1 a tie of equal (Na, Wa) pairs, 2 the
+ * level was decided by the fp64 fallback. */
+int zc_debug_c4_uct_select(zc_engine *eng, int32_t n, const uint16_t *child, const int32_t *na,
+                           const int32_t *wa, const int32_t *big_n, double c, int32_t *out_slot,
+                           int32_t *out_how);
 /* Value('random_rollout') on the device for n positions, game i using engine game
  * first_game+i's stream: out_value[i] in {-1,0,1}, out_words[i] = words consumed. */
 int zc_debug_c4_rollout(zc_engine *eng, int32_t first_game, int32_t n, const zc_c4_state *states,

@@ -25,10 +25,13 @@ the leaf loop itself and the others in a loop of their own — and prints
     224-word bulk step of the draw-ring stream), all of its branches counted, per step and
     per 64 generated words, and the instructions of a view (from the refill's join to the
     lane's word: a ds_bpermute_b32 of the window registers, or a byte read of the draw ring);
+  * the flush outside the rollouts (flush_budget below): a level of the prefetching walk, stage
+    1a of the planned flush, the draw table + chase, stages 2-3, backup + publish;
   * next_free_vgpr and the private segment size of c4_selfplay_kernel<false> and
     c4_search_kernel<false,false>.
 
-profiles/c4_rollout_isa_budget.txt keeps the output for the code before and after a change.
+profiles/c4_rollout_isa_budget.txt and profiles/c4_flush_isa_budget.txt keep the output for the
+code before and after a change.
 """
 import argparse
 import os
@@ -200,6 +203,66 @@ def stream_budget(blocks, byname, head, out):
     return {"refill": n, "words": words, "per64": n * 64 / words, "view": nview}
 
 
+def flush_budget(blocks, byname, Lh, out):
+    """The flush outside the rollouts (select_flush_plan, backup, publish), by the same columns.
+
+    The flush loop is the loop around the leaf loop.  In it, in layout order: the prefetching
+    walk (the loop whose latch moves the chosen child's slots over with three ds_bpermute_b32;
+    a level = the cheapest trip round it through the UCT scores, told by their square root:
+    v_sqrt_f32 for the fp32 decision, v_rsq_f64 for fp64), stage 1a (the flush loop's own blocks
+    between the walk and the chase, each once: X0's step, the terminal node's and, when the
+    chain is built by runs, one run with its fill; and where the compiler kept a loop there, the
+    per-node chain, the cheapest trip round it = one more chain node), the draw table + chase
+    (the block of unrolled s_bitset1_b64), stages 2-3
+    (the flush loop's own blocks from there to the rollouts, each once, rare paths included) and
+    backup + publish (every block after the leaf loop, each once)."""
+    pos = {b.name: i for i, b in enumerate(blocks)}
+    nops = lambda b, op: sum(o == op for o, _ in b.ins)
+    chase = next(b for b in blocks if nops(b, "s_bitset1_b64") >= 16)
+    # the innermost loop around both the leaf loop and the chase
+    F = next(h for h in loop_chain(byname, byname[Lh]) if h in loop_chain(byname, chase))
+    inF = [b for b in blocks if F in loop_chain(byname, b)]
+    inside = lambda h: [b for b in inF if h in loop_chain(byname, b)]
+    latch = next(b for b in inF if nops(b, "ds_bpermute_b32") >= 3 and b.loop != F and pos[b.name] < pos[chase.name])
+    W = latch.loop
+    wnames = {b.name for b in inside(W)}
+    trips = all_paths(byname, W, W, wnames)
+    res = {}
+
+    def trip_through(mark):
+        ps = [p[:-1] for p in trips if has(byname, p[:-1], mark)]
+        return min(ps, key=lambda p: cost(byname, p)) if ps else None
+
+    fast, slow = trip_through("v_sqrt_f32"), trip_through("v_rsq_f64")
+    print(f"flush loop {F}, walk loop {W}, chase in {chase.name}", file=out)
+    for name, p in (("walk level, fp32 decision", fast), ("walk level, fp64 scores", slow)):
+        if p:
+            fp64 = sum(op.endswith("_f64") or "_f64_" in op for b in p for op, _ in byname[b].ins)
+            print(f"flush {name:<28} {fmt_counts(byname, p)}  (fp64 {fp64})  " + " ".join(p), file=out)
+            res[name] = cost(byname, p)
+    wend = max(pos[n] for n in wnames)
+    once = [b.name for b in inF if b.loop == F and wend < pos[b.name] < pos[chase.name]]
+    print(f"flush {'stage 1a, blocks once':<28} {fmt_counts(byname, once)}  {len(once)} blocks", file=out)
+    res["stage1a"] = cost(byname, once)
+    between = {b.loop for b in inF if b.loop not in (F, W) and wend < pos[b.name] < pos[chase.name]}
+    if between:
+        S = max(between, key=lambda h: sum(b.n() for b in inside(h)))
+        snames = {b.name for b in inside(S)}
+        steps = [p[:-1] for p in all_paths(byname, S, S, snames)]
+        p = min(steps, key=lambda p: cost(byname, p))
+        print(f"flush {'stage 1a, one step':<28} {fmt_counts(byname, p)}  " + " ".join(p), file=out)
+        res["step"] = cost(byname, p)
+    print(f"flush {'draw table + chase':<28} {fmt_counts(byname, [chase.name])}  {chase.name}", file=out)
+    first_leaf = min(pos[b.name] for b in inF if Lh in loop_chain(byname, b))
+    last_leaf = max(pos[b.name] for b in inF if Lh in loop_chain(byname, b))
+    st23 = [b.name for b in inF if b.loop == F and pos[chase.name] < pos[b.name] < first_leaf]
+    tail = [b.name for b in inF if pos[b.name] > last_leaf]
+    print(f"flush {'stages 2-3':<28} {fmt_counts(byname, st23)}  {len(st23)} blocks", file=out)
+    print(f"flush {'backup + publish':<28} {fmt_counts(byname, tail)}  {len(tail)} blocks", file=out)
+    res.update(chase=chase.n(), stages23=cost(byname, st23), tail=cost(byname, tail))
+    return res
+
+
 def analyse(lines, out):
     fn, blocks = parse_function(lines, KERNEL)
     byname = {b.name: b for b in blocks}
@@ -255,6 +318,11 @@ def analyse(lines, out):
     print(file=out)
     res = {name: cost(byname, p) for name, p in paths}
     res["stream"] = stream_budget(blocks, byname, nofill, out)
+    print(file=out)
+    try:
+        res["flush"] = flush_budget(blocks, byname, Lh, out)
+    except (StopIteration, ValueError, IndexError) as e:  # its markers moved: the rollout budget still stands
+        print(f"flush section: markers not found ({type(e).__name__})", file=out)
     print(file=out)
     text = "\n".join(lines)
     for key in [KERNEL] + ALSO:

@@ -305,6 +305,9 @@ SIGNATURES = [
     ("zc_gen_end", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     ("zc_debug_uct", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p]),
+    ("zc_debug_c4_uct_select", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+                                              ctypes.c_void_p]),
     ("zc_debug_chess_probe_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_void_p]),
     ("zc_debug_chess_tree", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
@@ -786,6 +789,22 @@ class NativeEngine:
         out = np.zeros(len(logn), np.float64)
         check(lib().zc_debug_uct(self._h, len(logn), _ptr(logn), _ptr(na), _ptr(q), float(c), _ptr(out)))
         return out
+
+    def debug_c4_uct_select(self, child, na, wa, big_n, c: float):
+        """The rollout search's UCT choice at node records child/na/wa [n, 8], big_n [n]:
+        (slot [n], how [n]); how = 0 one fp32 candidate, 1 a tie of equal pairs, 2 fp64 fallback."""
+        child = np.ascontiguousarray(child, np.uint16).reshape(-1, 8)
+        na = np.ascontiguousarray(na, np.int32).reshape(-1, 8)
+        wa = np.ascontiguousarray(wa, np.int32).reshape(-1, 8)
+        big_n = np.ascontiguousarray(big_n, np.int32).reshape(-1)
+        n = len(big_n)
+        if not (len(child) == len(na) == len(wa) == n):
+            raise ValueError("child, na, wa must be [n, 8] for big_n [n]")
+        slot = np.zeros(n, np.int32)
+        how = np.zeros(n, np.int32)
+        check(lib().zc_debug_c4_uct_select(self._h, n, _ptr(child), _ptr(na), _ptr(wa), _ptr(big_n), float(c),
+                                           _ptr(slot), _ptr(how)))
+        return slot, how
 
     def phase_cycles_games(self, n: int) -> np.ndarray:
         """Per-game stamp cycles [n, 8] accumulated since the last phase_cycles() reset."""

@@ -132,6 +132,14 @@ __device__ __forceinline__ void set_prio(int lvl) {
     else if (lvl == 1) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(0);
 }
+// Counter builds reuse the stats' rollout_plies / rollout_blocks words for counts of their own:
+// -DZC_DIAG_WASTE (tools/rollout_stats.py): absorbed fills played / wasted; -DZC_DIAG_UCT: the
+// walk's contested levels (more than one fp32 candidate) / the levels that took the fp64 path.
+#if defined(ZC_DIAG_WASTE) || defined(ZC_DIAG_UCT)
+#define ZC_ROLLOUT_COUNTS 0
+#else
+#define ZC_ROLLOUT_COUNTS 1
+#endif
 #ifndef ZC_RSTAMP
 #define ZC_RSTAMP 0  // diagnostic build: 1..6 = accumulate one rollout region's cycles into *sub
 #endif
@@ -186,7 +194,7 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
             room_v = has_four(op_v) ? -2 : 41 - __popcll(x0 | x1);
             const uint64_t oc = x0 | x1;  // column heights, 4 bits per column
             for (int c = 0; c < 7; ++c) hp_v |= (uint32_t)__popcll((oc >> (7 * c)) & 0x3Full) << (4 * c);
-#ifndef ZC_DIAG_WASTE
+#if ZC_ROLLOUT_COUNTS
             cn.blocks += room_v >= 0 ? 1 : 0;  // a rollout's first block (the others: where it goes on)
 #endif
         }
@@ -333,7 +341,7 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
             // through the odd plies <= endply (row 1, inclusive scan at lane 15 + (endply+1)/2;
             // none when endply = 0)
             auto go_on = [&]() __attribute__((always_inline)) {
-#ifndef ZC_DIAG_WASTE
+#if ZC_ROLLOUT_COUNTS
                 cn.add(cn.blocks, 1);
 #endif
                 {
@@ -377,7 +385,7 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
         q_v = zc_writelane(q, jl, q_v);
       }
       if (g + (int)lane < jend) L[g + (int)lane].val = val_v;
-#ifndef ZC_DIAG_WASTE
+#if ZC_ROLLOUT_COUNTS
       cn.plies += q_v;  // lane-parallel (Counters)
 #endif
     }
@@ -454,8 +462,11 @@ __device__ void c4_rollouts_philox(Leaf *L, int nb, const uint8_t *s_sel, uint2 
 // n_i - (d - d_i) moves.  _randbelow(cnt) accepts a word when its top three bits t3 are below
 // T(cnt) (4, 4, 6, 4, 5, 6, 7 for cnt = 1..7): four acceptance classes c = T - 4.
 // select_flush_plan therefore
-//   (1a) walks the chain's shape on the scalar unit (boards, counts, first draws; each node's
-//        fields go to VGPR lane i by v_writelane, no LDS table, no exec juggling);
+//   (1a) walks the chain's shape (boards, counts, first draws; node i's fields go to lane i of
+//        six VGPRs, no LDS table): X0 and a terminal node by v_writelane, the nodes between
+//        them a RUN at a time — the nodes up to the next column fill differ only by a stack of
+//        stones in one column, so the scalar unit does one step per fill and the run's lanes
+//        write their own fields;
 //   (1b) builds, lane-parallel, a NEXT table over the 64-word view: lane l, byte c = 1 + the
 //        first word >= l (of words 0..61) that a class-c draw accepts, or 63 (none; lanes 62
 //        and 63 hold 63 in every byte, so the chase stays there);
@@ -473,20 +484,100 @@ __device__ void c4_rollouts_philox(Leaf *L, int nb, const uint8_t *s_sel, uint2 
 // records leaf paths for the stepwise search).  The fresh in-edges' counters are not zeroed
 // here: the planned flush's backup (search_move, fs.planned) writes them from one prefix sum.
 
+// bit j n, j = 0, 1, ...: where nodes that take n draws each start theirs (index n = 1..7)
+__constant__ const uint64_t kEvery[8] = {0ull,
+                                         0xFFFFFFFFFFFFFFFFull,
+                                         0x5555555555555555ull,
+                                         0x9249249249249249ull,
+                                         0x1111111111111111ull,
+                                         0x1084210842108421ull,
+                                         0x1041041041041041ull,
+                                         0x8102040810204081ull};
+
 __device__ __forceinline__ uint64_t lanes_in(int lo, int hi) {  // lanes lo .. hi-1 (0 <= lo <= hi <= 64)
     const uint64_t below_hi = hi >= 64 ? ~0ull : (1ull << hi) - 1ull;
     return below_hi & ~((1ull << lo) - 1ull);
 }
 
+// The UCT child of a node whose children are all visited: the first maximum, in slot order, of
+// U_k = fma(c, sqrt(log N / Na_k), Wa_k / Na_k) in fp64 (mcts.cpp:41-58).  The search needs that
+// ARGMAX, not the doubles, so the decision is taken in fp32 and fp64 runs only where fp32 cannot
+// tell.  Lane k (lanes 8.. mirror 0..7) holds slot k; `vmask` = the slots with a child (not 0).
+//
+//   S_k = fmaf(cf, sqrt(lgf * rcp(na)), wa * rcp(na)),   cf = (float)c, lgf = (float)log N
+//
+// with the hardware's v_rcp_f32 / v_sqrt_f32 (1 ulp each); na and wa are below 2^24, so their
+// conversions are exact.  With u = 2^-24 (half an ulp) the relative errors are: lgf u, rcp 2u,
+// their product 4u, its square root 2u + 2u = 4u, times cf (u) 5u; wa * rcp 3u; the fma's
+// rounding u of the sum.  With |Wa| <= Na and 1 <= Na <= N:
+//
+//   |S_k - U_k| <= u * (6 |c| sqrt(log N) + 4) (1 + O(u))  <  E = 2^-23 * (6 |c| sqrt(log N) + 4)
+//
+// (the fp64 roundings, ~2^-53 relative, and the rounding of m - delta below, u |m|, sit inside the
+// factor 2 as well).  E grows with N, so the host takes N = max_sims + 1 and passes delta = 2 E
+// (uct_fast_delta, zc_internal.h).  Let m = max S_k and C = {k : S_k >= m - delta}.  A slot outside C
+// has U_j < S_j + E < m - E <= U of the slot holding m, so the fp64 maximum lies in C:
+//   |C| = 1                       -> that slot;
+//   all of C share one (Na, Wa)   -> their U are the same double: the first slot of C (the
+//                                    reference's first-max rule; the usual tie of fresh children);
+//   otherwise                     -> this level in fp64, as before.
+// C is kept as "not (S_k < m - delta)", so a NaN or an infinite score (a non-finite c or (float)c:
+// delta = +inf) stays a candidate and such a level falls back unless it is a tie of equals.
+
+// The maximum over each 8-lane half row, in every lane of it: three v_max_f32 with the DPP operand
+// in the instruction (fmaxf on a DPP move compiles to the move, a canonicalising v_max of each
+// operand and the v_max: 4 instructions a step).  The s_nop is the two wait states a DPP read
+// of a VGPR needs after the VALU write, which the compiler cannot see into the asm to insert.
+// v_max_f32 returns the other operand for a NaN, as fmaxf does.
+__device__ __forceinline__ float max8(float v) {
+    float m;
+    __asm__("s_nop 1\n\t"
+            "v_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "s_nop 1\n\t"
+            "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "s_nop 1\n\t"
+            "v_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf"
+            : "=&v"(m)
+            : "v"(v));
+    return m;
+}
+// *how (diagnostics): 0 = one candidate, 1 = a tie of equal pairs, 2 = decided in fp64
+__device__ __forceinline__ int uct_select8(uint64_t vmask, int32_t na, int32_t wa, double lg, double c, float cf,
+                                           float delta, int *how = nullptr) {
+    const float r = __builtin_amdgcn_rcpf((float)na);
+    const float s = __builtin_amdgcn_sqrtf((float)lg * r);
+    const float S = __builtin_fmaf(cf, s, (float)wa * r);
+    const float Sv = __uint_as_float(mask_sel(vmask, 0xFF800000u, __float_as_uint(S)));  // no child: -inf
+    const float thr = max8(Sv) - delta;
+    const uint64_t C = vmask & ~__ballot(Sv < thr);
+    const int first = __builtin_ctzll(C);
+    if (how) *how = 0;
+    if ((C & (C - 1ull)) == 0ull) return first;
+    const int32_t na0 = __builtin_amdgcn_readlane(na, first), wa0 = __builtin_amdgcn_readlane(wa, first);
+    if (how) *how = 1;
+    if ((C & ~__ballot(((na ^ na0) | (wa ^ wa0)) == 0)) == 0ull) return first;
+    if (how) *how = 2;
+    const bool valid = (vmask >> (lane_id() & 7u)) & 1ull;
+    const double q = valid ? (double)wa / (double)na : 0.0;
+    const double v = valid ? fma(c, sqrt(lg / (double)na), q) : -INFINITY;
+    int bi;
+    max8_first(v, &bi);
+    return bi;
+}
+
 // walk_hbm (c4_device.h) for the rollout search, with the next level's record fetched while
 // the current level's UCT is computed: lane 8c + k loads slot k (child, Na, Wa) and header word
 // k & 3 of child c's record as soon as the node's children are known, so the memory latency of
-// a level hides under the previous level's fp64 arithmetic; the chosen child's slots then move
-// to lanes k by three bpermutes.  Same walk, same path, same result.
+// a level hides under the previous level's arithmetic; the chosen child's slots then move
+// to lanes k by three bpermutes.  The UCT child comes from uct_select8.  Same walk, same path,
+// same result.
 __device__ __forceinline__ WalkEnd walk_hbm_prefetch(const Tree &t, ConstDouble *logtab, uint64_t rp0, uint64_t rp1,
-                                                     int rturn, int done, double c, int &status) {
+                                                     int rturn, int done, double c, float delta, Counters &cn,
+                                                     int &status) {
     const uint32_t lane = lane_id();
     const uint32_t k = lane & 7u, cs = lane >> 3;  // the slot this lane scores / the child it fetches
+    const float cf = (float)c;
+    (void)cn;  // counts only in the -DZC_DIAG_UCT build
     int node = 0, depth = 0, turn = rturn, nN = done;  // nN = N(node) = Na of its in-edge
     uint64_t b0 = rp0, b1 = rp1;
     uint32_t pathv = (lane == 0) ? 0x00FF0000u : 0u;
@@ -515,19 +606,22 @@ __device__ __forceinline__ WalkEnd walk_hbm_prefetch(const Tree &t, ConstDouble 
             pwa = ((const int32_t *)(Rc + 64))[k];
         }
         const double lg = logtab[nN];  // log(N), glibc values tabulated on the host
-        const bool valid = k < nm && ch != 0xFFFF;
         int best;
-        const uint64_t unvisited = ((1ull << nm) - 1ull) & __ballot(ch != 0xFFFF) & __ballot(na == 0) & 0xFFull;
+        const uint64_t vmask = ((1ull << nm) - 1ull) & __ballot(ch != 0xFFFF) & 0xFFull;  // slots with a child
+        const uint64_t unvisited = vmask & __ballot(na == 0);
+        if (vmask == 0ull) break;  // no child: terminal leaf
         if (unvisited) {  // +inf beats everything; first such slot
             best = __builtin_ctzll(unvisited);
         } else {
             // UCT (mcts.cpp:41-45) = fma(c, sqrt(log(N)/Na), Qa), first max in slot order
-            const double q = valid ? (double)wa / (double)na : 0.0;
-            const double v = valid ? fma(c, sqrt(lg / (double)na), q) : -INFINITY;
-            int bi;
-            const double mx = max8_first(v, &bi);
-            if ((__ballot(mx == -INFINITY) & 1ull) != 0) break;  // no child: terminal leaf
-            best = bi;
+#ifdef ZC_DIAG_UCT
+            int how;
+            best = uct_select8(vmask, na, wa, lg, c, cf, delta, &how);
+            cn.add(cn.plies, how != 0);
+            cn.add(cn.blocks, how == 2);
+#else
+            best = uct_select8(vmask, na, wa, lg, c, cf, delta);
+#endif
         }
         nN = __builtin_amdgcn_readlane(na, best);
         const uint64_t bit = drop_bit(b0 | b1, (int)((ow >> (3 * best)) & 7u));
@@ -597,12 +691,12 @@ template <bool STAMP, class RNG>
 __device__ __forceinline__ void select_flush_plan(const Tree &t, Fresh *fresh, Leaf *leaves, const uint32_t *s_order,
                                                   ConstDouble *logtab, RNG &rng, Counters &cn, Stamp<STAMP> &stamp,
                                                   int &nnodes, int &status, uint64_t rp0, uint64_t rp1, int rturn,
-                                                  int done, int nb, double c, FlushSel &fs) {
+                                                  int done, int nb, double c, float delta, FlushSel &fs) {
     const uint32_t lane = lane_id();
     const int f0 = nnodes;
     for (int i = (int)lane; i < nb; i += 64)  // fresh slots: no children (the in-edge counters: the backup)
         *(uint4 *)fresh[i].ch = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-    const WalkEnd we = walk_hbm_prefetch(t, logtab, rp0, rp1, rturn, done, c, status);
+    const WalkEnd we = walk_hbm_prefetch(t, logtab, rp0, rp1, rturn, done, c, delta, cn, status);
     fs.f0 = f0;
     fs.x0node = we.node;
     fs.d0 = we.depth;
@@ -630,33 +724,83 @@ __device__ __forceinline__ void select_flush_plan(const Tree &t, Fresh *fresh, L
     int d = 0, i = 0, T = -1;
     uint64_t Sm = 0;  // bit s: a chain node's first draw
     int v_b0l = 0, v_b0h = 0, v_b1l = 0, v_b1h = 0, v_ow = 0, v_cd = 0;  // v_cd: cm | first draw << 8 | n << 16
-    for (;;) {
-        const int m = min((int)n, nb - d);
-        write_lane(v_b0l, (uint32_t)b0, i);
-        write_lane(v_b0h, (uint32_t)(b0 >> 32), i);
-        write_lane(v_b1l, (uint32_t)b1, i);
-        write_lane(v_b1h, (uint32_t)(b1 >> 32), i);
-        write_lane(v_ow, ow, i);
-        write_lane(v_cd, cm | ((uint32_t)d << 8) | (n << 16), i);
-        if (m == 0) {  // a chain node without moves: the flush's remaining leaves are all it
-            T = i;
-            break;
+    // Below X0 every node is entered through slot 0 of its own order word, so while no column
+    // fills consecutive chain nodes share ow, cm and n and drop into the same column ow & 7: a RUN
+    // of nodes that differ only in how many stones are stacked in that column (alternating
+    // sides) and in their first draw d + j n.  The serial dependence is per fill, not per node:
+    // the scalar unit does one step per run (its column and height, its length from one ballot,
+    // the fill's legal set) and the run's lanes write their own node's fields.  A run ends when
+    // its column's stone reaches the top row or when the flush's draws run out.  X0 (its lowest
+    // untried slot, cnt0 draws) and the terminal node T stay steps of their own.
+    auto put_node = [&](int at) __attribute__((always_inline)) {
+        write_lane(v_b0l, (uint32_t)b0, at);
+        write_lane(v_b0h, (uint32_t)(b0 >> 32), at);
+        write_lane(v_b1l, (uint32_t)b1, at);
+        write_lane(v_b1h, (uint32_t)(b1 >> 32), at);
+        write_lane(v_ow, ow, at);
+        write_lane(v_cd, cm | ((uint32_t)d << 8) | (n << 16), at);
+    };
+    // a stack of plies (bit k: ply k, side `turn` moving first) onto the boards, ply 0 at cell `at`
+    auto stack_on = [&](uint32_t plies, int at) __attribute__((always_inline)) {
+        const uint32_t own = turn ? 0x2Au : 0x15u;  // the plies that land on b0
+        b0 |= (uint64_t)(plies & own) << at;
+        b1 |= (uint64_t)(plies & (own ^ 0x3Fu)) << at;
+    };
+    put_node(0);  // X0: draws 0 .. min(cnt0, nb) - 1
+    Sm = 1ull;
+    d = min((int)n, nb);
+    i = 1;
+    if (d < nb) {
+        {  // the next walk enters X0's lowest untried slot
+            const int col = (int)((ow >> (3 * slot)) & 7u);
+            const uint64_t bit = drop_bit(b0 | b1, col);
+            if (turn) b1 |= bit; else b0 |= bit;
+            turn ^= 1;
+            if (bit & kTop) {
+                cm &= ~(1u << col);
+                ow = uni(s_order[cm]);
+            }
+            n = (ow >> 24) & 15u;
         }
-        Sm |= 1ull << d;
-        d += m;
-        if (d >= nb) break;
-        // the next walk enters this node's lowest untried slot
-        const int col = (int)((ow >> (3 * slot)) & 7u);
-        const uint64_t bit = drop_bit(b0 | b1, col);
-        if (turn) b1 |= bit; else b0 |= bit;
-        turn ^= 1;
-        if (bit & kTop) {
+        for (;;) {  // one run per iteration
+            if (n == 0) {  // a chain node without moves: the flush's remaining leaves are all it
+                put_node(i);
+                T = i;
+                break;
+            }
+            const int col = (int)(ow & 7u), at0 = 7 * col;
+            const int h = __popcll(((b0 | b1) >> at0) & 0x3Full);  // the column's height (< 6: it is legal)
+            // lane i + j: the run's node j, j stones up the column, first draw d + j n
+            const int jl = (int)lane - i;
+            const uint32_t first = (uint32_t)d + (uint32_t)jl * n;
+            const uint64_t Rm = __ballot(jl >= 0 && jl <= 5 - h && (int)first < nb);  // lanes i .. i + L - 1
+            const int L = __popcll(Rm);
+            {
+                const uint32_t plies = (1u << ((uint32_t)jl & 7u)) - 1u, own = turn ? 0x2Au : 0x15u;
+                const uint64_t n0 = b0 | ((uint64_t)(plies & own) << (at0 + h));
+                const uint64_t n1 = b1 | ((uint64_t)(plies & (own ^ 0x3Fu)) << (at0 + h));
+                v_b0l = (int)mask_sel(Rm, (uint32_t)v_b0l, (uint32_t)n0);
+                v_b0h = (int)mask_sel(Rm, (uint32_t)v_b0h, (uint32_t)(n0 >> 32));
+                v_b1l = (int)mask_sel(Rm, (uint32_t)v_b1l, (uint32_t)n1);
+                v_b1h = (int)mask_sel(Rm, (uint32_t)v_b1h, (uint32_t)(n1 >> 32));
+                v_ow = (int)mask_sel(Rm, (uint32_t)v_ow, ow);
+                v_cd = (int)mask_sel(Rm, (uint32_t)v_cd, cm | (first << 8) | (n << 16));
+            }
+            const int dn = d + L * (int)n;  // < nb + 7
+            Sm |= (kEvery[n] << d) & lanes_in(0, min(dn, 64));
+            i += L;
+            if (dn >= nb) {  // the draws ran out in this run
+                d = nb;
+                break;
+            }
+            // the run filled its column (L = 6 - h): its stones, then the new legal set
+            d = dn;
+            stack_on((1u << L) - 1u, at0 + h);
+            turn ^= L & 1;
             cm &= ~(1u << col);
             ow = uni(s_order[cm]);
+            n = (ow >> 24) & 15u;
         }
-        n = (ow >> 24) & 15u;
-        slot = 0;
-        ++i;
     }
     const int D = d;  // fresh nodes f0 .. f0 + D - 1
 
@@ -889,7 +1033,7 @@ __device__ __forceinline__ void search_move(const SearchParams &p, const SearchL
             if (p.bs < 64)
                 select_flush_plan<STAMP>(t, fresh, leaves, s_order, logtab, rng, cn, stamp, nnodes, status,
                                          uni64(root.stones[0]), uni64(root.stones[1]), uni(root.turn), done, nb,
-                                         p.c, fs);
+                                         p.c, p.uct_delta, fs);
             else
                 select_flush<false, STAMP>(t, fresh, leaves, nullptr, s_order, logtab, rng, cn, stamp, nnodes,
                                            status, uni64(root.stones[0]), uni64(root.stones[1]), uni(root.turn),
@@ -1412,6 +1556,34 @@ __global__ void uct_debug_kernel(int n, const double *logn, const int32_t *na, c
     out[i] = na[i] == 0 ? INFINITY : fma(c, sqrt(logn[i] / (double)na[i]), q[i]);
 }
 
+// The walk's choice at n node records (zc_debug_c4_uct_select): per node 8 slots of (child, Na,
+// Wa) and N; out_slot = the slot the walk enters (-1: no child), out_how = 0 decided by one fp32
+// candidate (or by the unvisited-slot rule), 1 = a tie of equal pairs, 2 = decided in fp64.
+__global__ __launch_bounds__(kBlock) void c4_uct_select_debug_kernel(int n, const uint16_t *ch, const int32_t *na,
+                                                                     const int32_t *wa, const int32_t *bigN,
+                                                                     const double *logtab, double c, float delta,
+                                                                     int32_t *out_slot, int32_t *out_how) {
+    const uint32_t lane = lane_id();
+    const uint32_t k = lane & 7u;
+    const float cf = (float)c;
+    for (int i = (int)blockIdx.x; i < n; i += (int)gridDim.x) {
+        const uint32_t chk = ch[8 * (size_t)i + k];
+        const int32_t nak = na[8 * (size_t)i + k], wak = wa[8 * (size_t)i + k];
+        const double lg = ((ConstDouble *)logtab)[uni(bigN[i])];
+        const uint64_t vmask = __ballot(chk != 0xFFFF) & 0xFFull;
+        const uint64_t unvisited = vmask & __ballot(nak == 0);
+        int best = -1, how = 0;
+        if (vmask != 0ull) {
+            if (unvisited) best = __builtin_ctzll(unvisited);
+            else best = uct_select8(vmask, nak, wak, lg, c, cf, delta, &how);
+        }
+        if (lane == 0) {
+            out_slot[i] = best;
+            out_how[i] = how;
+        }
+    }
+}
+
 }  // namespace
 
 // Games per workgroup: up to kSearchWaves share the tables (4 x ~8.6 KB + 2 KB at bs 32, so
@@ -1499,6 +1671,13 @@ void launch_c4_play(int n, zc_c4_state *states, const int32_t *moves, int32_t *r
 void launch_uct_debug(int n, const double *logn, const int32_t *na, const double *q, double c, double *out,
                       hipStream_t s) {
     hipLaunchKernelGGL(uct_debug_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, logn, na, q, c, out);
+}
+
+void launch_c4_uct_select_debug(int n, const uint16_t *ch, const int32_t *na, const int32_t *wa, const int32_t *bigN,
+                                const double *logtab, double c, float delta, int32_t *out_slot, int32_t *out_how,
+                                hipStream_t s) {
+    hipLaunchKernelGGL(c4_uct_select_debug_kernel, dim3(n < 8192 ? n : 8192), dim3(kBlock), 0, s, n, ch, na, wa, bigN,
+                       logtab, c, delta, out_slot, out_how);
 }
 
 }  // namespace zc

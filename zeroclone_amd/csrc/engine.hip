@@ -244,6 +244,7 @@ zc::SearchParams make_params(zc_engine *e, int32_t first, int32_t n, const zc_c4
     p.bs = bs;
     p.M = e->M;
     p.c = c;
+    p.uct_delta = zc::uct_fast_delta(c, e->M);
     p.roots = roots;
     p.out_move = mv;
     p.out_na = na;
@@ -1864,6 +1865,47 @@ int zc_debug_uct(zc_engine *eng, int32_t n, const double *logn, const int32_t *n
     (void)hipFree(dout);
     (void)hipFree(dn);
     return ZC_OK;
+}
+
+int zc_debug_c4_uct_select(zc_engine *eng, int32_t n, const uint16_t *child, const int32_t *na, const int32_t *wa,
+                           const int32_t *big_n, double c, int32_t *out_slot, int32_t *out_how) {
+    if (!eng || n < 0 || (n && (!child || !na || !wa || !big_n || !out_slot || !out_how)))
+        return fail(ZC_EINVAL, "bad argument");
+    for (int32_t i = 0; i < n; ++i) {
+        if (big_n[i] < 1 || big_n[i] > eng->M) return fail(ZC_EINVAL, "node %d: N outside [1, max_sims + 1]", i);
+        for (int k = 0; k < 8; ++k) {
+            const int32_t a = na[8 * (size_t)i + k], w = wa[8 * (size_t)i + k];
+            if (a < 0 || a > big_n[i] || w < -a || w > a)
+                return fail(ZC_EINVAL, "node %d slot %d: need 0 <= Na <= N and |Wa| <= Na", i, k);
+        }
+    }
+    if (!n) return ZC_OK;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    ZC_HIP(hipSetDevice(eng->cfg.device));
+    const size_t slots = 8 * (size_t)n;
+    uint8_t *blk;  // na, wa [8n] | N, slot, how [n] | child [8n]
+    ZC_HIP(hipMalloc(&blk, slots * 10 + (size_t)n * 12));
+    int32_t *dna = (int32_t *)blk, *dwa = dna + slots, *dn = dwa + slots, *dslot = dn + n, *dhow = dslot + n;
+    uint16_t *dch = (uint16_t *)(dhow + n);
+    hipStream_t s = eng->stream;
+    int r = ZC_OK;
+    auto hip = [&](hipError_t e) {
+        if (e != hipSuccess && r == ZC_OK) r = fail(ZC_EHIP, "%s", hipGetErrorString(e));
+    };
+    hip(hipMemcpyAsync(dna, na, slots * 4, hipMemcpyHostToDevice, s));
+    hip(hipMemcpyAsync(dwa, wa, slots * 4, hipMemcpyHostToDevice, s));
+    hip(hipMemcpyAsync(dn, big_n, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    hip(hipMemcpyAsync(dch, child, slots * 2, hipMemcpyHostToDevice, s));
+    if (r == ZC_OK) {
+        zc::launch_c4_uct_select_debug(n, dch, dna, dwa, dn, eng->a.logtab, c, zc::uct_fast_delta(c, eng->M), dslot,
+                                       dhow, s);
+        hip(hipGetLastError());
+    }
+    hip(hipMemcpyAsync(out_slot, dslot, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    hip(hipMemcpyAsync(out_how, dhow, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    hip(hipStreamSynchronize(s));
+    (void)hipFree(blk);
+    return r;
 }
 
 int zc_debug_c4_rollout(zc_engine *eng, int32_t first, int32_t n, const zc_c4_state *states, int32_t *out_value,

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <mutex>
@@ -81,9 +82,20 @@ enum : int {
     kCtlWords = 64,
 };
 
+// The margin of the walk's fp32 UCT decision (uct_select8, c4_search.hip): delta = 2 E with
+// E = 2^-23 * (6 |c| sqrt(log N) + 4), twice the first-order bound of |fp32 score - fp64 score|,
+// at the largest N the engine allows (n_max).  +inf when c or (float)c is not finite: every
+// contested level is then decided in fp64.  Rounded up on its way to fp32.
+inline float uct_fast_delta(double c, int n_max) {
+    if (!std::isfinite(c) || !std::isfinite((float)c)) return INFINITY;
+    const double E = std::ldexp(6.0 * std::fabs(c) * std::sqrt(std::log((double)(n_max < 2 ? 2 : n_max))) + 4.0, -23);
+    return (float)(2.0 * E * (1.0 + 0x1p-22));
+}
+
 struct SearchParams {
     int first_game, n_games, sims, bs, M;
     double c;
+    float uct_delta;  // uct_fast_delta(c, M)
     const int32_t *game_ids;  // optional: engine game of call entry i (else first_game + i)
     const zc_c4_state *roots;
     int32_t *out_move, *out_na;
@@ -416,6 +428,10 @@ void launch_traj_policy_dense(int n_rows, const int64_t *first, const int32_t *c
                               bool half, void *out, hipStream_t s);
 void launch_uct_debug(int n, const double *logn, const int32_t *na, const double *q, double c, double *out,
                       hipStream_t s);
+
+void launch_c4_uct_select_debug(int n, const uint16_t *ch, const int32_t *na, const int32_t *wa, const int32_t *bigN,
+                                const double *logtab, double c, float delta, int32_t *out_slot, int32_t *out_how,
+                                hipStream_t s);
 
 }  // namespace zc
 
