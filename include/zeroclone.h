@@ -159,6 +159,18 @@ int zc_c4_selfplay_carry_async(zc_engine *eng, int32_t first_game, int32_t n_gam
                                int32_t *d_ticket, zc_c4_state *d_out_states, int16_t *d_out_moves,
                                int32_t *d_out_results, zc_game_stats *d_stats, void *hip_stream);
 
+/* Optional per-step root visit counts of the three self-play launches above.  With a staging
+ * registered (device int32 [steps_cap][n_games][7]; NULL switches it off, the default) every
+ * later launch of this engine also writes the finished move's visits per column — the row
+ * zc_c4_search_async gives in d_out_root_na — to d_na[(k*n_games + i)*7 + col], beside step k's
+ * position, move and result.  A move suspended by a carry launch writes no row: the launch that
+ * finishes it writes it, at its own step index.  Steps a game did not reach are left unwritten
+ * (their result is ZC_SLOT_SKIP).  A launch whose moves / moves_cap exceeds steps_cap returns
+ * ZC_EINVAL and writes nothing.  The staging is read when a launch is enqueued, so it must stay
+ * allocated while launches that saw it are in flight.  zc_traj_policy_record_steps_async turns
+ * the rows into the trajectories' policy records. */
+int zc_c4_selfplay_visits(zc_engine *eng, int32_t *d_na, int32_t steps_cap);
+
 /* Drop the carried moves of games [first_game, first_game + n_games) (stream-ordered): their
  * next search starts afresh from whatever root they are given.  Their MT19937 streams stay
  * where the dropped searches left them, so those games' moves no longer follow an
@@ -475,6 +487,14 @@ int zc_chess_selfplay_pooled_async(zc_engine *eng, int32_t first_game, int32_t n
                                    int32_t *d_ticket, zc_chess_state *d_out_states, uint16_t *d_out_moves,
                                    int32_t *d_out_results, zc_game_stats *d_stats, void *hip_stream);
 int zc_chess_pooled_max_games(int32_t hist_cap, int32_t *out);
+/* The chess form of zc_c4_selfplay_visits: with d_na (device int32) and d_root_moves (device
+ * uint16), both [steps_cap][n_games][ZC_CHESS_MAX_MOVES], registered, the two launches above
+ * also write every move's root visit counts and the packed root moves that name them at
+ * [(k*n_games + i)*ZC_CHESS_MAX_MOVES + j], in the root's move-list order — the order of
+ * zc_chess_search_async's d_out_root_na and of zc_chess_legal_moves_async on that root; zeros
+ * past the root's moves.  d_na = NULL switches the output off (the default); a launch whose
+ * moves / moves_cap exceeds steps_cap returns ZC_EINVAL and writes nothing. */
+int zc_chess_selfplay_visits(zc_engine *eng, int32_t *d_na, uint16_t *d_root_moves, int32_t steps_cap);
 
 /* ---- Chess PUCT search (AlphaZero-style; no reference counterpart) -------
  * Selection by Q + c_puct * P * sqrt(sum N) / (1 + N) with priors P from a policy network,
@@ -748,6 +768,29 @@ int zc_traj_policy_append_async(int32_t n, const zc_traj_buffers *buf, const zc_
  * the entry pool cannot take sets bit 1 and gets first = count = 0 throughout. */
 int zc_traj_policy_commit_async(int32_t n, const zc_traj_buffers *buf, const zc_traj_policy_buffers *pol,
                                 void *hip_stream);
+/* The multi-step form of append + commit, as zc_traj_record_steps_async is of
+ * zc_traj_record_async: the visit counts of the `steps` steps of one self-play launch — d_na
+ * [steps][n][stride] and d_root_moves [steps][n][stride] (NULL: the index is the id) as
+ * zc_c4_selfplay_visits / zc_chess_selfplay_visits staged them, d_results the launch's
+ * [steps][n] results — recorded at once.  Call it BEFORE zc_traj_record_steps_async of the same
+ * launch, on the same stream: it reads the slot table (d_slot) and the counters (d_ctl) as the
+ * launch found them, which that call updates, and changes nothing of `buf`.  Afterwards
+ * d_pool_pi / d_pool_first / d_pool_count of the positions that call pools, the slots' CSR of
+ * the games still in progress and d_pctl hold, bit for bit, what `steps` rounds of
+ * (zc_traj_policy_append_async, zc_traj_record_async, zc_traj_policy_commit_async) leave: a
+ * finished game's entries are reserved in step-major, slot-minor order (a third scan beside
+ * that of games and positions), a game that starts and ends inside the launch goes straight
+ * from the staging to the pool, a game's last position has count 0, a finished game's slot
+ * restarts with off[0] = 0, and a game the trajectory pool drops reserves no entries.  The
+ * same ZC_TRAJ_PI_OVERFLOW bits are set for the same causes (the contents are then
+ * unspecified; nothing is written out of bounds).  Four launches whatever `steps` is.
+ * d_reached as for zc_traj_record_steps_async.  d_scratch: device scratch of at least
+ * zc_traj_policy_steps_scratch_bytes(n, steps) bytes, 16-byte aligned. */
+int zc_traj_policy_steps_scratch_bytes(int32_t n, int32_t steps, int64_t *bytes);
+int zc_traj_policy_record_steps_async(int32_t n, const zc_traj_buffers *buf, const zc_traj_policy_buffers *pol,
+                                      const int32_t *d_results, const int32_t *d_na, const uint16_t *d_root_moves,
+                                      int32_t stride, int32_t steps, const int32_t *d_reached, void *d_scratch,
+                                      int64_t scratch_bytes, void *hip_stream);
 /* Sparse records to dense training targets: d_out [n_rows][width], ZC_F32 or ZC_F16; row r
  * holds count / sum (one IEEE single-precision division; fp16: that float rounded to nearest)
  * of the entries d_entries[d_first[r] .. + d_count[r]) and zeros elsewhere (all zeros for a

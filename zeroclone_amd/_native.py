@@ -170,6 +170,13 @@ SIGNATURES = [
     ("zc_traj_record_steps_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_int64, ctypes.c_void_p]),
+    ("zc_c4_selfplay_visits", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
+    ("zc_chess_selfplay_visits", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
+    ("zc_traj_policy_steps_scratch_bytes", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, P(ctypes.c_int64)]),
+    ("zc_traj_policy_record_steps_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     ("zc_c4_hp_walk", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
                                      ctypes.c_void_p]),
     ("zc_c4_hp_expand", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
@@ -517,6 +524,17 @@ class NativeEngine:
                                                 ctypes.c_void_p(d_ticket), ctypes.c_void_p(d_states),
                                                 ctypes.c_void_p(d_moves16), ctypes.c_void_p(d_results),
                                                 ctypes.c_void_p(d_stats), ctypes.c_void_p(stream or None)))
+
+    def c4_selfplay_visits(self, d_na: int | None, steps_cap: int = 0) -> None:
+        """The self-play launches' per-step visit-count staging [steps_cap][n][7] int32
+        (zc_c4_selfplay_visits; None: off)."""
+        check(lib().zc_c4_selfplay_visits(self._h, ctypes.c_void_p(d_na or None), int(steps_cap)))
+
+    def chess_selfplay_visits(self, d_na: int | None, d_root_moves: int | None = None, steps_cap: int = 0) -> None:
+        """The chess self-play launches' staging of visit counts and root moves
+        [steps_cap][n][CHESS_MAX_MOVES] (zc_chess_selfplay_visits; None: off)."""
+        check(lib().zc_chess_selfplay_visits(self._h, ctypes.c_void_p(d_na or None),
+                                             ctypes.c_void_p(d_root_moves or None), int(steps_cap)))
 
     def c4_carry_discard(self, first_game: int, n: int, stream: int = 0) -> None:
         check(lib().zc_c4_carry_discard(self._h, int(first_game), int(n), ctypes.c_void_p(stream or None)))

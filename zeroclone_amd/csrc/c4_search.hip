@@ -1343,7 +1343,9 @@ __global__ __launch_bounds__(kSearchWaves * kBlock, 4) void c4_walk_kernel(Searc
 // each launch wait for the slowest game, here the waves only meet at the end of the run.
 // Step k's post-move position / move / result go to out_states[k*n + gl], out_moves[...],
 // out_results[...] (the inputs of zc_traj_record_async for step k, replayed in step order
-// after the launch); out_stats[gl] accumulates over the moves.
+// after the launch); out_stats[gl] accumulates over the moves.  With p.out_na (null: off) the
+// finished move's root visits per column go to out_na[(k*n + gl)*7 + col], the row of
+// zc_traj_policy_record_steps_async; a suspended move writes none.
 // Carried moves (zc_c4_selfplay_carry_async): a carry launch suspends each in-flight move at
 // its next flush boundary once the pooled budget is spent, saving {simulations done, tree
 // nodes, Philox tag} in a.carry[g] (the tree, the MT stream and the root stay in HBM).  EVERY
@@ -1414,6 +1416,7 @@ __global__ __launch_bounds__(kSearchWaves * kBlock, 4) void c4_selfplay_kernel(S
         turn ^= 1;
         const int r = won ? turn * 2 - 1 : ((s0 | s1) == kFull ? 0 : ZC_C4_ONGOING);
         const size_t o = (size_t)mv * p.n_games + gl;
+        if (p.out_na && lane < 7) p.out_na[o * 7 + lane] = na_col;  // zc_c4_selfplay_visits: the root's row
         if (lane == 0) {
             zc_c4_state post;
             post.stones[0] = s0;

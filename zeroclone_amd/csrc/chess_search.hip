@@ -761,7 +761,8 @@ __global__ __launch_bounds__(64) void chess_play_step_kernel(ChessPlayParams q, 
 // c4_search.hip's c4_selfplay_kernel): per move the whole search from the game's root, the
 // step above, the refill.  With q.ticket the games share q.budget moves (pooled); steps a
 // game did not reach are ZC_SLOT_SKIP / move 0xFFFF.  Outputs [moves][n]; q.stats[gl] sums
-// the moves' counters (reserved = games finished).
+// the moves' counters (reserved = games finished).  With q.out_step_na (null: off) every
+// move's root visit counts and root moves go to [moves][n][ZC_CHESS_MAX_MOVES] as well.
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void chess_selfplay_kernel(ChessParams p, ChessPlayParams q) {
     extern __shared__ uint16_t s_hist[];
     __shared__ CLds L;
@@ -805,6 +806,14 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void c
             break;
         }
         const uint32_t m = uni((uint32_t)t.mv[base + bi]);
+        if (q.out_step_na) {  // the row finish() gives a lockstep search, and the moves that name it
+            const int nm = uni((int)R->nmoves);
+            const size_t ro = ((size_t)mv * p.n_games + gl) * ZC_CHESS_MAX_MOVES;
+            for (int j = (int)lane; j < ZC_CHESS_MAX_MOVES; j += 64) {
+                q.out_step_na[ro + j] = j < nm ? t.na[base + j] : 0;
+                q.out_step_moves[ro + j] = j < nm ? t.mv[base + j] : (uint16_t)0;
+            }
+        }
         const int r = chess_play_judge(q, gl, L, s_hist, m, err);
         chess_play_commit(q, gl, L, (size_t)mv * p.n_games + gl, m, r);
         finished += r != ZC_C4_ONGOING;

@@ -220,6 +220,14 @@ int check_carry(const zc_engine *e, int32_t first, int32_t n) {
     return ZC_OK;
 }
 
+// A self-play launch with the visit-count staging registered (zc_*_selfplay_visits): its steps
+// must fit the staging.
+int check_visits_cap(const char *setter, const void *staging, int cap, int32_t moves) {
+    if (staging && moves > cap)
+        return fail(ZC_EINVAL, "%d steps exceed the %d steps of the visit-count staging (%s)", moves, cap, setter);
+    return ZC_OK;
+}
+
 void carry_covered(zc_engine *e, int32_t first, int32_t n) {  // a launch that leaves none carried
     if (first <= e->carry_lo && first + n >= e->carry_hi) e->carry_lo = e->carry_hi = 0;
 }
@@ -499,8 +507,9 @@ int zc_c4_selfplay_async(zc_engine *eng, int32_t first, int32_t n, zc_c4_state *
     if (moves < 1) return fail(ZC_EINVAL, "moves must be >= 1 (got %d)", moves);
     if (!n) return ZC_OK;
     std::lock_guard<std::mutex> lk(eng->mu);
+    if (int r = check_visits_cap("zc_c4_selfplay_visits", eng->c4_visits, eng->c4_visits_cap, moves)) return r;
     ZC_HIP(hipSetDevice(eng->cfg.device));
-    zc::SearchParams p = make_params(eng, first, n, d_roots, sims, c, bs, nullptr, nullptr, d_stats);
+    zc::SearchParams p = make_params(eng, first, n, d_roots, sims, c, bs, nullptr, eng->c4_visits, d_stats);
     p.moves = moves;
     p.io_roots = d_roots;
     p.out_states = d_out_states;
@@ -528,6 +537,7 @@ int c4_pooled(zc_engine *eng, int32_t first, int32_t n, zc_c4_state *d_roots, in
         return fail(ZC_EINVAL, "budget %lld outside [0, moves_cap x n_games] or >= 2^31", (long long)budget);
     if (!n) return ZC_OK;
     std::lock_guard<std::mutex> lk(eng->mu);
+    if (int r = check_visits_cap("zc_c4_selfplay_visits", eng->c4_visits, eng->c4_visits_cap, moves_cap)) return r;
     ZC_HIP(hipSetDevice(eng->cfg.device));
     // A wave takes its tickets only once resident: with more games than the chip holds at
     // once, the first waves could spend the whole budget and the rest never move.  Refused.
@@ -543,7 +553,7 @@ int c4_pooled(zc_engine *eng, int32_t first, int32_t n, zc_c4_state *d_roots, in
                     "the rest would never move; use zc_c4_selfplay_async or fewer games per launch", n, resident, bs);
     hipStream_t s = (hipStream_t)hip_stream;
     ZC_HIP(hipMemsetAsync(d_ticket, 0, 2 * sizeof(int32_t), s));
-    zc::SearchParams p = make_params(eng, first, n, d_roots, sims, c, bs, nullptr, nullptr, d_stats);
+    zc::SearchParams p = make_params(eng, first, n, d_roots, sims, c, bs, nullptr, eng->c4_visits, d_stats);
     p.moves = moves_cap;
     p.io_roots = d_roots;
     p.out_states = d_out_states;
@@ -581,6 +591,15 @@ int zc_c4_selfplay_carry_async(zc_engine *eng, int32_t first, int32_t n, zc_c4_s
                                zc_game_stats *d_stats, void *hip_stream) {
     return c4_pooled(eng, first, n, d_roots, sims, c, bs, moves_cap, budget, d_ticket, d_out_states, d_out_moves,
                      d_out_results, d_stats, hip_stream, 1);
+}
+
+int zc_c4_selfplay_visits(zc_engine *eng, int32_t *d_na, int32_t steps_cap) {
+    if (!eng) return fail(ZC_EINVAL, "null argument");
+    if (d_na && steps_cap < 1) return fail(ZC_EINVAL, "steps_cap must be >= 1 (got %d)", steps_cap);
+    std::lock_guard<std::mutex> lk(eng->mu);
+    eng->c4_visits = d_na;
+    eng->c4_visits_cap = d_na ? steps_cap : 0;
+    return ZC_OK;
 }
 
 int zc_c4_carry_discard(zc_engine *eng, int32_t first, int32_t n, void *hip_stream) {
@@ -981,6 +1000,33 @@ int zc_traj_policy_commit_async(int32_t n, const zc_traj_buffers *buf, const zc_
     return ZC_OK;
 }
 
+int zc_traj_policy_steps_scratch_bytes(int32_t n, int32_t steps, int64_t *bytes) {
+    if (n < 0 || steps < 0 || !bytes) return fail(ZC_EINVAL, "bad argument");
+    *bytes = (int64_t)zc::traj_policy_steps_scratch_bytes(n, steps);
+    return ZC_OK;
+}
+
+int zc_traj_policy_record_steps_async(int32_t n, const zc_traj_buffers *buf, const zc_traj_policy_buffers *pol,
+                                      const int32_t *d_results, const int32_t *d_na, const uint16_t *d_root_moves,
+                                      int32_t stride, int32_t steps, const int32_t *d_reached, void *d_scratch,
+                                      int64_t scratch_bytes, void *hip_stream) {
+    if (int r = check_traj(n, buf, nullptr)) return r;
+    if (int r = check_traj_policy(pol)) return r;
+    if (stride < 1 || stride > 65536) return fail(ZC_EINVAL, "stride must be in [1, 65536] (got %d)", stride);
+    if (steps < 0) return fail(ZC_EINVAL, "steps must be >= 0 (got %d)", steps);
+    if ((int64_t)n * steps >= ((int64_t)1 << 31)) return fail(ZC_EINVAL, "n x steps must be < 2^31");
+    if (n && steps && (!d_results || !d_na)) return fail(ZC_EINVAL, "bad argument");
+    if (!n || !steps) return ZC_OK;
+    const size_t need = zc::traj_policy_steps_scratch_bytes(n, steps);
+    if (!d_scratch || ((uintptr_t)d_scratch & 15) || scratch_bytes < (int64_t)need)
+        return fail(ZC_EINVAL, "scratch: %lld bytes at %p, need %zu bytes 16-byte aligned", (long long)scratch_bytes,
+                    d_scratch, need);
+    zc::launch_traj_policy_record_steps(n, steps, *buf, *pol, d_results, d_na, d_root_moves, stride, d_reached,
+                                        d_scratch, (hipStream_t)hip_stream);
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+
 int zc_traj_policy_dense_async(int32_t n_rows, const int64_t *d_first, const int32_t *d_count,
                                const uint32_t *d_entries, int32_t width, int32_t dtype, void *d_out,
                                void *hip_stream) {
@@ -1137,6 +1183,7 @@ int chess_selfplay_common(zc_engine *eng, int32_t first, int32_t n, const zc_che
         return fail(ZC_EINVAL, "budget %lld outside [0, moves_cap x n_games] or >= 2^31", (long long)budget);
     if (!n) return ZC_OK;
     std::lock_guard<std::mutex> lk(eng->mu);
+    if (int r = check_visits_cap("zc_chess_selfplay_visits", eng->chess_visits, eng->chess_visits_cap, moves)) return r;
     ZC_HIP(hipSetDevice(eng->cfg.device));
     if (int r = ensure_chess(eng)) return r;
     hipStream_t s = (hipStream_t)hip_stream;
@@ -1157,6 +1204,8 @@ int chess_selfplay_common(zc_engine *eng, int32_t first, int32_t n, const zc_che
     q.ticket = d_ticket;
     q.budget = (int32_t)budget;
     q.stats = d_stats;
+    q.out_step_na = eng->chess_visits;
+    q.out_step_moves = eng->chess_visit_moves;
     zc::launch_chess_selfplay(p, q, s);
     ZC_HIP(hipGetLastError());
     return ZC_OK;
@@ -1197,6 +1246,17 @@ int zc_chess_selfplay_pooled_async(zc_engine *eng, int32_t first, int32_t n, con
     if (n && !d_ticket) return fail(ZC_EINVAL, "null argument");
     return chess_selfplay_common(eng, first, n, b, sims, c, bs, policy, freedom, moves_cap, budget, d_ticket,
                                  d_out_states, d_out_moves, d_out_results, d_stats, hip_stream);
+}
+
+int zc_chess_selfplay_visits(zc_engine *eng, int32_t *d_na, uint16_t *d_root_moves, int32_t steps_cap) {
+    if (!eng) return fail(ZC_EINVAL, "null argument");
+    if (d_na && (!d_root_moves || steps_cap < 1))
+        return fail(ZC_EINVAL, "the staging needs d_root_moves and steps_cap >= 1 (got %d)", steps_cap);
+    std::lock_guard<std::mutex> lk(eng->mu);
+    eng->chess_visits = d_na;
+    eng->chess_visit_moves = d_na ? d_root_moves : nullptr;
+    eng->chess_visits_cap = d_na ? steps_cap : 0;
+    return ZC_OK;
 }
 
 int zc_chess_pooled_max_games(int32_t hist_cap, int32_t *out) {

@@ -230,13 +230,10 @@ constexpr int kSlotWaves = 4;
 
 // (A) lane = step.  A slot's moves are the steps before its first ZC_SLOT_SKIP; a game that
 // ends at step k has the positions since the previous finish (opening included) or, for the
-// slot's game in progress at the launch's start, its history plus steps 0..k.
-__global__ __launch_bounds__(kSlotWaves * 64) void traj_steps_lens_kernel(int n, int K, const int32_t *reached,
-                                                                          const int32_t *slot,
-                                                                          const int32_t *results, StepScratch sc) {
-    const int lane = (int)(threadIdx.x & 63);
-    const int g = (int)(blockIdx.x * kSlotWaves + (threadIdx.x >> 6));
-    if (g >= n) return;
+// slot's game in progress at the launch's start, its history plus steps 0..k.  Returns the
+// slot's moves played (also left in sc.played[g]).
+__device__ __forceinline__ int steps_lens(int n, int K, const int32_t *reached, const int32_t *slot,
+                                          const int32_t *results, const StepScratch &sc, int g, int lane) {
     const int Kr = steps_reached(K, reached);
     int lenc = slot[4 * (size_t)g];
     bool stopped = slot[4 * (size_t)g + 1] < 0;  // idle slot: nothing recorded
@@ -259,6 +256,16 @@ __global__ __launch_bounds__(kSlotWaves * 64) void traj_steps_lens_kernel(int n,
         stopped = stopped || first_skip < 64;
     }
     if (lane == 0) sc.played[g] = m;
+    return m;
+}
+
+__global__ __launch_bounds__(kSlotWaves * 64) void traj_steps_lens_kernel(int n, int K, const int32_t *reached,
+                                                                          const int32_t *slot,
+                                                                          const int32_t *results, StepScratch sc) {
+    const int lane = (int)(threadIdx.x & 63);
+    const int g = (int)(blockIdx.x * kSlotWaves + (threadIdx.x >> 6));
+    if (g >= n) return;
+    steps_lens(n, K, reached, slot, results, sc, g, lane);
 }
 
 // (B) one workgroup per step: exclusive prefixes of (finished, length) along the row.
@@ -520,6 +527,264 @@ __global__ __launch_bounds__(kSlotWaves * 64) void traj_policy_copy_kernel(int n
     for (int e = lane; e < total; e += 64) q.d_pool_pi[at + e] = src[e];
 }
 
+// ---------------------------------------------------------------- multi-step policy record
+// The visit counts of the K steps of one self-play launch recorded at once: what K rounds of
+// (append, record, commit) leave, from the launch's staged rows na[k][g][stride] (and the root
+// moves mv[k][g][stride] that name them; null: id = index).  Runs BEFORE the multi-step record of
+// the same launch — it reads the slot table and the counters as the launch found them and
+// changes neither.  A single commit reserves the entries of the games finished in its step in
+// slot order, so a game's place in the entry pool is a third exclusive prefix sum over the
+// [K][n] grid in step-major order, of the entries of each finished game the pool took.
+// Kernels: (A) as above, one wave per slot, which here also counts every step's entries nnz[k][g]
+// and their running sum cum[k][g] over the slot's game (from the history's fill for the game in
+// progress, from 0 after a finish); (B) as above; (E) one workgroup per step: the prefix of
+// the row totals before its step (no kernel C: the counters are only read), which of its
+// finished games the pool drops, the scan of the others' entries along the row; (F) one wave per
+// slot: each finished game's first / count per pooled position and its entries — the history's,
+// then the staged rows' — to their pool place, then the unfinished game's rows appended to the
+// slot's CSR.
+struct PolicyStepScratch {
+    StepScratch s;
+    int32_t *nnz, *cum;          // [K][n]
+    int64_t *exe, *rowtot_e;     // [K][n], [K]
+    int64_t *ebase;              // [1] ZC_TRAJ_PI_ENTRIES before the call
+};
+
+__host__ __device__ inline size_t policy_steps_scratch_layout(int n, int K, uint8_t *p, PolicyStepScratch *sc) {
+    size_t o = align16(steps_scratch_layout(n, K, p, sc ? &sc->s : nullptr));
+    const size_t kn = (size_t)K * n;
+    if (sc) sc->nnz = (int32_t *)(p + o);
+    o = align16(o + kn * sizeof(int32_t));
+    if (sc) sc->cum = (int32_t *)(p + o);
+    o = align16(o + kn * sizeof(int32_t));
+    if (sc) sc->exe = (int64_t *)(p + o);
+    o = align16(o + kn * sizeof(int64_t));
+    if (sc) sc->rowtot_e = (int64_t *)(p + o);
+    o = align16(o + (size_t)K * sizeof(int64_t));
+    if (sc) sc->ebase = (int64_t *)(p + o);
+    return o + 2 * sizeof(int64_t);
+}
+
+// The non-zero counts of one staged row: their number (the whole wave gets it).
+__device__ __forceinline__ int policy_row_nnz(const int32_t *row, int stride, int lane) {
+    int run = 0;
+    for (int c0 = 0; c0 < stride; c0 += 64) {
+        const int j = c0 + lane;
+        run += __popcll(__ballot(j < stride && row[j] > 0));
+    }
+    return run;
+}
+
+// One staged row compacted (as traj_policy_append_kernel compacts it) to dst[at0 ..), written
+// below `cap` only; returns kPiSlotFull / kPiSaturated bits (per lane).
+__device__ __forceinline__ int policy_row_emit(const int32_t *row, const uint16_t *mv, int stride, int lane,
+                                               uint32_t *dst, long long at0, long long cap) {
+    int run = 0, ov = 0;
+    for (int c0 = 0; c0 < stride; c0 += 64) {
+        const int j = c0 + lane;
+        const int cnt = j < stride ? row[j] : 0;
+        const unsigned long long have = __ballot(cnt > 0);
+        if (cnt > 0) {
+            const long long at = at0 + run + __popcll(have & ((1ull << lane) - 1));
+            if (cnt > 65535) ov |= kPiSaturated;
+            const uint32_t id = mv ? (uint32_t)mv[j] : (uint32_t)j;
+            if (at < cap) dst[at] = id | ((uint32_t)min(cnt, 65535) << 16);
+            else ov |= kPiSlotFull;
+        }
+        run += __popcll(have);
+    }
+    return ov;
+}
+
+// (A) with the entry counts: the lengths as traj_steps_lens_kernel, then step by step the rows'
+// non-zero counts and their running sum over the slot's game.
+__global__ __launch_bounds__(kSlotWaves * 64) void traj_policy_steps_lens_kernel(int n, int K, const int32_t *reached,
+                                                                                 zc_traj_buffers b,
+                                                                                 zc_traj_policy_buffers q,
+                                                                                 const int32_t *results,
+                                                                                 const int32_t *na, int stride,
+                                                                                 PolicyStepScratch sc) {
+    const int lane = (int)(threadIdx.x & 63);
+    const int g = (int)(blockIdx.x * kSlotWaves + (threadIdx.x >> 6));
+    if (g >= n) return;
+    const int32_t *slot = b.d_slot + 4 * (size_t)g;
+    const int m = steps_lens(n, K, reached, b.d_slot, results, sc.s, g, lane);
+    if (g == 0 && lane == 0) sc.ebase[0] = q.d_pctl[ZC_TRAJ_PI_ENTRIES];  // (F) updates the counter
+    if (slot[1] < 0) return;  // idle: m = 0
+    const int h = min(max(slot[0], 1), b.max_len);
+    int run = q.d_slot_off[(size_t)g * (b.max_len + 1) + h - 1];  // the entries of positions 0 .. h-2
+    for (int k = 0; k < m; ++k) {
+        const size_t e = (size_t)k * n + g;
+        const int c = policy_row_nnz(na + e * stride, stride, lane);
+        run += c;
+        const int r = results[e];
+        if (lane == 0) {
+            sc.nnz[e] = c;
+            sc.cum[e] = run;
+        }
+        if (r != ZC_C4_ONGOING) run = 0;  // finished: the next game starts empty
+    }
+}
+
+// (E) one workgroup per step.  Threads first sum the (games, positions) totals of the rows
+// before this one; then along the row each finished game the trajectory pool takes (the test of
+// traj_steps_copy_kernel) contributes its entries, clamped as a slot's history clamps them.
+__global__ __launch_bounds__(kRecThreads) void traj_policy_steps_rows_kernel(int n, int K, const int32_t *reached,
+                                                                             zc_traj_buffers b,
+                                                                             zc_traj_policy_buffers q,
+                                                                             PolicyStepScratch sc) {
+    const int k = (int)blockIdx.x;
+    if (k >= steps_reached(K, reached)) return;
+    long long gpre = 0, ppre = 0;
+    for (int c0 = 0; c0 < k; c0 += kRecThreads) {
+        const int kk = c0 + (int)threadIdx.x;
+        int x = kk < k ? (int)sc.s.rowtot[2 * kk] : 0;
+        long long y = kk < k ? sc.s.rowtot[2 * kk + 1] : 0;
+        int tx;
+        long long ty;
+        block_scan2(x, y, tx, ty);
+        gpre += tx;
+        ppre += ty;
+    }
+    const long long pos0 = b.d_ctl[kTrajPositions] + ppre, games0 = b.d_ctl[kTrajGames] + gpre;
+    const size_t row = (size_t)k * n;
+    long long ebase = 0;
+    for (int c0 = 0; c0 < n; c0 += kRecThreads) {
+        const int g = c0 + (int)threadIdx.x;
+        long long E = 0;
+        if (g < n) {
+            const int L = sc.s.fl[row + g];
+            if (L > 0) {
+                const long long G = games0 + sc.s.exg[row + g], P = pos0 + sc.s.exp[row + g];
+                if (!(P + L > b.pool_cap || G >= b.games_cap)) E = min(sc.cum[row + g], q.slot_cap);
+            }
+        }
+        int x = 0, tx;
+        long long y = E, ty;
+        block_scan2(x, y, tx, ty);
+        if (g < n) sc.exe[row + g] = ebase + y;
+        ebase += ty;
+    }
+    if (threadIdx.x == 0) {
+        sc.rowtot_e[k] = ebase;
+        sc.s.rowpre[2 * k] = gpre;
+        sc.s.rowpre[2 * k + 1] = ppre;
+    }
+}
+
+// (F) one wave per slot, walking its games as traj_steps_copy_kernel does.  Position i of a
+// game whose first step is bs, with hh = h - 1 of its positions searched before the launch, was
+// searched at step bs + i - hh (i >= hh); its entries start at cum - nnz of that step.
+__global__ __launch_bounds__(kSlotWaves * 64) void traj_policy_steps_copy_kernel(int n, int K, const int32_t *reached,
+                                                                                 zc_traj_buffers b,
+                                                                                 zc_traj_policy_buffers q,
+                                                                                 const int32_t *na, const uint16_t *mv,
+                                                                                 int stride, PolicyStepScratch sc) {
+    const int lane = (int)(threadIdx.x & 63);
+    const int g = (int)(blockIdx.x * kSlotWaves + (threadIdx.x >> 6));
+    if (g >= n) return;
+    const int Kr = steps_reached(K, reached);
+    const long long ebase = sc.ebase[0];
+    if (g == 0 && lane == 0) {  // the counter's update: every wave read its old value from the scratch
+        long long tot = 0;
+        for (int k = 0; k < Kr; ++k) tot += sc.rowtot_e[k];
+        q.d_pctl[ZC_TRAJ_PI_ENTRIES] = ebase + tot;
+    }
+    const int32_t *slot = b.d_slot + 4 * (size_t)g;
+    int game = slot[1];
+    if (game < 0) return;
+    const long long pos0 = b.d_ctl[kTrajPositions], games0 = b.d_ctl[kTrajGames], next0 = b.d_ctl[kTrajNext],
+                    quota = b.d_ctl[kTrajQuota];
+    int32_t *off = q.d_slot_off + (size_t)g * (b.max_len + 1);
+    uint32_t *spi = q.d_slot_pi + (size_t)g * q.slot_cap;
+    const long long cap = q.slot_cap;
+    const int m = sc.s.played[g];
+    int hh = min(max(slot[0], 1), b.max_len) - 1, bs = 0, ov = 0;
+    bool first = true;
+    long long epre = 0;  // the entries of the rows before step kdone
+    int kdone = 0;
+    for (int c0 = 0; c0 < m && game >= 0; c0 += 64) {
+        const int k = c0 + lane;
+        const int Lv = k < m ? sc.s.fl[(size_t)k * n + g] : 0;
+        unsigned long long fin = __ballot(Lv > 0);
+        while (fin && game >= 0) {
+            const int j = __ffsll((long long)fin) - 1;
+            fin &= fin - 1;
+            const int kk = c0 + j;
+            const size_t e = (size_t)kk * n + g;
+            const int L = __shfl(Lv, j);
+            for (; kdone < kk; kdone += 64) {
+                long long v = (kdone + lane < kk) ? sc.rowtot_e[kdone + lane] : 0;
+                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+                epre += v;
+            }
+            kdone = kk;
+            const long long gi = sc.s.rowpre[2 * kk] + sc.s.exg[e];
+            const long long G = games0 + gi, P = pos0 + sc.s.rowpre[2 * kk + 1] + sc.s.exp[e];
+            const long long total = sc.cum[e];
+            const long long E = min(total, cap);
+            if (total > cap) ov |= kPiSlotFull;
+            if (!(P + L > b.pool_cap || G >= b.games_cap)) {
+                long long at = ebase + epre + sc.exe[e];
+                if (at + E > q.pi_pool_cap) {  // dropped: first = count = 0
+                    ov |= kPiPoolFull;
+                    at = -1;
+                }
+                for (int i = lane; i < L; i += 64) {
+                    long long o0, o1;
+                    if (i < hh) {
+                        o0 = i ? off[i] : 0;
+                        o1 = off[i + 1];
+                    } else if (i + 1 < L) {
+                        const size_t es = (size_t)(bs + i - hh) * n + g;
+                        o1 = min((long long)sc.cum[es], cap);
+                        o0 = min((long long)sc.cum[es] - sc.nnz[es], cap);
+                    } else {
+                        o0 = o1 = E;
+                    }
+                    q.d_pool_first[P + i] = at < 0 ? 0 : at + o0;
+                    q.d_pool_count[P + i] = at < 0 ? 0 : (int32_t)(o1 - o0);
+                }
+                if (at >= 0) {
+                    const long long held = hh > 0 ? min((long long)off[hh], cap) : 0;
+                    for (long long x = lane; x < held; x += 64) q.d_pool_pi[at + x] = spi[x];
+                    for (int s = bs; s <= kk; ++s) {
+                        const size_t es = (size_t)s * n + g;
+                        ov |= policy_row_emit(na + es * stride, mv ? mv + es * stride : nullptr, stride, lane,
+                                              q.d_pool_pi + at, (long long)sc.cum[es] - sc.nnz[es], cap) & kPiSaturated;
+                    }
+                }
+            }
+            // the offsets the single appends of this game left in the slot (a later game of the
+            // slot overwrites them as far as it gets)
+            for (int s = bs + lane; s <= kk; s += 64) {
+                const int pos = hh + (s - bs);
+                if (pos < b.max_len) off[pos + 1] = (int32_t)min((long long)sc.cum[(size_t)s * n + g], cap);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            const long long nx = next0 + gi;
+            game = nx < quota ? (int)nx : -1;
+            first = false;
+            hh = 0;
+            bs = kk + 1;
+        }
+    }
+    // the game in progress: its rows since bs appended to the slot's CSR
+    if (!first && lane == 0) off[0] = 0;
+    const int cnt = game >= 0 ? m - bs : 0;
+    for (int t = 0; t < cnt; ++t) {
+        const int pos = hh + t;
+        if (pos >= b.max_len) break;  // never: the record flags a game longer than max_len
+        const size_t es = (size_t)(bs + t) * n + g;
+        const long long c1 = sc.cum[es];
+        ov |= policy_row_emit(na + es * stride, mv ? mv + es * stride : nullptr, stride, lane, spi, c1 - sc.nnz[es], cap);
+        if (lane == 0) off[pos + 1] = (int32_t)min(c1, cap);
+    }
+    ov = (__ballot(ov & kPiSlotFull) ? kPiSlotFull : 0) | (__ballot(ov & kPiPoolFull) ? kPiPoolFull : 0) |
+         (__ballot(ov & kPiSaturated) ? kPiSaturated : 0);
+    if (lane == 0 && ov) atomicOr((unsigned long long *)(q.d_pctl + ZC_TRAJ_PI_OVERFLOW), (unsigned long long)ov);
+}
+
 // Dense targets, width 7 — one wave per row, lane = column: count / sum of the row's entries.
 template <typename T>
 __global__ __launch_bounds__(256) void traj_policy_dense7_kernel(int n_rows, const int64_t *first,
@@ -614,6 +879,20 @@ void launch_traj_record_steps(int n, int K, const zc_traj_buffers &b, const void
     hipLaunchKernelGGL(traj_steps_totals_kernel, dim3(1), dim3(kRecThreads), 0, s, K, reached, b, sc);
     hipLaunchKernelGGL(traj_steps_copy_kernel, slots, wb, 0, s, n, K, reached, b, (const uint8_t *)states, moves,
                        results, sc);
+}
+
+size_t traj_policy_steps_scratch_bytes(int n, int K) { return policy_steps_scratch_layout(n, K, nullptr, nullptr); }
+
+void launch_traj_policy_record_steps(int n, int K, const zc_traj_buffers &b, const zc_traj_policy_buffers &q,
+                                     const int32_t *results, const int32_t *na, const uint16_t *mv, int stride,
+                                     const int32_t *reached, void *scratch, hipStream_t s) {
+    PolicyStepScratch sc;
+    policy_steps_scratch_layout(n, K, (uint8_t *)scratch, &sc);
+    const dim3 slots((unsigned)((n + kSlotWaves - 1) / kSlotWaves)), wb(kSlotWaves * 64);
+    hipLaunchKernelGGL(traj_policy_steps_lens_kernel, slots, wb, 0, s, n, K, reached, b, q, results, na, stride, sc);
+    hipLaunchKernelGGL(traj_steps_rows_kernel, dim3((unsigned)K), dim3(kRecThreads), 0, s, n, K, reached, sc.s);
+    hipLaunchKernelGGL(traj_policy_steps_rows_kernel, dim3((unsigned)K), dim3(kRecThreads), 0, s, n, K, reached, b, q, sc);
+    hipLaunchKernelGGL(traj_policy_steps_copy_kernel, slots, wb, 0, s, n, K, reached, b, q, na, mv, stride, sc);
 }
 
 void launch_traj_record(int n, const zc_traj_buffers &b, void *states, const int16_t *moves, int32_t *results,

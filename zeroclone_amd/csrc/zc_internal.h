@@ -106,6 +106,7 @@ struct SearchParams {
     int philox;            // rollouts: 0 = the game's MT19937 stream (exact), 1 = Philox mode
     uint64_t philox_seed;  // Philox key of the Philox rollout mode
     // self-play run (c4_selfplay_kernel): moves per game, per-step outputs [moves][n_games]
+    // (out_na there: the optional [moves][n_games][7] visit counts of zc_c4_selfplay_visits)
     int moves;
     zc_c4_state *io_roots;  // = roots, written after every move
     zc_c4_state *out_states;
@@ -354,6 +355,11 @@ struct ChessPlayParams {
     int32_t *ticket;              // pooled: moves drawn while ticket[0] < budget; ticket[1] = most moves
     int32_t budget;
     zc_game_stats *stats;         // self-play launch: per-game sums
+    // self-play launch, optional (zc_chess_selfplay_visits; null: off): every finished move's
+    // root visit counts and packed root moves [moves][n][ZC_CHESS_MAX_MOVES], in the root's
+    // move-list order (zeros past the root's moves)
+    int32_t *out_step_na;
+    uint16_t *out_step_moves;
 };
 void launch_chess_play_step(const ChessPlayParams &q, int n, hipStream_t s);
 void launch_chess_selfplay(const ChessParams &p, const ChessPlayParams &q, hipStream_t s);
@@ -424,6 +430,10 @@ void launch_traj_record_steps(int n, int K, const zc_traj_buffers &b, const void
 void launch_traj_policy_append(int n, const zc_traj_buffers &b, const zc_traj_policy_buffers &q, const int32_t *na,
                                const uint16_t *mv, int stride, hipStream_t s);
 void launch_traj_policy_commit(int n, const zc_traj_buffers &b, const zc_traj_policy_buffers &q, hipStream_t s);
+size_t traj_policy_steps_scratch_bytes(int n, int K);
+void launch_traj_policy_record_steps(int n, int K, const zc_traj_buffers &b, const zc_traj_policy_buffers &q,
+                                     const int32_t *results, const int32_t *na, const uint16_t *mv, int stride,
+                                     const int32_t *reached, void *scratch, hipStream_t s);
 void launch_traj_policy_dense(int n_rows, const int64_t *first, const int32_t *count, const uint32_t *ent, int width,
                               bool half, void *out, hipStream_t s);
 void launch_uct_debug(int n, const double *logn, const int32_t *na, const double *q, double c, double *out,
@@ -448,6 +458,11 @@ struct zc_engine {
     int64_t bytes = 0;
     int stamp = 0;
     uint64_t *tstamps = nullptr;  // zc_debug_c4_launch_stamps: device buffer, 4 words per game
+    // zc_c4_selfplay_visits / zc_chess_selfplay_visits: the self-play launches' per-step visit-count
+    // staging (null: off) and the steps it holds
+    int32_t *c4_visits = nullptr, *chess_visits = nullptr;
+    uint16_t *chess_visit_moves = nullptr;
+    int c4_visits_cap = 0, chess_visits_cap = 0;
     int rollout_mode = 0;        // ZC_ROLLOUT_EXACT / ZC_ROLLOUT_PHILOX
     uint64_t rollout_seed = 0;
     int carry_lo = 0, carry_hi = 0;  // games that may hold a carried self-play move (engine.hip check_carry)

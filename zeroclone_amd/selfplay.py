@@ -116,7 +116,7 @@ class Trajectories:
 
     `policy_width` (7: Connect4, 4096: chess) also records every search's root visit counts,
     sparse (zc_traj_policy_*): `record_policy()` after the search, the commit inside
-    `record()`.  `pi_slot_cap` entries per slot's game (default: every move of every position
+    `record()`; the fused launches' staged counts go through `record_steps(na=...)`.  `pi_slot_cap` entries per slot's game (default: every move of every position
     visited) and `pi_pool_cap` pooled entries until the next `take()`."""
 
     PI_STRIDE = {7: 7, 4096: _native.CHESS_MAX_MOVES}   # policy_width -> moves per root (d_out_root_na's row)
@@ -274,14 +274,21 @@ class Trajectories:
             ctypes.c_void_p(stream or None)))
 
     def record_steps(self, d_states: int, moves: torch.Tensor, results: torch.Tensor, steps: int,
-                     reached: torch.Tensor | None = None, stream: int = 0):
+                     reached: torch.Tensor | None = None, stream: int = 0, na: torch.Tensor | None = None,
+                     root_moves: torch.Tensor | None = None):
         """record() for `steps` consecutive [steps][n] self-play outputs in one call
         (zc_traj_record_steps_async: four launches whatever `steps` is); only the steps
-        k < *reached are read.  Needs the unlimited quota."""
+        k < *reached are read.  Needs the unlimited quota.
+        A pool recording the policy needs the launch's staged visit counts na [steps, n, stride]
+        int32 (zc_c4_selfplay_visits / zc_chess_selfplay_visits; chess also the staged root moves
+        of the same shape, 16-bit): zc_traj_policy_record_steps_async records them first, from
+        the slot table the position record then updates."""
         if self.quota != _UNLIMITED:
             raise ValueError("multi-step recording needs the unlimited quota (start(None))")
-        if self.policy_width is not None:
+        if self.policy_width is not None and na is None:
             raise ValueError("the multi-step launches export no per-move visit counts: record the policy with step()")
+        if na is not None:
+            self._record_policy_steps(results, int(steps), reached, stream, na, root_moves)
         need = ctypes.c_int64(0)
         _native.check(_native.lib().zc_traj_steps_scratch_bytes(self.n, int(steps), ctypes.byref(need)))
         if getattr(self, "_scratch", None) is None or self._scratch.numel() < need.value:
@@ -291,6 +298,26 @@ class Trajectories:
             ctypes.c_void_p(results.data_ptr()), int(steps),
             ctypes.c_void_p(reached.data_ptr() if reached is not None else None),
             ctypes.c_void_p(self._scratch.data_ptr()), self._scratch.numel(), ctypes.c_void_p(stream or None)))
+
+    def _record_policy_steps(self, results: torch.Tensor, steps: int, reached: torch.Tensor | None, stream: int,
+                             na: torch.Tensor, root_moves: torch.Tensor | None):
+        if self.policy_width is None:
+            raise ValueError("this pool records no visit counts (policy_width=None)")
+        if (na.dim() != 3 or na.shape[0] < steps or tuple(na.shape[1:]) != (self.n, self.pi_stride)
+                or na.dtype != torch.int32 or not na.is_contiguous()):
+            raise ValueError(f"na must be a contiguous int32 [>= {steps}, {self.n}, {self.pi_stride}] tensor")
+        if root_moves is not None and (tuple(root_moves.shape) != tuple(na.shape) or root_moves.element_size() != 2
+                                       or not root_moves.is_contiguous()):
+            raise ValueError("root_moves must be a contiguous 16-bit tensor of na's shape")
+        need = ctypes.c_int64(0)
+        _native.check(_native.lib().zc_traj_policy_steps_scratch_bytes(self.n, steps, ctypes.byref(need)))
+        if getattr(self, "_pscratch", None) is None or self._pscratch.numel() < need.value:
+            self._pscratch = torch.empty(max(need.value, 16), dtype=torch.uint8, device=self.dev)
+        _native.check(_native.lib().zc_traj_policy_record_steps_async(
+            self.n, ctypes.byref(self._buf), ctypes.byref(self._pol), ctypes.c_void_p(results.data_ptr()),
+            ctypes.c_void_p(na.data_ptr()), ctypes.c_void_p(root_moves.data_ptr() if root_moves is not None else None),
+            self.pi_stride, steps, ctypes.c_void_p(reached.data_ptr() if reached is not None else None),
+            ctypes.c_void_p(self._pscratch.data_ptr()), self._pscratch.numel(), ctypes.c_void_p(stream or None)))
 
     def finished(self) -> int:
         """Games finished since start() (one device read); raises at once if the pool has
@@ -383,7 +410,8 @@ class _SelfPlayPool:
     A game supplies the attributes below, its state (`roots`, `moves`, ... and `start()`) and
     four launches: `_search` (its own search kernel into moves / na / stats), `_root_moves`
     (the move list that names a root's visit counts), `_play` (play the searched moves; returns
-    what `Trajectories.record` is to be given) and `_launch` (a fused multi-move launch);
+    what `Trajectories.record` is to be given), `_launch` (a fused multi-move launch) and
+    `_visits` (register the fused launches' visit-count staging with the engine);
     `_adopt_state` is its share of `adopt()`."""
 
     MOVE_DTYPE: torch.dtype   # of `moves`, as the game's kernels write them
@@ -396,14 +424,16 @@ class _SelfPlayPool:
     def __init__(self, games: int, sims: int, c: float, batch_size: int, seed: int, rank: int, device,
                  temperature: float, record_policy: bool, init_row: torch.Tensor, max_len: int,
                  games_cap: int | None, pi_slot_cap: int | None, pi_pool_cap: int | None,
-                 record: bool = True, max_sims: int | None = None):
+                 record: bool = True, max_sims: int | None = None, fused_policy: bool = False):
         """The refusals come before the engine: they need no GPU."""
         if record_policy and sims > _native.ZC_TRAJ_PI_MAX_COUNT:   # an entry's count field is 16 bits
             raise ValueError(f"record_policy stores visit counts in 16 bits: sims {sims} > "
                              f"{_native.ZC_TRAJ_PI_MAX_COUNT}")
         if record_policy and not record:   # the entries ride on the trajectories
             raise ValueError("record_policy needs the trajectory recorder (record=True)")
-        self.record_policy = bool(record_policy)
+        if fused_policy and not record_policy:   # the switch only lifts the fused launches' refusal
+            raise ValueError("fused_policy records the fused launches' visit counts: it needs record_policy=True")
+        self.record_policy, self.fused_policy = bool(record_policy), bool(fused_policy)
         self.G, self.sims, self.c, self.bs = games, sims, c, batch_size
         self.dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.eng = _native.NativeEngine(max_games=games, max_sims=max_sims or sims, max_batch=batch_size,
@@ -522,9 +552,11 @@ class _SelfPlayPool:
         then the recording of every step, in step order.  Needs the unlimited quota
         (start(None)): with a quota the refill depends on other slots' finishes, which step()
         decides once per step.  `kernel_done`: an event recorded after the launch, before the
-        recording."""
+        recording.  With fused_policy the [moves][G][NA_WIDTH] visit-count staging is allocated
+        with the outputs and registered with the engine (`_visits`) before the launch, and the
+        recording takes it along."""
         name = "run" if budget is None else "run_pooled"
-        if self.record_policy:
+        if self.record_policy and not self.fused_policy:
             raise ValueError(_NO_FUSED_POLICY)
         if self.traj is not None and self.traj.quota != _UNLIMITED:
             raise ValueError(f"{name}() plays without a game quota; use step() under simulate_games' quota")
@@ -535,15 +567,21 @@ class _SelfPlayPool:
             self._run_states = torch.zeros((moves,) + self.roots.shape, dtype=self.roots.dtype, device=self.dev)
             self._run_moves = torch.zeros((moves, self.G), dtype=torch.int16, device=self.dev)
             self._run_results = torch.zeros((moves, self.G), dtype=torch.int32, device=self.dev)
+            self._run_na = self._run_root_moves = None
+            if self.fused_policy:
+                self._run_na = torch.zeros((moves, self.G, self.NA_WIDTH), dtype=torch.int32, device=self.dev)
             self._run_k = moves
         if budget is not None and self._ticket is None:
             self._ticket = torch.zeros(2, dtype=torch.int32, device=self.dev)   # counter, most moves played
+        if self.fused_policy:
+            self._visits(moves)
         self._launch(moves, budget, carry, s)
         if kernel_done is not None:
             kernel_done.record()
         if self.record:
             self.traj.record_steps(self._run_states.data_ptr(), self._run_moves, self._run_results, moves,
-                                   reached=self._ticket[1:] if budget is not None else None, stream=s)
+                                   reached=self._ticket[1:] if budget is not None else None, stream=s,
+                                   na=self._run_na, root_moves=self._run_root_moves)
         return self._run_results
 
     def check(self):
@@ -579,9 +617,14 @@ class C4SelfPlay(_SelfPlayPool):
                  rank: int = 0, device: int = 0, record: bool = True, games_cap: int | None = None,
                  net=None, puct_net=None, temperature: float = 1.0, puct_seed: int = 1, streams: int = 1,
                  record_policy: bool = False, pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
-                 reuse_tree: bool = False, tree_nodes: int | None = None):
+                 reuse_tree: bool = False, tree_nodes: int | None = None, fused_policy: bool = False):
         """record_policy: every step()'s root visit counts go with the positions into the
         trajectories (TrajBatch.pi / policy_targets(7)), in every search mode.
+        fused_policy (needs record_policy): run(), run_pooled() (carry=True too) and drain()
+        record them as well — the launch stages every finished move's counts
+        (zc_c4_selfplay_visits, [moves][games][7] int32) and zc_traj_policy_record_steps_async
+        pools them: the same TrajBatch.pi as the same moves played with step().  Off by default:
+        without it the fused launches of a record_policy pool keep refusing.
         reuse_tree (PUCT mode): each search keeps the subtree of the move just played
         (C4PuctSearch(reuse=True)) and adds sims - 1 visits to it; a tree holds up to
         `tree_nodes` nodes (default min(2 * sims, 65534)), and a search whose kept nodes leave
@@ -596,7 +639,8 @@ class C4SelfPlay(_SelfPlayPool):
         super().__init__(games, sims, c, batch_size, seed, rank, device, temperature, record_policy,
                          torch.zeros(24, dtype=torch.uint8), self.MAX_LEN, games_cap, pi_slot_cap, pi_pool_cap,
                          record=record,
-                         max_sims=(tree_nodes or min(2 * sims, 65534)) if reuse_tree else None)
+                         max_sims=(tree_nodes or min(2 * sims, 65534)) if reuse_tree else None,
+                         fused_policy=fused_policy)
         self.reuse_tree = bool(reuse_tree)
         self.record = record
         self.roots = torch.zeros((games, 3), dtype=torch.int64, device=self.dev)
@@ -662,6 +706,9 @@ class C4SelfPlay(_SelfPlayPool):
         if self.reuse_tree:
             self.ps.forget()
 
+    def _visits(self, moves: int):
+        self.eng.c4_selfplay_visits(self._run_na.data_ptr(), moves)
+
     def _launch(self, moves: int, budget: int | None, carry: bool, s: int):
         """zc_c4_selfplay_async / zc_c4_selfplay_pooled_async (carry: zc_c4_selfplay_carry_async);
         either resumes carried moves first."""
@@ -678,7 +725,8 @@ class C4SelfPlay(_SelfPlayPool):
         """`moves` moves for every game in ONE launch (zc_c4_selfplay_async: each game at its
         own pace, finished games refilled from the opening in the kernel), then the
         trajectory recording of every step, in step order — the same games, pool and labels
-        as `moves` calls of step().  Needs the unlimited quota (start(None)).
+        as `moves` calls of step() (with fused_policy their root visit counts too; a
+        record_policy pool without it refuses).  Needs the unlimited quota (start(None)).
         Returns the per-step results [moves, G]; self.stats sums the moves' counters."""
         self.results.copy_(self._fused(moves, None, stream, kernel_done)[-1])
         return self._run_results
@@ -695,6 +743,8 @@ class C4SelfPlay(_SelfPlayPool):
         carry=True (zc_c4_selfplay_carry_async): once the budget is spent the in-flight moves
         stop at their next flush and carry over — the next run()/run_pooled() resumes them
         first; drain() finishes them; step() and the lockstep searches refuse until then.
+        With fused_policy every finished move's visit counts are recorded with its position,
+        a carried move's by the launch that finishes it.
         Returns the per-step results [moves_cap, G]; self.stats sums the launch's counters."""
         return self._fused(moves_cap, budget, stream, kernel_done, carry)
 
@@ -756,9 +806,15 @@ class ChessSelfPlay(_SelfPlayPool):
                  hist_cap: int = 1024, puct_net=None, temperature: float = 1.0, puct_seed: int = 1,
                  puct_streams: int = 1, streams: int = 1, record_policy: bool = False,
                  pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
-                 reuse_tree: bool = False, tree_nodes: int | None = None):
+                 reuse_tree: bool = False, tree_nodes: int | None = None, fused_policy: bool = False):
         """record_policy: every step()'s root visit counts go with the positions into the
         trajectories (TrajBatch.pi / policy_targets(4096)), in every search mode.
+        fused_policy (needs record_policy): run() and run_pooled() record them as well — the
+        launch stages every move's counts and root moves (zc_chess_selfplay_visits,
+        [moves][games][256] int32 + int16: about 63 MB at 60 steps x 1024 games) and
+        zc_traj_policy_record_steps_async pools them: the same TrajBatch.pi as the same moves
+        played with step().  Off by default: without it the fused launches of a record_policy
+        pool keep refusing.
         reuse_tree (PUCT mode): each search keeps the subtree of the move just played
         (ChessPuctSearch(reuse=True)) and adds sims - 1 visits to it; a tree holds up to
         `tree_nodes` nodes (default min(2 * sims, 65534)) and 64 child slots per node, and a
@@ -776,7 +832,8 @@ class ChessSelfPlay(_SelfPlayPool):
             pi_slot_cap = (max_len - 1) * (_native.CHESS_MAX_MOVES if reuse_tree else min(sims, _native.CHESS_MAX_MOVES))
         super().__init__(games, sims, c, batch_size, seed, rank, device, temperature, record_policy,
                          init, max_len, games_cap, pi_slot_cap, pi_pool_cap,
-                         max_sims=(tree_nodes or min(2 * sims, 65534)) if reuse_tree else None)
+                         max_sims=(tree_nodes or min(2 * sims, 65534)) if reuse_tree else None,
+                         fused_policy=fused_policy)
         self.reuse_tree = bool(reuse_tree)
         self.eng.chess_reserve()
         self.policy, self.freedom = int(policy), float(freedom)
@@ -836,6 +893,12 @@ class ChessSelfPlay(_SelfPlayPool):
         if self.reuse_tree:
             self.ps.forget()
 
+    def _visits(self, moves: int):
+        """Chess names a root's visit counts by the root's moves, staged beside them."""
+        if self._run_root_moves is None:
+            self._run_root_moves = torch.zeros(tuple(self._run_na.shape), dtype=torch.int16, device=self.dev)
+        self.eng.chess_selfplay_visits(self._run_na.data_ptr(), self._run_root_moves.data_ptr(), moves)
+
     def _launch(self, moves: int, budget: int | None, carry: bool, s: int):
         """zc_chess_selfplay_async / zc_chess_selfplay_pooled_async."""
         head = [self.eng.handle, 0, self.G, ctypes.byref(self._pb), self.sims, self.c, self.bs, self.policy,
@@ -852,7 +915,8 @@ class ChessSelfPlay(_SelfPlayPool):
     def run(self, moves: int, stream: int | None = None, kernel_done=None) -> torch.Tensor:
         """Crude score: `moves` moves for every game in ONE launch (zc_chess_selfplay_async),
         then the multi-step recording — the same games, pool and labels as `moves` calls of
-        step().  Returns the per-step results [moves, G]; self.stats sums the moves."""
+        step() (with fused_policy their root visit counts too; a record_policy pool without it
+        refuses).  Returns the per-step results [moves, G]; self.stats sums the moves."""
         return self._fused(moves, None, stream, kernel_done)
 
     def run_pooled(self, budget: int, moves_cap: int, stream: int | None = None, kernel_done=None) -> torch.Tensor:
