@@ -801,6 +801,34 @@ int zc_traj_policy_dense_async(int32_t n_rows, const int64_t *d_first, const int
                                const uint32_t *d_entries, int32_t width, int32_t dtype, void *d_out,
                                void *hip_stream);
 
+/* ---- arena: two networks on one pool of games (arena.hip) ------------------------------
+ * A pool whose games are evaluated by network A or B (key bit 0 of each game: 0 = A, 1 = B)
+ * partitions its games before a search and moves each flush's rows through the partition:
+ * gather -> network A on the first count[0] games' rows, B on the rest -> scatter.  Device
+ * pointers; the calls only enqueue on hip_stream (no allocation, no synchronisation: they can
+ * be captured).  They keep no engine and record no message: ZC_EINVAL names a violated
+ * condition below (zeroclone_amd/_native.py's wrappers say which).
+ *
+ * zc_arena_route_async: d_perm[n] = the STABLE partition of 0..n-1 by d_key[i] & 1 (the
+ * indices with bit 0 clear in ascending order, then those with it set in ascending order;
+ * the key's other bits are ignored), d_count[2] = the two group sizes.  One workgroup of
+ * ZC_ARENA_ROUTE_THREADS threads walks the keys in chunks of that size.  n >= 0.
+ *
+ * zc_arena_gather_async: for i < n, j < rows: row d_perm[i] * game_rows + j of d_src ->
+ * row i * rows + j of d_dst (rows of row_bytes bytes; a game owns game_rows rows in game
+ * order and `rows` of them, 1 <= rows <= game_rows, in partition order).
+ * zc_arena_scatter_async: the inverse, row i * rows + j of d_src -> row d_perm[i] * game_rows
+ * + j of d_dst; rows j >= rows of a game are left untouched.  row_bytes: any positive multiple
+ * of 2; both base pointers 2-byte aligned; the copy uses the widest access (16, 8, 4 or 2
+ * bytes per lane) that row_bytes and both pointers allow.  n * game_rows < 2^31.  An entry of
+ * d_perm outside [0, n) copies nothing. */
+#define ZC_ARENA_ROUTE_THREADS 1024
+int zc_arena_route_async(int32_t n, const int32_t *d_key, int32_t *d_perm, int32_t *d_count, void *hip_stream);
+int zc_arena_gather_async(int32_t n, int32_t rows, int32_t game_rows, int64_t row_bytes, const int32_t *d_perm,
+                          const void *d_src, void *d_dst, void *hip_stream);
+int zc_arena_scatter_async(int32_t n, int32_t rows, int32_t game_rows, int64_t row_bytes, const int32_t *d_perm,
+                           const void *d_src, void *d_dst, void *hip_stream);
+
 /* ---- any game backend: SURVEY §8(b)'s fallback (gen_search.hip) ----------------------
  * mcts.get_move (mcts.cpp:102-160) for a backend the device knows nothing about: the caller
  * keeps the game states and move objects (backend.get_legal_moves / play_move, the policy

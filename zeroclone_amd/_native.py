@@ -297,6 +297,12 @@ SIGNATURES = [
                                                    ctypes.c_void_p]),
     ("zc_traj_policy_dense_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_arena_route_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p]),
+    ("zc_arena_gather_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_arena_scatter_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("zc_chess_from_fen", ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
     ("zc_chess_init", ctypes.c_int, [ctypes.c_void_p]),
     ("zc_c4_from_rows", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, P(C4State)]),
@@ -418,6 +424,60 @@ def unpack_chess_move(m: int):
 
 def pack_chess_move(fr: int, fc: int, tr: int, tc: int, value: float) -> int:
     return (fr * 8 + fc) | ((tr * 8 + tc) << 6) | (int(value) << 12)
+
+
+ARENA_ROUTE_THREADS = 1024   # ZC_ARENA_ROUTE_THREADS: the route kernel's workgroup, and its chunk of keys
+
+
+def _arena_rc(name: str, rc: int):
+    """The arena entry points record no message (include/zeroclone.h): the wrappers below check
+    what the library checks, so a code from it is a launch error."""
+    if rc == ZC_EINVAL:
+        raise ValueError(f"{name}: bad argument")
+    if rc < 0:
+        raise ZeroCloneError(rc, f"{name}: the launch failed")
+
+
+def arena_route(n: int, d_key: int, d_perm: int, d_count: int, stream: int = 0):
+    """zc_arena_route_async on device pointers: d_perm[n] int32 = the stable partition of 0..n-1 by
+    d_key[i] & 1, d_count[2] int32 = the group sizes.  Only enqueues."""
+    if n < 0:
+        raise ValueError(f"n must be >= 0 (got {n})")
+    if not d_count or (n and not (d_key and d_perm)):
+        raise ValueError("zc_arena_route_async: null device pointer")
+    _arena_rc("zc_arena_route_async", lib().zc_arena_route_async(
+        int(n), ctypes.c_void_p(d_key), ctypes.c_void_p(d_perm), ctypes.c_void_p(d_count), ctypes.c_void_p(stream or None)))
+
+
+def _arena_copy(fn_name: str, n, rows, game_rows, row_bytes, d_perm, d_src, d_dst, stream):
+    if n < 0 or not 1 <= rows <= game_rows:
+        raise ValueError(f"{fn_name}: need n >= 0 and 1 <= rows <= game_rows (got n {n}, rows {rows}, "
+                         f"game_rows {game_rows})")
+    if row_bytes < 2 or row_bytes % 2 or row_bytes >= 1 << 31:
+        raise ValueError(f"{fn_name}: row_bytes must be a positive multiple of 2 below 2^31 (got {row_bytes})")
+    if n * game_rows >= 1 << 31:
+        raise ValueError(f"{fn_name}: n * game_rows must be < 2^31")
+    if n and not (d_perm and d_src and d_dst):
+        raise ValueError(f"{fn_name}: null device pointer")
+    if (d_src | d_dst) & 1:
+        raise ValueError(f"{fn_name}: source and destination must be 2-byte aligned")
+    _arena_rc(fn_name, getattr(lib(), fn_name)(
+        int(n), int(rows), int(game_rows), int(row_bytes), ctypes.c_void_p(d_perm), ctypes.c_void_p(d_src),
+        ctypes.c_void_p(d_dst), ctypes.c_void_p(stream or None)))
+
+
+def arena_gather(n: int, rows: int, game_rows: int, row_bytes: int, d_perm: int, d_src: int, d_dst: int,
+                 stream: int = 0):
+    """zc_arena_gather_async: row d_perm[i] * game_rows + j of d_src -> row i * rows + j of d_dst
+    (i < n, j < rows).  Only enqueues."""
+    _arena_copy("zc_arena_gather_async", n, rows, game_rows, row_bytes, d_perm, d_src, d_dst, stream)
+
+
+def arena_scatter(n: int, rows: int, game_rows: int, row_bytes: int, d_perm: int, d_src: int, d_dst: int,
+                  stream: int = 0):
+    """zc_arena_scatter_async: the inverse of arena_gather (row i * rows + j of d_src -> row
+    d_perm[i] * game_rows + j of d_dst; a game's rows j >= rows are left untouched)."""
+    _arena_copy("zc_arena_scatter_async", n, rows, game_rows, row_bytes, d_perm, d_src, d_dst, stream)
 
 
 class NativeEngine:

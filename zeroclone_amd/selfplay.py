@@ -617,9 +617,12 @@ class C4SelfPlay(_SelfPlayPool):
                  rank: int = 0, device: int = 0, record: bool = True, games_cap: int | None = None,
                  net=None, puct_net=None, temperature: float = 1.0, puct_seed: int = 1, streams: int = 1,
                  record_policy: bool = False, pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
-                 reuse_tree: bool = False, tree_nodes: int | None = None, fused_policy: bool = False):
+                 reuse_tree: bool = False, tree_nodes: int | None = None, fused_policy: bool = False,
+                 puct_args: dict | None = None):
         """record_policy: every step()'s root visit counts go with the positions into the
         trajectories (TrajBatch.pi / policy_targets(7)), in every search mode.
+        puct_args: C4PuctSearch's c_puct / dirichlet_alpha / dirichlet_eps, where its defaults
+        are not wanted.
         fused_policy (needs record_policy): run(), run_pooled() (carry=True too) and drain()
         record them as well — the launch stages every finished move's counts
         (zc_c4_selfplay_visits, [moves][games][7] int32) and zc_traj_policy_record_steps_async
@@ -647,7 +650,8 @@ class C4SelfPlay(_SelfPlayPool):
         self.moves16 = torch.zeros(games, dtype=torch.int16, device=self.dev)
         self.carry_pending = False   # run_pooled(carry=True) left moves in flight (drain() finishes them)
         self._networks(net, valued.C4ValuedSearch, {}, streams,
-                       puct_net, valued.C4PuctSearch, dict(seed=puct_seed, reuse=self.reuse_tree), streams)
+                       puct_net, valued.C4PuctSearch,
+                       dict(seed=puct_seed, reuse=self.reuse_tree, **(puct_args or {})), streams)
 
     def start(self, quota: int | None = None):
         """Every slot back to the opening; with a quota, slots beyond it idle and finished
@@ -806,9 +810,12 @@ class ChessSelfPlay(_SelfPlayPool):
                  hist_cap: int = 1024, puct_net=None, temperature: float = 1.0, puct_seed: int = 1,
                  puct_streams: int = 1, streams: int = 1, record_policy: bool = False,
                  pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
-                 reuse_tree: bool = False, tree_nodes: int | None = None, fused_policy: bool = False):
+                 reuse_tree: bool = False, tree_nodes: int | None = None, fused_policy: bool = False,
+                 puct_args: dict | None = None):
         """record_policy: every step()'s root visit counts go with the positions into the
         trajectories (TrajBatch.pi / policy_targets(4096)), in every search mode.
+        puct_args: ChessPuctSearch's c_puct / dirichlet_alpha / dirichlet_eps, where its defaults
+        are not wanted.
         fused_policy (needs record_policy): run() and run_pooled() record them as well — the
         launch stages every move's counts and root moves (zc_chess_selfplay_visits,
         [moves][games][256] int32 + int16: about 63 MB at 60 steps x 1024 games) and
@@ -844,8 +851,8 @@ class ChessSelfPlay(_SelfPlayPool):
         # from the select kernel (no conversion launch per flush)
         nhwc = bool(getattr(puct_net, "conv_head", False)) and os.environ.get("ZC_PUCT_NHWC", "1") != "0"   # 0: A/B
         self._networks(net, valued.ChessValuedSearch, dict(policy=self.policy, freedom=self.freedom), streams,
-                       puct_net, valued.ChessPuctSearch, dict(seed=puct_seed, planes_nhwc=nhwc, reuse=self.reuse_tree),
-                       puct_streams)
+                       puct_net, valued.ChessPuctSearch,
+                       dict(seed=puct_seed, planes_nhwc=nhwc, reuse=self.reuse_tree, **(puct_args or {})), puct_streams)
         self.hist_cap = hist_cap  # moves per side
         self.hist = torch.zeros((games, 2, self.hist_cap), dtype=torch.int16, device=self.dev)
         self.hlen = torch.zeros((games, 2), dtype=torch.int32, device=self.dev)

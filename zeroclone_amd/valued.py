@@ -294,6 +294,128 @@ class NetValue:
         return out
 
 
+class _Routed:
+    """Two callables behind one: game perm[i] (i < n_a) is fn_a's, the others fn_b's
+    (`set_route`, the partition of zc_arena_route_async).  A flush's rows are gathered into
+    partition order (zc_arena_gather_async), fn_a runs on the first n_a games' rows and fn_b on
+    the rest, each in one call and an empty group in none, and the outputs are scattered back
+    to game order (zc_arena_scatter_async).  Only the planes are routed: the inner callables
+    get leaves=None.  The gather buffers are kept between calls; n_a is a host value, so a
+    routed flush cannot be replayed from a graph captured under another partition."""
+
+    def __init__(self, fn_a, fn_b):
+        self.fns = (fn_a, fn_b)
+        self.perm, self.n_a = None, 0
+        self._bufs = {}
+
+    def set_route(self, perm: torch.Tensor, n_a: int):
+        """perm [n] int32 on the device: the games in partition order; the first n_a are fn_a's."""
+        if perm.dtype != torch.int32 or perm.dim() != 1 or not perm.is_contiguous():
+            raise ValueError("perm must be a contiguous int32 [n_games] tensor")
+        if not 0 <= int(n_a) <= perm.shape[0]:
+            raise ValueError(f"n_a {n_a} outside [0, {perm.shape[0]}]")
+        self.perm, self.n_a = perm, int(n_a)
+
+    def _buf(self, name: str, shape: tuple, like: torch.Tensor, dtype=None) -> torch.Tensor:
+        """One buffer per use and shape (a search has two or three: the full flush, the short
+        last one, the roots), allocated at its first call."""
+        key = (name, tuple(shape), dtype or like.dtype, like.device)
+        b = self._bufs.get(key)
+        if b is None:
+            b = self._bufs[key] = torch.zeros(key[1], dtype=key[2], device=key[3])
+        return b
+
+    def _games(self, n: int):
+        if self.perm is None or self.perm.shape[0] != n:
+            raise ValueError(f"set_route() first, with a partition of the flush's {n} games")
+
+    def _gather(self, name: str, src: torch.Tensor, n: int, rows: int, game_rows: int) -> torch.Tensor:
+        """The first `rows` of each game's game_rows rows of src, in partition order."""
+        if not src.is_contiguous() or src.shape[0] != n * game_rows:
+            raise ValueError(f"a routed tensor must be contiguous with {n * game_rows} rows")
+        dst = self._buf(name, (n * rows, *src.shape[1:]), src)
+        _native.arena_gather(n, rows, game_rows, src[0].numel() * src.element_size(), self.perm.data_ptr(),
+                             src.data_ptr(), dst.data_ptr(), _stream(src.device))
+        return dst
+
+    def _scatter(self, src: torch.Tensor, dst: torch.Tensor, n: int, rows: int, game_rows: int):
+        _native.arena_scatter(n, rows, game_rows, src[0].numel() * src.element_size(), self.perm.data_ptr(),
+                              src.data_ptr(), dst.data_ptr(), _stream(src.device))
+
+    def _groups(self, n: int, rows: int):
+        """(fn, first row, end row, first game, end game) of each non-empty group."""
+        k = self.n_a
+        return [(fn, lo * rows, hi * rows, lo, hi) for fn, lo, hi in ((self.fns[0], 0, k), (self.fns[1], k, n))
+                if hi > lo]
+
+
+class RoutedValue(_Routed):
+    """A value search's value_fn over two value functions (e.g. two NetValue)."""
+
+    def _values(self, planes, n: int, rows: int, game_rows: int, counts, out):
+        self._games(n)
+        g = self._gather("planes", planes, n, rows, game_rows)
+        v = self._buf("values", (n * rows,), planes, torch.float64)
+        for fn, lo, hi, g0, g1 in self._groups(n, rows):
+            v[lo:hi].copy_(fn(None, g[lo:hi], counts[g0:g1] if counts is not None else None).reshape(-1))
+        self._scatter(v, out, n, rows, game_rows)
+        return out
+
+    @torch.no_grad()
+    def __call__(self, leaves, planes, counts):
+        n = counts.shape[0]
+        rows = planes.shape[0] // n
+        self._games(n)
+        c = self._gather("counts", counts, n, 1, 1)
+        return self._values(planes, n, rows, rows, c, self._buf("out", (n * rows,), planes, torch.float64))
+
+    @torch.no_grad()
+    def rows(self, planes, n: int, bs: int, nb: int, out):
+        """The short last flush (NetValue.rows): the first nb rows of each game are gathered and
+        evaluated (counts=None for the inner callables), and the values land in out's first nb
+        slots of each game."""
+        return self._values(planes, n, nb, bs, None, out)
+
+
+class RoutedPolicy(_Routed):
+    """A PUCT search's net_fn over two policy + value networks (e.g. two PolicyNet): returns
+    (values fp64, logits) in game order.  Like PolicyNet it depends on the planes alone, so the
+    roots flush evaluates one row a game.  Both networks must return logits of one dtype and
+    width."""
+    roots_only = True
+
+    def __init__(self, fn_a, fn_b):
+        super().__init__(fn_a, fn_b)
+        self._logits = None   # (dtype, width) of the first network that ran
+
+    @torch.no_grad()
+    def __call__(self, leaves, planes, counts):
+        n = counts.shape[0]
+        rows = planes.shape[0] // n
+        self._games(n)
+        g = self._gather("planes", planes, n, rows, rows)
+        c = self._gather("counts", counts, n, 1, 1)
+        v = self._buf("values", (n * rows,), planes, torch.float64)
+        lg = None
+        for fn, lo, hi, g0, g1 in self._groups(n, rows):
+            fv, fl = fn(None, g[lo:hi], c[g0:g1])
+            fl = fl.reshape(hi - lo, -1)
+            if self._logits is None:
+                self._logits = (fl.dtype, fl.shape[1])
+            if (fl.dtype, fl.shape[1]) != self._logits:
+                raise ValueError(f"the two networks' logits differ: {fl.dtype} x {fl.shape[1]} against "
+                                 f"{self._logits[0]} x {self._logits[1]}")
+            if lg is None:
+                lg = self._buf("logits", (n * rows, fl.shape[1]), fl)
+            v[lo:hi].copy_(fv.reshape(-1))
+            lg[lo:hi].copy_(fl)
+        vo = self._buf("vout", (n * rows,), planes, torch.float64)
+        lo_ = self._buf("lout", tuple(lg.shape), lg)
+        self._scatter(v, vo, n, rows, rows)
+        self._scatter(lg, lo_, n, rows, rows)
+        return vo, lo_
+
+
 class HostValue:
     """Any reference-style Value object: value.batch(states, backend=backend) per game per
     flush, on c4_backend states built from the device leaves.  With `eng`, Python's global
