@@ -801,6 +801,75 @@ int zc_traj_policy_dense_async(int32_t n_rows, const int64_t *d_first, const int
                                const uint32_t *d_entries, int32_t width, int32_t dtype, void *d_out,
                                void *hip_stream);
 
+/* ---- training: minibatches and the loss from compact rows (train.hip) ------------------
+ * The learner's two device steps.  Device pointers; the calls only enqueue on hip_stream (no
+ * allocation, no synchronisation: they can be captured).  They keep no engine and record no
+ * message: ZC_EINVAL names a violated condition below (zeroclone_amd/_native.py's wrappers say
+ * which).
+ *
+ * A training set is positions as the self-play pools keep them (zc_c4_state rows of 24 bytes or
+ * zc_chess_state rows of 72), their Engine.get_dataset labels and, optionally, the root visit
+ * counts in the TrajBatch CSR: row i owns d_pi[d_pi_off[i] .. d_pi_off[i + 1]), entries
+ * id | count << 16 as zc_traj_policy_append_async writes them.  d_pi_off and d_pi both NULL: no
+ * policy targets. */
+#define ZC_TRAIN_C4 0
+#define ZC_TRAIN_CHESS 1
+typedef struct zc_train_set {
+    int32_t game;       /* ZC_TRAIN_C4 / ZC_TRAIN_CHESS                  */
+    int32_t row_bytes;  /* 24 / 72                                       */
+    int64_t n_rows;
+    const void *d_rows;
+    const int32_t *d_labels;   /* [n_rows]                                */
+    const int64_t *d_pi_off;   /* [n_rows + 1] or NULL                    */
+    const uint32_t *d_pi;      /* the entries, or NULL                    */
+} zc_train_set;
+/* zc_train_batch_async: batch row b < B is set row i = d_index[b] (int64; any order, repeats
+ * allowed).  One wave per batch row.
+ *   d_planes  [B][C][H][W], planes_dtype ZC_F32 / ZC_F16, state_to_tensor layout: Connect4
+ *             [2][6][7] with the side to move first, chess [17][8][8] as zc_chess_planes_async
+ *   d_z       [B] float: the label
+ *   d_legal   [B][stride] uint16, d_n_legal [B] int32: the position's legal moves.  Connect4:
+ *             stride 7, the columns that are not full in ascending order; chess: stride
+ *             ZC_CHESS_MAX_MOVES, the list and order of zc_chess_legal_moves_async.  Slots past
+ *             n_legal are 0.
+ *   d_target  [B][stride] float, aligned with d_legal: count(move j) / the sum of the row's
+ *             counts (one IEEE single division, the value zc_traj_policy_dense_async writes), 0
+ *             for a legal move without an entry; the whole row 0 when the set row has no entries
+ *             or the set no policy.  Entries are matched by move id (chess: by from / to, the
+ *             packed move's low 12 bits).
+ *   d_status  [1] int32, OR-ed into (the caller zeroes it): bit 0 an entry named a move that is
+ *             not in the position's legal list (the entry is dropped, its count stays in the
+ *             row's sum), bit 1 an index outside [0, n_rows) (the batch row is all zeros,
+ *             n_legal 0), bit 2 a chess position with more than ZC_CHESS_MAX_MOVES legal moves
+ *             (n_legal 0).  Nothing is read or written out of bounds.
+ * d_flags [B] uint8 or NULL: bit 0 = mirror the row left to right (Connect4 only: column c
+ * becomes 6 - c in the planes, the legal list — still ascending — and the targets).  Chess with
+ * d_flags != NULL is ZC_EINVAL. */
+int zc_train_batch_async(const zc_train_set *set, int32_t B, const int64_t *d_index, const uint8_t *d_flags,
+                         int32_t planes_dtype, void *d_planes, float *d_z, uint16_t *d_legal, int32_t *d_n_legal,
+                         float *d_target, int32_t *d_status, void *hip_stream);
+/* zc_train_loss_async: value and policy loss of B >= 1 rows with their gradients, fp32
+ * arithmetic throughout, the row maximum subtracted before exp.
+ *   Lv = mean_b (v_b - z_b)^2                      d_grad_v[b] = 2 (v_b - z_b) / B
+ *   a row is a policy row when its targets sum to more than 0; P = their number
+ *   p_b = softmax of row b's logits over its legal moves (d_legal[b][0 .. d_n_legal[b]))
+ *   Lp = 1/P sum over policy rows of -sum_j target_bj log p_bj          (0 when P = 0)
+ *   d_grad_logits[b][index(j)] = (p_bj - target_bj) / P on policy rows, 0 everywhere else
+ * d_logits [B][width], logits_dtype ZC_F32 / ZC_F16; d_grad_logits the same shape and type,
+ * written in full (16-byte aligned for width 4096).  width 7: a move's index is its id (ids
+ * above 6 are ignored), stride <= 64; width 4096: (id & 63) * 64 + ((id >> 6) & 63), stride <=
+ * ZC_CHESS_MAX_MOVES.  d_v [B] float is the tanh head's output.  d_loss [2] = {Lv, Lp}.
+ * d_logits NULL: a value-only model — Lp = 0, d_loss and d_grad_v alone are written and the
+ * policy arguments are ignored.  The sums over rows run in a fixed order: the same inputs give
+ * the same bits.  Non-finite logits give non-finite results; nothing is checked.
+ * d_scratch: device scratch of at least zc_train_loss_scratch_bytes(B) bytes, 16-byte aligned.
+ * Three launches (two for a value-only model). */
+int zc_train_loss_scratch_bytes(int32_t B, int64_t *bytes);
+int zc_train_loss_async(int32_t B, int32_t width, int32_t stride, const void *d_logits, int32_t logits_dtype,
+                        const float *d_v, const float *d_z, const uint16_t *d_legal, const int32_t *d_n_legal,
+                        const float *d_target, void *d_scratch, int64_t scratch_bytes, float *d_loss, float *d_grad_v,
+                        void *d_grad_logits, void *hip_stream);
+
 /* ---- arena: two networks on one pool of games (arena.hip) ------------------------------
  * A pool whose games are evaluated by network A or B (key bit 0 of each game: 0 = A, 1 = B)
  * partitions its games before a search and moves each flush's rows through the partition:

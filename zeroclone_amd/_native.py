@@ -70,6 +70,14 @@ class TrajPolicyBuffers(ctypes.Structure):
                 ("d_pctl", ctypes.c_void_p)]
 
 
+class TrainSet(ctypes.Structure):
+    """zc_train_set (include/zeroclone.h): a compact training set's device pointers."""
+    _fields_ = [("game", ctypes.c_int32), ("row_bytes", ctypes.c_int32), ("n_rows", ctypes.c_int64),
+                ("d_rows", ctypes.c_void_p), ("d_labels", ctypes.c_void_p), ("d_pi_off", ctypes.c_void_p),
+                ("d_pi", ctypes.c_void_p)]
+
+
+ZC_TRAIN_C4, ZC_TRAIN_CHESS = 0, 1
 ZC_TRAJ_PI_ENTRIES, ZC_TRAJ_PI_OVERFLOW = 0, 1
 ZC_TRAJ_PI_MAX_COUNT = 65535   # a policy entry's count field: 16 bits
 ZC_TRAJ_POSITIONS, ZC_TRAJ_GAMES, ZC_TRAJ_NEXT, ZC_TRAJ_QUOTA, ZC_TRAJ_FINISHED, ZC_TRAJ_OVERFLOW = range(6)
@@ -297,6 +305,14 @@ SIGNATURES = [
                                                    ctypes.c_void_p]),
     ("zc_traj_policy_dense_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_train_batch_async", ctypes.c_int, [P(TrainSet), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_train_loss_scratch_bytes", ctypes.c_int, [ctypes.c_int32, P(ctypes.c_int64)]),
+    ("zc_train_loss_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("zc_arena_route_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p]),
     ("zc_arena_gather_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
@@ -478,6 +494,70 @@ def arena_scatter(n: int, rows: int, game_rows: int, row_bytes: int, d_perm: int
     """zc_arena_scatter_async: the inverse of arena_gather (row i * rows + j of d_src -> row
     d_perm[i] * game_rows + j of d_dst; a game's rows j >= rows are left untouched)."""
     _arena_copy("zc_arena_scatter_async", n, rows, game_rows, row_bytes, d_perm, d_src, d_dst, stream)
+
+
+def _train_rc(name: str, rc: int):
+    """The training entry points record no message either: the wrappers below check what the
+    library checks."""
+    if rc == ZC_EINVAL:
+        raise ValueError(f"{name}: bad argument")
+    if rc < 0:
+        raise ZeroCloneError(rc, f"{name}: the launch failed")
+
+
+def train_batch(ts: TrainSet, B: int, d_index: int, d_flags: int, planes_f16: bool, d_planes: int, d_z: int,
+                d_legal: int, d_n_legal: int, d_target: int, d_status: int, stream: int = 0):
+    """zc_train_batch_async on device pointers: batch row b = set row d_index[b] decoded to planes,
+    label, legal moves and targets.  d_flags 0: no mirror flags.  Only enqueues."""
+    if B < 0:
+        raise ValueError(f"B must be >= 0 (got {B})")
+    if (ts.game, ts.row_bytes) not in ((ZC_TRAIN_C4, 24), (ZC_TRAIN_CHESS, 72)):
+        raise ValueError(f"zc_train_batch_async: game {ts.game} with rows of {ts.row_bytes} bytes")
+    if ts.game == ZC_TRAIN_CHESS and d_flags:
+        raise ValueError("zc_train_batch_async: a chess position has no mirror image (flags must be None)")
+    if bool(ts.d_pi_off) != bool(ts.d_pi):
+        raise ValueError("zc_train_batch_async: d_pi_off and d_pi go together")
+    if B and not (ts.d_rows and ts.d_labels and d_index and d_planes and d_z and d_legal and d_n_legal and d_target
+                  and d_status):
+        raise ValueError("zc_train_batch_async: null device pointer")
+    _train_rc("zc_train_batch_async", lib().zc_train_batch_async(
+        ctypes.byref(ts), int(B), ctypes.c_void_p(d_index), ctypes.c_void_p(d_flags or None),
+        ZC_F16 if planes_f16 else ZC_F32, ctypes.c_void_p(d_planes), ctypes.c_void_p(d_z), ctypes.c_void_p(d_legal),
+        ctypes.c_void_p(d_n_legal), ctypes.c_void_p(d_target), ctypes.c_void_p(d_status),
+        ctypes.c_void_p(stream or None)))
+
+
+def train_loss_scratch_bytes(B: int) -> int:
+    need = ctypes.c_int64(0)
+    _train_rc("zc_train_loss_scratch_bytes", lib().zc_train_loss_scratch_bytes(int(B), ctypes.byref(need)))
+    return need.value
+
+
+def train_loss(B: int, width: int, stride: int, d_logits: int, logits_f16: bool, d_v: int, d_z: int, d_legal: int,
+               d_n_legal: int, d_target: int, d_scratch: int, scratch_bytes: int, d_loss: int, d_grad_v: int,
+               d_grad_logits: int, stream: int = 0):
+    """zc_train_loss_async on device pointers: d_loss[2] = {Lv, Lp}, d_grad_v [B], d_grad_logits
+    [B, width] (written in full).  d_logits 0: a value-only model.  Only enqueues."""
+    if B < 1:
+        raise ValueError(f"B must be >= 1 (got {B})")
+    if not (d_v and d_z and d_loss and d_grad_v):
+        raise ValueError("zc_train_loss_async: null device pointer")
+    if not d_scratch or d_scratch & 15 or scratch_bytes < (6 * B + 4) * 4:
+        raise ValueError(f"zc_train_loss_async: scratch of {scratch_bytes} bytes, need {(6 * B + 4) * 4} 16-byte aligned")
+    if d_logits:
+        if width not in (7, 4096):
+            raise ValueError(f"width must be 7 or 4096 (got {width})")
+        if not 1 <= stride <= (64 if width == 7 else CHESS_MAX_MOVES):
+            raise ValueError(f"stride {stride} out of range for width {width}")
+        if not (d_legal and d_n_legal and d_target and d_grad_logits):
+            raise ValueError("zc_train_loss_async: null device pointer")
+        if width == 4096 and d_grad_logits & 15:
+            raise ValueError("zc_train_loss_async: grad_logits must be 16-byte aligned")
+    _train_rc("zc_train_loss_async", lib().zc_train_loss_async(
+        int(B), int(width), int(stride), ctypes.c_void_p(d_logits or None), ZC_F16 if logits_f16 else ZC_F32,
+        ctypes.c_void_p(d_v), ctypes.c_void_p(d_z), ctypes.c_void_p(d_legal or None), ctypes.c_void_p(d_n_legal or None),
+        ctypes.c_void_p(d_target or None), ctypes.c_void_p(d_scratch), int(scratch_bytes), ctypes.c_void_p(d_loss),
+        ctypes.c_void_p(d_grad_v), ctypes.c_void_p(d_grad_logits or None), ctypes.c_void_p(stream or None)))
 
 
 class NativeEngine:

@@ -584,6 +584,36 @@ class _SelfPlayPool:
                                    na=self._run_na, root_moves=self._run_root_moves)
         return self._run_results
 
+    def set_network(self, model):
+        """Search with `model`'s current weights from the next step() on: the hand-back of the
+        learner's loop (learner.full_training_run).  `model` is the trainable module — a
+        `nets.ValueNetwork` for a pool built with `net=`, a `nets.PolicyValueNetwork` for one
+        built with `puct_net=`; its inference form is built here (learner.inference_form) and
+        replaces the pool's value / PUCT callable, every stream's replica included.  Kept PUCT
+        trees (reuse_tree) hold the old network's priors and values and are dropped.  A step graph
+        captured before (`capture_step()`; the caller holds it) has the old network's launches
+        baked in: it is not this pool's to drop — capture again.  A pool built without a network
+        refuses."""
+        from . import learner, nets
+        if self.ps is None and self.vs is None:
+            raise ValueError("this pool was built without a network (net= / puct_net=): its search takes none")
+        puct = self.ps is not None
+        if isinstance(model, nets.PolicyValueNetwork) != puct:
+            raise TypeError("a puct_net= pool takes a PolicyValueNetwork, a net= pool a ValueNetwork")
+        net = learner.inference_form(model, self.dev)
+        old = self.net_fn if puct else self.value_fn
+        wrap = valued.PolicyNet if puct else valued.NetValue
+        if isinstance(old, (list, tuple)):   # one replica a stream: weights shared, buffers its own
+            new = [wrap(net.replica() if hasattr(net, "replica") else net) for _ in old]
+        else:
+            new = wrap(net)
+        if puct:
+            self.net_fn = new
+            if getattr(self, "reuse_tree", False):
+                self.ps.forget()
+        else:
+            self.value_fn = new
+
     def check(self):
         """Raises what the device collected (chess)."""
 
