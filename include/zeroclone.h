@@ -648,6 +648,22 @@ int zc_net_tower_policy_ex_async(int32_t n_boards, int32_t h, int32_t w, int32_t
                                  const void *d_in, const void *d_packed_weights, const float *d_biases,
                                  const float *d_fc_w, float fc_b, double *d_values, const void *d_pw, const float *d_pb,
                                  int32_t policy_channels, int32_t relu, void *d_pout, void *hip_stream);
+/* The counted forms: zc_net_tower_async and zc_net_tower_policy_ex_async on a row count that lives
+ *   on the device (d_count, int32, 4-byte aligned; read when the launch runs, so the call can
+ *   be captured and replayed on another count).  n_boards is the CAPACITY: the grid is sized
+ *   for it and every buffer holds that many rows.  The launch evaluates rows [0, min(*d_count,
+ *   n_boards)) (a negative count is 0): a workgroup whose first board is at or past the count
+ *   returns before it touches anything, and rows at or past the count are neither read nor
+ *   written.  The rows below the count get the bits the plain launch gives them — a board's
+ *   result depends on no other board.  The evaluation cache's miss path (below). */
+int zc_net_tower_counted_async(int32_t n_boards, int32_t h, int32_t w, int32_t cin0, int32_t nconv, const void *d_in,
+                               const void *d_packed_weights, const float *d_biases, void *d_out, const float *d_fc_w,
+                               float fc_b, double *d_values, const int32_t *d_count, void *hip_stream);
+int zc_net_tower_policy_counted_async(int32_t n_boards, int32_t h, int32_t w, int32_t cin0, int32_t nconv,
+                                      const void *d_in, const void *d_packed_weights, const float *d_biases,
+                                      const float *d_fc_w, float fc_b, double *d_values, const void *d_pw,
+                                      const float *d_pb, int32_t policy_channels, int32_t relu, void *d_pout,
+                                      const int32_t *d_count, void *hip_stream);
 int zc_net_planes_to_nhwc_async(int32_t n, int32_t cin, int32_t hw, int32_t cpad, const void *d_planes, void *d_out,
                                 void *hip_stream);
 int zc_net_value_head_async(int32_t n, int32_t hw, const void *d_act, const float *d_fc_w, float fc_b, double *d_values,
@@ -897,6 +913,63 @@ int zc_arena_gather_async(int32_t n, int32_t rows, int32_t game_rows, int64_t ro
                           const void *d_src, void *d_dst, void *hip_stream);
 int zc_arena_scatter_async(int32_t n, int32_t rows, int32_t game_rows, int64_t row_bytes, const int32_t *d_perm,
                            const void *d_src, void *d_dst, void *hip_stream);
+
+/* ---- evaluation cache: skip the network for rows already evaluated (evalcache.hip) --------
+ * A set-associative table in device memory, keyed by the compact leaf row (zc_c4_state 24 B,
+ * zc_chess_state 72 B: the planes are a function of that row, so equal rows have equal planes
+ * and, the network computing every board on its own, equal outputs).  The payload is the fp64
+ * value and logit_bytes of logits (0 for a value network).  A HIT IS FULL-KEY EQUALITY; the
+ * 16-bit hash tag in an entry's meta word only pre-filters.  ZC_EVALCACHE_WAYS ways per set;
+ * the number of sets is the largest power of two with ways * sets <= entries.  Layout:
+ *   [header 64 B][meta u32 x E][keys key_bytes x E][values f64 x E][logits round16(logit_bytes) x E]
+ * key_bytes: a multiple of 8 in [8, 512]; logit_bytes: even, >= 0.  The calls take the table's
+ * three sizes every time (the block itself holds no description), keep no engine and record no
+ * message: ZC_EINVAL names a violated condition below.  They only enqueue on hip_stream (no
+ * allocation, no host read: they can be captured).
+ *
+ * ONE TABLE IS USED BY ONE STREAM AT A TIME.  Probe and commit are ordered by that stream, a
+ * probe never runs beside a commit, and so there is no reader / writer protocol.
+ *
+ * zc_evalcache_bytes: *bytes = the block's size, *sets = its sets (either may be NULL).
+ * zc_evalcache_clear_async: empties the table (d_table 16-byte aligned, zc_evalcache_bytes long).
+ *
+ * A flush goes probe -> counted network on the dense rows -> commit, with *d_count == 0 before
+ * the probe (the commit leaves it so).
+ *
+ * zc_evalcache_probe_async: n_rows rows take part, the first rows_per_game of each game's
+ * game_rows rows of the buffers (as zc_arena_gather_async; n_rows a multiple of rows_per_game).
+ * One wave per row.  Hit: the entry's value -> d_out_values[row], its logits -> d_out_logits +
+ * row * logit_bytes.  Miss: the row takes dense slot s = the next value of *d_count (one atomic
+ * per workgroup), its plane_bytes of d_planes go to d_dense_planes + s * plane_bytes and
+ * d_miss_rows[s] = row; its output slots are left untouched.  The dense order may differ from
+ * run to run.  The copies use the widest access (16, 8, 4 or 2 bytes) the sizes and pointers
+ * allow.  d_stats (may be NULL): four int64 counters, ZC_EVALCACHE_STAT_*; the probe adds to
+ * PROBED and HITS.
+ *
+ * zc_evalcache_commit_async: one wave per dense slot s < min(*d_count, n_rows) (n_rows,
+ * rows_per_game, game_rows as the probe's): d_dense_values[s] and d_dense_logits + s *
+ * logit_bytes go to row d_miss_rows[s]'s output slots and into the table — the set's first
+ * empty way, else the way three hash bits pick.  The way is claimed with one atomicCAS on its
+ * meta word and written only by the wave that won it; an entry claimed in a launch cannot be
+ * claimed again in that launch.  An insert is DROPPED (the cache is best-effort) when a way of
+ * the set already carries the key's tag (the same row pending twice in the flush), or the
+ * victim's claim is lost.  Adds to INSERTS and DROPPED.  A one-thread launch then sets *d_count
+ * = 0 and moves the table to its next epoch. */
+#define ZC_EVALCACHE_WAYS 8
+#define ZC_EVALCACHE_STAT_PROBED 0
+#define ZC_EVALCACHE_STAT_HITS 1
+#define ZC_EVALCACHE_STAT_INSERTS 2
+#define ZC_EVALCACHE_STAT_DROPPED 3
+int zc_evalcache_bytes(int64_t entries, int32_t key_bytes, int32_t logit_bytes, int64_t *bytes, int64_t *sets);
+int zc_evalcache_clear_async(void *d_table, int64_t entries, int32_t key_bytes, int32_t logit_bytes, void *hip_stream);
+int zc_evalcache_probe_async(void *d_table, int64_t entries, int32_t key_bytes, int32_t logit_bytes, int32_t n_rows,
+                             int32_t rows_per_game, int32_t game_rows, const void *d_keys, const void *d_planes,
+                             int64_t plane_bytes, double *d_out_values, void *d_out_logits, void *d_dense_planes,
+                             int32_t *d_miss_rows, int32_t *d_count, int64_t *d_stats, void *hip_stream);
+int zc_evalcache_commit_async(void *d_table, int64_t entries, int32_t key_bytes, int32_t logit_bytes, int32_t n_rows,
+                              int32_t rows_per_game, int32_t game_rows, const void *d_keys, const int32_t *d_miss_rows,
+                              int32_t *d_count, const double *d_dense_values, const void *d_dense_logits,
+                              double *d_out_values, void *d_out_logits, int64_t *d_stats, void *hip_stream);
 
 /* ---- any game backend: SURVEY §8(b)'s fallback (gen_search.hip) ----------------------
  * mcts.get_move (mcts.cpp:102-160) for a backend the device knows nothing about: the caller

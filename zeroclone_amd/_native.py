@@ -293,6 +293,16 @@ SIGNATURES = [
                                                     ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
                                                     ctypes.c_void_p]),
+    ("zc_net_tower_counted_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                  ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_net_tower_policy_counted_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("zc_net_planes_to_nhwc_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("zc_net_value_head_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
@@ -319,6 +329,19 @@ SIGNATURES = [
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("zc_arena_scatter_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_evalcache_bytes", ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, P(ctypes.c_int64),
+                                          P(ctypes.c_int64)]),
+    ("zc_evalcache_clear_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_void_p]),
+    ("zc_evalcache_probe_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p]),
+    ("zc_evalcache_commit_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("zc_chess_from_fen", ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
     ("zc_chess_init", ctypes.c_int, [ctypes.c_void_p]),
     ("zc_c4_from_rows", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, P(C4State)]),
@@ -494,6 +517,79 @@ def arena_scatter(n: int, rows: int, game_rows: int, row_bytes: int, d_perm: int
     """zc_arena_scatter_async: the inverse of arena_gather (row i * rows + j of d_src -> row
     d_perm[i] * game_rows + j of d_dst; a game's rows j >= rows are left untouched)."""
     _arena_copy("zc_arena_scatter_async", n, rows, game_rows, row_bytes, d_perm, d_src, d_dst, stream)
+
+
+EVALCACHE_WAYS = 8                                     # ZC_EVALCACHE_WAYS
+EVALCACHE_STATS = ("probed", "hits", "inserts", "dropped")   # ZC_EVALCACHE_STAT_*: the four int64 counters
+
+
+def evalcache_check_sizes(entries: int, key_bytes: int, logit_bytes: int):
+    """What zc_evalcache_bytes checks, with the reason (the library records no message)."""
+    if not 1 <= int(entries) <= 1 << 30:
+        raise ValueError(f"entries must be in [1, 2^30] (got {entries})")
+    if key_bytes < 8 or key_bytes % 8 or key_bytes > 512:
+        raise ValueError(f"key_bytes must be a multiple of 8 in [8, 512] (got {key_bytes})")
+    if logit_bytes < 0 or logit_bytes % 2 or logit_bytes > 1 << 20:
+        raise ValueError(f"logit_bytes must be even, in [0, 2^20] (got {logit_bytes})")
+
+
+def evalcache_bytes(entries: int, key_bytes: int, logit_bytes: int) -> tuple[int, int]:
+    """zc_evalcache_bytes: (the table's size in bytes, its number of sets)."""
+    evalcache_check_sizes(entries, key_bytes, logit_bytes)
+    b, s = ctypes.c_int64(0), ctypes.c_int64(0)
+    _arena_rc("zc_evalcache_bytes", lib().zc_evalcache_bytes(int(entries), int(key_bytes), int(logit_bytes),
+                                                             ctypes.byref(b), ctypes.byref(s)))
+    return b.value, s.value
+
+
+def evalcache_clear(d_table: int, entries: int, key_bytes: int, logit_bytes: int, stream: int = 0):
+    """zc_evalcache_clear_async: empties the table.  Only enqueues."""
+    _arena_rc("zc_evalcache_clear_async", lib().zc_evalcache_clear_async(
+        ctypes.c_void_p(d_table), int(entries), int(key_bytes), int(logit_bytes), ctypes.c_void_p(stream or None)))
+
+
+def _evalcache_rows(name: str, n_rows: int, rows_per_game: int, game_rows: int):
+    if n_rows < 0 or not 1 <= rows_per_game <= game_rows or n_rows % rows_per_game:
+        raise ValueError(f"{name}: need 1 <= rows_per_game <= game_rows and n_rows a multiple of rows_per_game "
+                         f"(got n_rows {n_rows}, rows_per_game {rows_per_game}, game_rows {game_rows})")
+    if n_rows // rows_per_game * game_rows >= 1 << 31:
+        raise ValueError(f"{name}: the buffers' rows must number below 2^31")
+
+
+def evalcache_probe(d_table: int, entries: int, key_bytes: int, logit_bytes: int, n_rows: int, rows_per_game: int,
+                    game_rows: int, d_keys: int, d_planes: int, plane_bytes: int, d_out_values: int, d_out_logits: int,
+                    d_dense_planes: int, d_miss_rows: int, d_count: int, d_stats: int = 0, stream: int = 0):
+    """zc_evalcache_probe_async (include/zeroclone.h) on device pointers.  Only enqueues."""
+    name = "zc_evalcache_probe_async"
+    _evalcache_rows(name, n_rows, rows_per_game, game_rows)
+    if plane_bytes < 2 or plane_bytes % 2:
+        raise ValueError(f"{name}: plane_bytes must be a positive multiple of 2 (got {plane_bytes})")
+    if not d_count or (n_rows and not (d_keys and d_planes and d_out_values and d_dense_planes and d_miss_rows
+                                       and (d_out_logits or not logit_bytes))):
+        raise ValueError(f"{name}: null device pointer")
+    _arena_rc(name, lib().zc_evalcache_probe_async(
+        ctypes.c_void_p(d_table), int(entries), int(key_bytes), int(logit_bytes), int(n_rows), int(rows_per_game),
+        int(game_rows), ctypes.c_void_p(d_keys), ctypes.c_void_p(d_planes), int(plane_bytes),
+        ctypes.c_void_p(d_out_values), ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_dense_planes),
+        ctypes.c_void_p(d_miss_rows), ctypes.c_void_p(d_count), ctypes.c_void_p(d_stats or None),
+        ctypes.c_void_p(stream or None)))
+
+
+def evalcache_commit(d_table: int, entries: int, key_bytes: int, logit_bytes: int, n_rows: int, rows_per_game: int,
+                     game_rows: int, d_keys: int, d_miss_rows: int, d_count: int, d_dense_values: int,
+                     d_dense_logits: int, d_out_values: int, d_out_logits: int, d_stats: int = 0, stream: int = 0):
+    """zc_evalcache_commit_async (include/zeroclone.h) on device pointers; leaves *d_count = 0.
+    Only enqueues."""
+    name = "zc_evalcache_commit_async"
+    _evalcache_rows(name, n_rows, rows_per_game, game_rows)
+    if not d_count or (n_rows and not (d_keys and d_miss_rows and d_dense_values and d_out_values
+                                       and ((d_dense_logits and d_out_logits) or not logit_bytes))):
+        raise ValueError(f"{name}: null device pointer")
+    _arena_rc(name, lib().zc_evalcache_commit_async(
+        ctypes.c_void_p(d_table), int(entries), int(key_bytes), int(logit_bytes), int(n_rows), int(rows_per_game),
+        int(game_rows), ctypes.c_void_p(d_keys), ctypes.c_void_p(d_miss_rows), ctypes.c_void_p(d_count),
+        ctypes.c_void_p(d_dense_values), ctypes.c_void_p(d_dense_logits or None), ctypes.c_void_p(d_out_values),
+        ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_stats or None), ctypes.c_void_p(stream or None)))
 
 
 def _train_rc(name: str, rc: int):

@@ -97,6 +97,9 @@ class _ArenaPool:
                              "network's values (reuse_tree)")
         if kw.get("record_policy"):
             raise ValueError("an arena records no policy targets (record_policy)")
+        if kw.get("eval_cache"):
+            raise ValueError("an arena routes the planes alone, without the leaf rows an evaluation cache keys on "
+                             "(eval_cache)")
         if kw.get("streams", 1) > 1 or kw.get("puct_streams", 1) > 1:
             raise ValueError("an arena searches on one stream (streams / puct_streams > 1): the two groups are not "
                              "contiguous game ranges")

@@ -1,0 +1,328 @@
+// evalcache.hip — a device-resident cache of network evaluations (include/zeroclone.h,
+// "evaluation cache"): a set-associative table keyed by the compact leaf row, and the two
+// kernels that carry a flush through it (probe -> counted network on the misses -> commit).
+//
+// The table, ZC_EVALCACHE_WAYS ways per set and a power-of-two number of sets, in one block:
+//
+//   [header 64 B: epoch u32][meta u32 x E][keys key_bytes x E][values f64 x E][logits lstride x E]
+//
+// E = ways * sets entries, lstride = logit_bytes rounded up to 16, every array 16-byte aligned.
+// An entry's meta word is 0 while it is empty, else (tag << 16) | epoch: a 16-bit tag of the
+// key's hash (never 0) that only pre-filters a lookup — a hit is full-key equality — and the
+// low 16 bits of the commit launch that wrote it.  The epoch is what keeps two waves of one
+// commit launch off one entry: an entry is claimed with one atomicCAS on its meta word, and a
+// word that carries the running launch's epoch is not claimable again until the next launch.
+//
+// One table belongs to one stream: probe and commit are ordered by the stream, so a probe never
+// runs beside a commit and there is no reader / writer protocol.  Within a commit launch no
+// wave reads a key or a payload; the meta words are read and claimed with device-scope atomics.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/zeroclone.h"
+
+namespace {
+
+constexpr int WAYS = ZC_EVALCACHE_WAYS;
+static_assert(WAYS == 8, "a set's ways are looked up by lanes 0..7 and picked by three hash bits");
+constexpr int HEADER_BYTES = 64;
+constexpr int BLOCK = 512, WAVES = BLOCK / 64;   // one wave per row
+constexpr int MAX_KEY_WORDS = 64;                // a lane per key word
+
+struct Table {
+    uint32_t *epoch;
+    uint32_t *meta;
+    uint64_t *keys;
+    double *values;
+    uint8_t *logits;
+    uint32_t set_mask;
+    int kw;               // key words (8 bytes each)
+    int64_t logit_bytes, lstride;
+};
+
+// false: the sizes are outside what the table covers
+bool layout(int64_t entries, int32_t key_bytes, int32_t logit_bytes, int64_t *sets_out, int64_t *bytes_out) {
+    if (entries < 1 || entries > ((int64_t)1 << 30)) return false;
+    if (key_bytes < 8 || (key_bytes & 7) || key_bytes > 8 * MAX_KEY_WORDS) return false;
+    if (logit_bytes < 0 || (logit_bytes & 1) || logit_bytes > (1 << 20)) return false;
+    int64_t sets = 1;
+    while (sets * 2 * WAYS <= entries) sets *= 2;
+    const int64_t E = sets * WAYS, lstride = ((int64_t)logit_bytes + 15) & ~(int64_t)15;
+    if (sets_out) *sets_out = sets;
+    if (bytes_out) *bytes_out = HEADER_BYTES + E * (4 + (int64_t)key_bytes + 8 + lstride);
+    return true;
+}
+
+bool make_table(void *d_table, int64_t entries, int32_t key_bytes, int32_t logit_bytes, Table *t) {
+    int64_t sets;
+    if (!d_table || ((uintptr_t)d_table & 15) || !layout(entries, key_bytes, logit_bytes, &sets, nullptr)) return false;
+    const int64_t E = sets * WAYS;
+    uint8_t *p = (uint8_t *)d_table;
+    t->epoch = (uint32_t *)p;
+    t->meta = (uint32_t *)(p + HEADER_BYTES);
+    t->keys = (uint64_t *)(p + HEADER_BYTES + E * 4);
+    t->values = (double *)((uint8_t *)t->keys + E * key_bytes);
+    t->logits = (uint8_t *)(t->values + E);
+    t->set_mask = (uint32_t)(sets - 1);
+    t->kw = key_bytes / 8;
+    t->logit_bytes = logit_bytes;
+    t->lstride = ((int64_t)logit_bytes + 15) & ~(int64_t)15;
+    return true;
+}
+
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+    x ^= x >> 33;
+    x *= 0xff51afd7ed558ccdULL;
+    x ^= x >> 33;
+    x *= 0xc4ceb9fe1a85ec53ULL;
+    x ^= x >> 33;
+    return x;
+}
+
+// The hash of a key whose word `lane` this lane holds (lanes at or past kw hold nothing): every
+// word mixed with its position, xor-ed across the wave, mixed again.  The same in every lane.
+__device__ __forceinline__ uint64_t key_hash(uint64_t word, int lane, int kw) {
+    uint64_t h = lane < kw ? mix64(word + 0x9E3779B97F4A7C15ULL * (uint64_t)(lane + 1)) : 0;
+    uint32_t lo = (uint32_t)h, hi = (uint32_t)(h >> 32);
+    for (int d = 32; d; d >>= 1) {
+        lo ^= (uint32_t)__shfl_xor((int)lo, d, 64);
+        hi ^= (uint32_t)__shfl_xor((int)hi, d, 64);
+    }
+    return mix64(((uint64_t)hi << 32) | lo);
+}
+
+__device__ __forceinline__ uint32_t hash_tag(uint64_t h) {
+    const uint32_t t = (uint32_t)(h >> 48);
+    return t ? t : 1u;
+}
+
+// `bytes` from src to dst by the lanes of one wave, at the widest access (16, 8, 4 or 2 bytes)
+// that the size and both pointers allow; the choice is the same in every lane.
+__device__ __forceinline__ void wave_copy(void *dst, const void *src, int64_t bytes, int lane) {
+    const uintptr_t bits = (uintptr_t)dst | (uintptr_t)src | (uintptr_t)bytes;
+    if (!(bits & 15)) {
+        for (int64_t i = lane; i < bytes / 16; i += 64) ((uint4 *)dst)[i] = ((const uint4 *)src)[i];
+    } else if (!(bits & 7)) {
+        for (int64_t i = lane; i < bytes / 8; i += 64) ((uint2 *)dst)[i] = ((const uint2 *)src)[i];
+    } else if (!(bits & 3)) {
+        for (int64_t i = lane; i < bytes / 4; i += 64) ((uint32_t *)dst)[i] = ((const uint32_t *)src)[i];
+    } else {
+        for (int64_t i = lane; i < bytes / 2; i += 64) ((uint16_t *)dst)[i] = ((const uint16_t *)src)[i];
+    }
+}
+
+__device__ __forceinline__ void count_add(int64_t *p, int v) {
+    if (v) atomicAdd((unsigned long long *)p, (unsigned long long)v);
+}
+
+// One wave per taking-part row r < n_rows (row (r / rows_per_game) * game_rows + r %
+// rows_per_game of the buffers).  Lanes 0..7 read the set's meta words and the tag filters the
+// ways; for a way that passes, lane i compares key word i.  A hit copies the entry's payload to
+// the row's output slots; a miss takes the next dense slot (one atomic on *d_count per
+// workgroup, for all of its missing rows), copies the row's planes there and records the row.
+__global__ __launch_bounds__(BLOCK) void evalcache_probe_kernel(
+    Table t, int n_rows, int rows_per_game, int game_rows, const uint64_t *__restrict__ keys,
+    const uint8_t *__restrict__ planes, int64_t plane_bytes, double *__restrict__ out_values,
+    uint8_t *__restrict__ out_logits, uint8_t *__restrict__ dense_planes, int32_t *__restrict__ miss_rows,
+    int32_t *d_count, int64_t *stats) {
+    __shared__ int s_miss[WAVES];
+    __shared__ int s_base;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * WAVES + wave;
+    const bool live = r < n_rows;
+    int64_t row = 0, entry = -1;
+    if (live) {
+        const int g = r / rows_per_game;
+        row = (int64_t)g * game_rows + (r - g * rows_per_game);
+        const uint64_t word = lane < t.kw ? keys[row * t.kw + lane] : 0;
+        const uint64_t h = key_hash(word, lane, t.kw);
+        const int64_t e0 = (int64_t)((uint32_t)h & t.set_mask) * WAYS;
+        const uint32_t tag = hash_tag(h);
+        const uint32_t meta = lane < WAYS ? t.meta[e0 + lane] : 0u;
+        unsigned long long cand = __ballot(lane < WAYS && (meta >> 16) == tag);   // an empty way's tag is 0
+        while (cand) {
+            const int w = __builtin_ctzll(cand);
+            cand &= cand - 1;
+            const bool eq = lane < t.kw ? t.keys[(e0 + w) * t.kw + lane] == word : true;
+            if (__all(eq)) {
+                entry = e0 + w;
+                break;
+            }
+        }
+    }
+    if (lane == 0) s_miss[wave] = live && entry < 0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int nm = 0;
+        for (int w = 0; w < WAVES; ++w) nm += s_miss[w];
+        const int nlive = min(WAVES, n_rows - (int)blockIdx.x * WAVES);
+        s_base = nm ? atomicAdd(d_count, nm) : 0;
+        if (stats) {
+            count_add(stats + ZC_EVALCACHE_STAT_PROBED, nlive);
+            count_add(stats + ZC_EVALCACHE_STAT_HITS, nlive - nm);
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    if (entry >= 0) {
+        if (lane == 0) out_values[row] = t.values[entry];
+        if (t.logit_bytes)
+            wave_copy(out_logits + row * t.logit_bytes, t.logits + entry * t.lstride, t.logit_bytes, lane);
+    } else {
+        int slot = s_base;
+        for (int w = 0; w < wave; ++w) slot += s_miss[w];
+        if (slot < 0 || slot >= n_rows) return;   // *d_count was not 0 before the flush: no slot is this row's
+        wave_copy(dense_planes + (int64_t)slot * plane_bytes, planes + row * plane_bytes, plane_bytes, lane);
+        if (lane == 0) miss_rows[slot] = (int32_t)row;
+    }
+}
+
+// One wave per dense slot below min(*d_count, cap): the slot's payload goes to its row's output
+// slots and into the table — the set's first empty way, else the way three hash bits pick —
+// unless a way already carries the key's tag (the same key being inserted by another wave of
+// this launch, or a tag collision: the insert is dropped either way).  The way is claimed with
+// one atomicCAS on its meta word; a wave that loses the claim of an empty way looks at the set
+// again, one that loses a victim (or finds it claimed in this launch) drops its insert.
+__global__ __launch_bounds__(BLOCK) void evalcache_commit_kernel(
+    Table t, int cap, int64_t total_rows, const uint64_t *__restrict__ keys, const int32_t *__restrict__ miss_rows,
+    const int32_t *__restrict__ d_count, const double *__restrict__ dense_values,
+    const uint8_t *__restrict__ dense_logits, double *__restrict__ out_values, uint8_t *__restrict__ out_logits,
+    int64_t *stats) {
+    __shared__ int s_ins[WAVES], s_drop[WAVES];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int slot = blockIdx.x * WAVES + wave;
+    const int count = min(max(*d_count, 0), cap);
+    int ins = 0, drop = 0;
+    const int64_t row = slot < count ? miss_rows[slot] : -1;
+    if (row >= 0 && row < total_rows) {
+        const double v = dense_values[slot];
+        const uint8_t *lg = dense_logits + (int64_t)slot * t.logit_bytes;
+        if (lane == 0) out_values[row] = v;
+        if (t.logit_bytes) wave_copy(out_logits + row * t.logit_bytes, lg, t.logit_bytes, lane);
+        const uint64_t word = lane < t.kw ? keys[row * t.kw + lane] : 0;
+        const uint64_t h = key_hash(word, lane, t.kw);
+        const int64_t e0 = (int64_t)((uint32_t)h & t.set_mask) * WAYS;
+        const uint32_t tag = hash_tag(h), epoch = *t.epoch & 0xFFFFu, mine = (tag << 16) | epoch;
+        int64_t entry = -1;
+        for (int attempt = 0; attempt < WAYS; ++attempt) {
+            const uint32_t meta = lane < WAYS ? __hip_atomic_load(t.meta + e0 + lane, __ATOMIC_RELAXED,
+                                                                  __HIP_MEMORY_SCOPE_AGENT)
+                                              : 0u;
+            if (__ballot(lane < WAYS && (meta >> 16) == tag)) break;
+            const unsigned long long empty = __ballot(lane < WAYS && meta == 0u);
+            const int w = empty ? __builtin_ctzll(empty) : (int)((h >> 32) & (WAYS - 1));
+            const uint32_t old = (uint32_t)__shfl((int)meta, w, 64);
+            if (old && (old & 0xFFFFu) == epoch) break;   // claimed in this launch
+            int won = 0;
+            if (lane == 0) won = atomicCAS(t.meta + e0 + w, old, mine) == old;
+            if (__shfl(won, 0, 64)) {
+                entry = e0 + w;
+                break;
+            }
+            if (!empty) break;
+        }
+        if (entry >= 0) {
+            if (lane < t.kw) t.keys[entry * t.kw + lane] = word;
+            if (lane == 0) t.values[entry] = v;
+            if (t.logit_bytes) wave_copy(t.logits + entry * t.lstride, lg, t.logit_bytes, lane);
+            ins = 1;
+        } else {
+            drop = 1;
+        }
+    }
+    if (!stats) return;
+    if (lane == 0) {
+        s_ins[wave] = ins;
+        s_drop[wave] = drop;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int ni = 0, nd = 0;
+        for (int w = 0; w < WAVES; ++w) {
+            ni += s_ins[w];
+            nd += s_drop[w];
+        }
+        count_add(stats + ZC_EVALCACHE_STAT_INSERTS, ni);
+        count_add(stats + ZC_EVALCACHE_STAT_DROPPED, nd);
+    }
+}
+
+// After a commit launch: the next flush counts its misses from 0, and the next commit launch
+// claims under another epoch.
+__global__ void evalcache_finish_kernel(uint32_t *epoch, int32_t *d_count) {
+    *d_count = 0;
+    *epoch += 1;
+}
+
+int done() { return hipGetLastError() == hipSuccess ? ZC_OK : ZC_EHIP; }
+
+}  // namespace
+
+extern "C" {
+
+int zc_evalcache_bytes(int64_t entries, int32_t key_bytes, int32_t logit_bytes, int64_t *bytes, int64_t *sets) {
+    return layout(entries, key_bytes, logit_bytes, sets, bytes) ? ZC_OK : ZC_EINVAL;
+}
+
+int zc_evalcache_clear_async(void *d_table, int64_t entries, int32_t key_bytes, int32_t logit_bytes,
+                             void *hip_stream) {
+    Table t;
+    if (!make_table(d_table, entries, key_bytes, logit_bytes, &t)) return ZC_EINVAL;
+    const size_t n = HEADER_BYTES + ((size_t)t.set_mask + 1) * WAYS * sizeof(uint32_t);
+    return hipMemsetAsync(d_table, 0, n, (hipStream_t)hip_stream) == hipSuccess ? ZC_OK : ZC_EHIP;
+}
+
+int zc_evalcache_probe_async(void *d_table, int64_t entries, int32_t key_bytes, int32_t logit_bytes, int32_t n_rows,
+                             int32_t rows_per_game, int32_t game_rows, const void *d_keys, const void *d_planes,
+                             int64_t plane_bytes, double *d_out_values, void *d_out_logits, void *d_dense_planes,
+                             int32_t *d_miss_rows, int32_t *d_count, int64_t *d_stats, void *hip_stream) {
+    Table t;
+    if (!make_table(d_table, entries, key_bytes, logit_bytes, &t)) return ZC_EINVAL;
+    if (n_rows < 0 || rows_per_game < 1 || game_rows < rows_per_game || n_rows % rows_per_game) return ZC_EINVAL;
+    if ((int64_t)(n_rows / rows_per_game) * game_rows >= ((int64_t)1 << 31)) return ZC_EINVAL;
+    if (plane_bytes < 2 || (plane_bytes & 1) || !d_count || ((uintptr_t)d_count & 3) || ((uintptr_t)d_stats & 7))
+        return ZC_EINVAL;
+    if (!n_rows) return ZC_OK;
+    if (!d_keys || !d_planes || !d_out_values || !d_dense_planes || !d_miss_rows || (logit_bytes && !d_out_logits))
+        return ZC_EINVAL;
+    if (((uintptr_t)d_keys & 7) || ((uintptr_t)d_out_values & 7) || ((uintptr_t)d_miss_rows & 3) ||
+        (((uintptr_t)d_planes | (uintptr_t)d_dense_planes | (uintptr_t)d_out_logits) & 1))
+        return ZC_EINVAL;
+    (void)hipGetLastError();   // an earlier call's error is not this launch's
+    hipLaunchKernelGGL(evalcache_probe_kernel, dim3((n_rows + WAVES - 1) / WAVES), dim3(BLOCK), 0,
+                       (hipStream_t)hip_stream, t, (int)n_rows, (int)rows_per_game, (int)game_rows,
+                       (const uint64_t *)d_keys, (const uint8_t *)d_planes, plane_bytes, d_out_values,
+                       (uint8_t *)d_out_logits, (uint8_t *)d_dense_planes, d_miss_rows, d_count, d_stats);
+    return done();
+}
+
+int zc_evalcache_commit_async(void *d_table, int64_t entries, int32_t key_bytes, int32_t logit_bytes, int32_t n_rows,
+                              int32_t rows_per_game, int32_t game_rows, const void *d_keys, const int32_t *d_miss_rows, int32_t *d_count,
+                              const double *d_dense_values, const void *d_dense_logits, double *d_out_values,
+                              void *d_out_logits, int64_t *d_stats, void *hip_stream) {
+    Table t;
+    if (!make_table(d_table, entries, key_bytes, logit_bytes, &t)) return ZC_EINVAL;
+    if (n_rows < 0 || !d_count || ((uintptr_t)d_count & 3) || ((uintptr_t)d_stats & 7)) return ZC_EINVAL;
+    if (rows_per_game < 1 || game_rows < rows_per_game || n_rows % rows_per_game) return ZC_EINVAL;
+    const int64_t total_rows = (int64_t)(n_rows / rows_per_game) * game_rows;
+    if (total_rows >= ((int64_t)1 << 31)) return ZC_EINVAL;
+    if (n_rows) {
+        if (!d_keys || !d_miss_rows || !d_dense_values || !d_out_values ||
+            (logit_bytes && (!d_dense_logits || !d_out_logits)))
+            return ZC_EINVAL;
+        if (((uintptr_t)d_keys & 7) || ((uintptr_t)d_out_values & 7) || ((uintptr_t)d_dense_values & 7) ||
+            ((uintptr_t)d_miss_rows & 3) || (((uintptr_t)d_dense_logits | (uintptr_t)d_out_logits) & 1))
+            return ZC_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)hip_stream;
+    (void)hipGetLastError();   // an earlier call's error is not this launch's
+    if (n_rows)
+        hipLaunchKernelGGL(evalcache_commit_kernel, dim3((n_rows + WAVES - 1) / WAVES), dim3(BLOCK), 0, s, t,
+                           (int)n_rows, total_rows, (const uint64_t *)d_keys, d_miss_rows, (const int32_t *)d_count, d_dense_values,
+                           (const uint8_t *)d_dense_logits, d_out_values, (uint8_t *)d_out_logits, d_stats);
+    hipLaunchKernelGGL(evalcache_finish_kernel, dim3(1), dim3(1), 0, s, t.epoch, d_count);
+    return done();
+}
+
+}  // extern "C"

@@ -1086,11 +1086,17 @@ struct TowerPolicy {
     int relu;            // ReLU on the outputs (the linear-head network's conv) or not (logits)
 };
 
-template <int H, int W, int BPH, int CIN0, int NT, int WPE, int PG = 1, int MF = 32, int EPI = 0>
+// CNT: the counted form's flag (zc_net_tower_counted_async).  Empty, the kernel is the plain
+// tower with the plain tower's arguments.  `const int32_t *`, a trailing argument points at the
+// row count on the device: nboards is then the capacity the grid was sized for, and a workgroup
+// whose first board is at or past min(*count, nboards) returns before it touches LDS; the others
+// run on the clamped count, so rows at or past it are neither read nor written.
+template <int H, int W, int BPH, int CIN0, int NT, int WPE, int PG = 1, int MF = 32, int EPI = 0, typename... CNT>
 __global__ __launch_bounds__(256 * PG) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void tower_kernel(
     int nboards, int nconv, const _Float16 *__restrict__ in, const _Float16 *__restrict__ wall,
     const float *__restrict__ ball, _Float16 *__restrict__ out, const float *__restrict__ fcw, float fcb,
-    double *__restrict__ values, TowerPolicy pol) {
+    double *__restrict__ values, TowerPolicy pol, CNT... cnt) {
+    static_assert(sizeof...(CNT) <= 1, "at most one count argument");
     constexpr int HW = H * W;
     static_assert(BPH * HW <= 32 * NT * PG, "tile too large");
     static_assert(MF == 32 || (MF == 16 && PG == 1), "the 16x16x32 form has one pixel group");
@@ -1106,6 +1112,11 @@ __global__ __launch_bounds__(256 * PG) __attribute__((amdgpu_waves_per_eu(WPE, W
     const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) & 3, pg = tid >> 8;
     const int pbase = pg * 32 * NT;   // this wave's first pixel of the tile
     const int b0 = blockIdx.x * BPH;
+    if constexpr (sizeof...(CNT) == 1) {
+        const int32_t *const count = (cnt, ...);
+        nboards = min(max(*count, 0), nboards);
+        if (b0 >= nboards) return;
+    }
     const int npix = min(BPH, nboards - b0) * HW;
     const h8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
     const int r = lane & 31, hh = lane >> 5;
@@ -1342,7 +1353,13 @@ int tower_epi() {  // 1 = the 16x16x32 form's epilogue with 16-byte stores,
 
 template <int H, int W, int BPH, int NT, int WPE, int PG = 1, int MF = 32>
 void launch_tower(int n, int nconv, const void *in, const void *wall, const float *ball, void *out, const float *fcw,
-                  float fcb, double *values, TowerPolicy pol, hipStream_t s) {
+                  float fcb, double *values, TowerPolicy pol, const int32_t *count, hipStream_t s) {
+    if (count) {  // the counted form: the default epilogue only (the A/B epilogues are the plain launch's)
+        hipLaunchKernelGGL((tower_kernel<H, W, BPH, 32, NT, WPE, PG, MF, 0, const int32_t *>), dim3((n + BPH - 1) / BPH),
+                           dim3(256 * PG), (tower_lds<NT, PG, MF>()), s, n, nconv, (const _Float16 *)in,
+                           (const _Float16 *)wall, ball, (_Float16 *)out, fcw, fcb, values, pol, count);
+        return;
+    }
     if constexpr (MF == 16) {
         if (tower_epi() == 1) {
             hipLaunchKernelGGL((tower_kernel<H, W, BPH, 32, NT, WPE, PG, MF, 1>), dim3((n + BPH - 1) / BPH),
@@ -1525,7 +1542,7 @@ bool launch_net_conv3x3_packed(int n, int h, int w, int cin, const void *in, con
 
 bool launch_net_tower(int n, int h, int w, int cin0, int nconv, const void *in, const void *wall, const float *ball,
                       void *out, const float *fcw, float fcb, double *values, const void *pw, const float *pb,
-                      void *pout, hipStream_t s, int pol_channels, int pol_relu) {
+                      void *pout, hipStream_t s, int pol_channels, int pol_relu, const int32_t *count) {
     if (cin0 != 32 || nconv < 1 || !(nconv & 1)) return false;
     if (pout && pol_channels != 32 && pol_channels != 64) return false;
     const TowerPolicy pol{(const _Float16 *)pw, pb, (_Float16 *)pout, head_raw(), pol_channels / 32, pol_relu ? 1 : 0};
@@ -1535,15 +1552,15 @@ bool launch_net_tower(int n, int h, int w, int cin0, int nconv, const void *in, 
 #define ZC_TOWER_PG 1
 #endif
 #if ZC_TOWER_PG == 2
-    if (h == 8 && w == 8) launch_tower<8, 8, 4, 4, 2, 2>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, s);
-    else if (h == 6 && w == 7) launch_tower<6, 7, 6, 4, 2, 2>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, s);
+    if (h == 8 && w == 8) launch_tower<8, 8, 4, 4, 2, 2>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
+    else if (h == 6 && w == 7) launch_tower<6, 7, 6, 4, 2, 2>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
 #else
     if (tower_mf() == 16) {
-        if (h == 8 && w == 8) launch_tower<8, 8, 2, 4, 2, 1, 16>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, s);
-        else if (h == 6 && w == 7) launch_tower<6, 7, 3, 4, 2, 1, 16>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, s);
+        if (h == 8 && w == 8) launch_tower<8, 8, 2, 4, 2, 1, 16>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
+        else if (h == 6 && w == 7) launch_tower<6, 7, 3, 4, 2, 1, 16>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
         else return false;
-    } else if (h == 8 && w == 8) launch_tower<8, 8, 2, 4, 2>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, s);
-    else if (h == 6 && w == 7) launch_tower<6, 7, 3, 4, 2>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, s);
+    } else if (h == 8 && w == 8) launch_tower<8, 8, 2, 4, 2>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
+    else if (h == 6 && w == 7) launch_tower<6, 7, 3, 4, 2>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
 #endif
     else return false;
     return true;

@@ -1,0 +1,180 @@
+"""An evaluation cache for the network searches (include/zeroclone.h "evaluation cache",
+csrc/evalcache.hip): a flush's rows whose position was evaluated before take the stored value
+and logits, and the network runs on the others alone.
+
+    probe -> network on the dense rows of the misses (a counted launch) -> commit
+
+The key is the whole compact leaf row (zc_c4_state, zc_chess_state), and the planes are a
+function of that row; the MFMA towers compute every board independently of its neighbours, so
+a stored output is the computed one bit for bit and a search with the cache returns what the
+search without it returns.  The miss count lives on the device and the network call takes it
+there (nets.MfmaValueNetwork.tower's `count`), so the path has no host read and a whole move
+can be captured in a HIP graph as before.
+
+`CachedValue(net, cache)` stands where `valued.NetValue(net)` stands and `CachedPolicy(net,
+cache)` where `valued.PolicyNet(net)` does.  Both need the leaf rows: allocate the search with
+leaves=True.  One EvalCache belongs to one stream and to one set of weights: give every
+stream's replica of the network a cache of its own, and `clear()` it when the weights change.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _native
+from .nets import MfmaPolicyValueNetwork, MfmaValueNetwork
+
+
+def _stream(dev) -> int:
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+class EvalCache:
+    """The table (zc_evalcache_*), its miss counter, its four counters and the dense buffers of
+    the misses (allocated per flush shape at first use).  entries: the table holds the largest
+    power-of-two number of 8-way sets within it.  key_bytes: the leaf row's size (24: zc_c4_state,
+    72: zc_chess_state).  logit_bytes: the logits of one row (0: a value network)."""
+
+    def __init__(self, entries: int, key_bytes: int, logit_bytes: int = 0, device="cuda"):
+        _native.evalcache_check_sizes(entries, key_bytes, logit_bytes)
+        self.entries, self.key_bytes, self.logit_bytes = int(entries), int(key_bytes), int(logit_bytes)
+        self.dev = torch.device(device)
+        if self.dev.type != "cuda":
+            raise ValueError("the evaluation cache lives on a GPU")
+        self.table = None    # allocated at first use
+        self._bufs = {}
+
+    def _sizes(self):
+        return self.entries, self.key_bytes, self.logit_bytes
+
+    def _ensure(self):
+        if self.table is None:
+            if torch.cuda.is_current_stream_capturing():   # the zero fill would be replayed with the graph
+                raise RuntimeError("the evaluation cache must exist before a graph capture: call clear() first")
+            nbytes, self.sets = _native.evalcache_bytes(*self._sizes())
+            self.table = torch.zeros(nbytes, dtype=torch.uint8, device=self.dev)   # all zeros: empty
+            self.count = torch.zeros(1, dtype=torch.int32, device=self.dev)
+            self.counters = torch.zeros(len(_native.EVALCACHE_STATS), dtype=torch.int64, device=self.dev)
+
+    def clear(self):
+        """Empty the table (stream-ordered; the counters keep counting)."""
+        self._ensure()
+        _native.evalcache_clear(self.table.data_ptr(), *self._sizes(), _stream(self.dev))
+
+    def stats(self) -> dict:
+        """{"probed", "hits", "inserts", "dropped"} so far.  Synchronises."""
+        self._ensure()
+        return dict(zip(_native.EVALCACHE_STATS, (int(x) for x in self.counters.cpu())))
+
+    def _buf(self, name: str, shape: tuple, dtype) -> torch.Tensor:
+        key = (name, tuple(shape), dtype)
+        b = self._bufs.get(key)
+        if b is None:
+            b = self._bufs[key] = torch.zeros(key[1], dtype=dtype, device=self.dev)
+        return b
+
+    def _keys(self, leaves, planes, game_rows: int):
+        if leaves is None:
+            raise ValueError("the evaluation cache keys on the leaf rows: allocate the search with leaves=True")
+        if not leaves.is_contiguous() or not planes.is_contiguous():
+            raise ValueError("leaves and planes must be contiguous")
+        if leaves[0].numel() * leaves.element_size() != self.key_bytes:
+            raise ValueError(f"a leaf row has {leaves[0].numel() * leaves.element_size()} bytes, the cache's keys "
+                             f"{self.key_bytes}")
+        if leaves.shape[0] != planes.shape[0] or leaves.shape[0] % game_rows:
+            raise ValueError("leaves and planes must hold the same whole number of games' rows")
+
+    def probe(self, leaves, planes, rows: int, game_rows: int, out_values, out_logits=None):
+        """The first `rows` of each game's game_rows rows through the table: the hits' payloads
+        land in out_values / out_logits; returns (the misses' planes packed from row 0 of a
+        buffer of n_games * rows rows, self.count = their number on the device)."""
+        self._keys(leaves, planes, game_rows)
+        self._ensure()
+        n_rows = leaves.shape[0] // game_rows * rows
+        dense = self._buf("planes", (n_rows, *planes.shape[1:]), planes.dtype)
+        miss = self._buf("miss", (n_rows,), torch.int32)
+        _native.evalcache_probe(self.table.data_ptr(), *self._sizes(), n_rows, rows, game_rows, leaves.data_ptr(),
+                                planes.data_ptr(), planes[0].numel() * planes.element_size(), out_values.data_ptr(),
+                                out_logits.data_ptr() if out_logits is not None else 0, dense.data_ptr(),
+                                miss.data_ptr(), self.count.data_ptr(), self.counters.data_ptr(), _stream(self.dev))
+        return dense, self.count
+
+    def commit(self, leaves, rows: int, game_rows: int, dense_values, dense_logits, out_values, out_logits=None):
+        """After the network ran on probe's dense planes: the misses' outputs go to their rows'
+        slots of out_values / out_logits and into the table; self.count is 0 again."""
+        n_rows = leaves.shape[0] // game_rows * rows
+        miss = self._buf("miss", (n_rows,), torch.int32)
+        if dense_values.dtype != torch.float64 or dense_values.numel() < n_rows:
+            raise ValueError(f"the network must return fp64 values for {n_rows} rows")
+        if self.logit_bytes:
+            if dense_logits is None or not dense_logits.is_contiguous() or dense_logits.shape[0] < n_rows or \
+                    dense_logits[0].numel() * dense_logits.element_size() != self.logit_bytes:
+                raise ValueError(f"the network must return contiguous logits of {self.logit_bytes} bytes a row")
+        _native.evalcache_commit(self.table.data_ptr(), *self._sizes(), n_rows, rows, game_rows, leaves.data_ptr(),
+                                 miss.data_ptr(), self.count.data_ptr(), dense_values.data_ptr(),
+                                 dense_logits.data_ptr() if self.logit_bytes else 0, out_values.data_ptr(),
+                                 out_logits.data_ptr() if out_logits is not None else 0, self.counters.data_ptr(),
+                                 _stream(self.dev))
+
+
+class CachedValue:
+    """valued.NetValue behind an EvalCache: a value search's value_fn over an MfmaValueNetwork.
+    The search must be allocated with leaves=True."""
+    wants_leaves = True    # the shared driver then passes the leaf rows to rows() too
+
+    def __init__(self, net, cache: EvalCache):
+        if not isinstance(net, MfmaValueNetwork):
+            raise ValueError("CachedValue needs an MfmaValueNetwork (nets.for_inference(..., backend='mfma')): a "
+                             "torch module cannot take its row count from the device")
+        if cache.logit_bytes:
+            raise ValueError("a value network's cache holds no logits (logit_bytes = 0)")
+        self.model, self.cache = net, cache
+
+    def _flush(self, leaves, planes, rows: int, game_rows: int, out):
+        dense, count = self.cache.probe(leaves, planes, rows, game_rows, out)
+        self.cache.commit(leaves, rows, game_rows, self.model(dense, count=count), None, out)
+        return out
+
+    @torch.no_grad()
+    def __call__(self, leaves, planes, counts):
+        if leaves is None:
+            raise ValueError("CachedValue needs the leaf rows: allocate the search with leaves=True")
+        return self._flush(leaves, planes, 1, 1, self.cache._buf("out", (planes.shape[0],), torch.float64))
+
+    @torch.no_grad()
+    def rows(self, planes, n: int, bs: int, nb: int, out, leaves=None):
+        """NetValue.rows: the short last flush, each game's first nb rows alone."""
+        if leaves is None:
+            raise ValueError("CachedValue needs the leaf rows: allocate the search with leaves=True")
+        return self._flush(leaves, planes, nb, bs, out)
+
+
+class CachedPolicy:
+    """valued.PolicyNet behind an EvalCache: a PUCT search's net_fn over an
+    MfmaPolicyValueNetwork (linear or convolutional head, fused).  The cache's logit_bytes is
+    the network's logits row: 2 * n_logits (fp16).  The search must be allocated with
+    leaves=True; the roots flush gets the roots' rows from the shared driver."""
+    roots_only = True
+    wants_leaves = True
+
+    def __init__(self, net, cache: EvalCache):
+        if not isinstance(net, MfmaPolicyValueNetwork):
+            raise ValueError("CachedPolicy needs an MfmaPolicyValueNetwork: a torch module cannot take its row "
+                             "count from the device")
+        if not (net.conv_head or net.fused):
+            raise ValueError("CachedPolicy needs the fused policy head (32 policy planes on 128 channels)")
+        width = 64 * 64 if net.conv_head else net.w2.shape[1]
+        if cache.logit_bytes != 2 * width:
+            raise ValueError(f"the network's logits are {2 * width} bytes a row, the cache's {cache.logit_bytes}")
+        self.net, self.cache, self.width = net, cache, width
+
+    @torch.no_grad()
+    def __call__(self, leaves, planes, counts):
+        if leaves is None:
+            raise ValueError("CachedPolicy needs the leaf rows: allocate the search with leaves=True")
+        c, L = self.cache, planes.shape[0]
+        vo = c._buf("vout", (L,), torch.float64)
+        lo = c._buf("lout", (L, self.width), torch.float16)
+        dense, count = c.probe(leaves, planes, 1, 1, vo, lo)
+        v, lg = self.net(dense, count=count)
+        c.commit(leaves, 1, 1, v, lg.contiguous(), vo, lo)
+        return vo, lo

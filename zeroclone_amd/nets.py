@@ -176,12 +176,15 @@ class MfmaValueNetwork:
                                torch.empty(n, dtype=torch.float64, device=self.dev))
         return self._bufs[key]
 
-    def tower(self, planes, fused: bool = True, head: bool = False, activation: bool = True):
+    def tower(self, planes, fused: bool = True, head: bool = False, activation: bool = True, count=None):
         """Stem + residual blocks: the final activation, NHWC fp16 [n, h*w, 128].  fused: one
         launch for the whole tower (zc_net_tower_async); otherwise one launch per layer
         (zc_net_conv3x3_packed_async) — bit-identical.  head (fused only): the value head runs
         in the same launch into the returned fp64 values; activation=False skips writing the
-        activation (a value-only network needs none)."""
+        activation (a value-only network needs none).  count (fused only): an int32 tensor on
+        the device holding the number of rows to evaluate (zc_net_tower_counted_async) — n is
+        then the capacity, rows [0, min(count, n)) get the bits of the plain call and the
+        outputs' rows past them are left as they were."""
         import torch
         from . import _native
         L = _native.lib()
@@ -194,11 +197,16 @@ class MfmaValueNetwork:
         s = ctypes_stream(self.dev)
         _native.check(L.zc_net_planes_to_nhwc_async(n, c, hw, self.cpad, planes.data_ptr(), x0.data_ptr(), s))
         if fused:
-            _native.check(L.zc_net_tower_async(n, h, w, self.cpad, len(self.wp), x0.data_ptr(), self.wall.data_ptr(),
-                                               self.ball.data_ptr(), a.data_ptr() if activation or not head else None,
-                                               self.fcw.data_ptr() if head else None, self.fcb,
-                                               vals.data_ptr() if head else None, s))
+            args = (n, h, w, self.cpad, len(self.wp), x0.data_ptr(), self.wall.data_ptr(), self.ball.data_ptr(),
+                    a.data_ptr() if activation or not head else None, self.fcw.data_ptr() if head else None, self.fcb,
+                    vals.data_ptr() if head else None)
+            if count is None:
+                _native.check(L.zc_net_tower_async(*args, s))
+            else:
+                _native.check(L.zc_net_tower_counted_async(*args, _count_ptr(count, self.dev), s))
             return a, vals
+        if count is not None:
+            raise ValueError("count needs the fused tower")
         if head:
             raise ValueError("head=True needs the fused tower")
 
@@ -213,11 +221,11 @@ class MfmaValueNetwork:
             a, b = b, a
         return a, vals
 
-    def tower_policy(self, planes, pw, pb, pout, relu: bool = True):
+    def tower_policy(self, planes, pw, pb, pout, relu: bool = True, count=None):
         """The tower, the value head and a policy 1x1 conv 128 -> P (P = 32 or 64; pw:
         pack_policy_1x1's fragments, pb fp32 [P]) in ONE launch (zc_net_tower_policy_ex_async):
         fp64 values [n]; pout [n, h*w, P] fp16 receives conv1x1 + pb, ReLU'd when `relu`.  No
-        tower activation is written."""
+        tower activation is written.  count: as tower's (zc_net_tower_policy_counted_async)."""
         import torch
         from . import _native
         if planes.dim() == 3:   # already the tower's input layout, [n, h*w, cpad] fp16 (8x8 boards)
@@ -240,23 +248,38 @@ class MfmaValueNetwork:
         else:
             planes = planes.contiguous()
             _native.check(L.zc_net_planes_to_nhwc_async(n, c, h * w, self.cpad, planes.data_ptr(), x0.data_ptr(), s))
-        _native.check(L.zc_net_tower_policy_ex_async(n, h, w, self.cpad, len(self.wp), x0.data_ptr(),
-                                                     self.wall.data_ptr(), self.ball.data_ptr(), self.fcw.data_ptr(),
-                                                     self.fcb, vals.data_ptr(), pw.data_ptr(), pb.data_ptr(), P,
-                                                     1 if relu else 0, pout.data_ptr(), s))
+        args = (n, h, w, self.cpad, len(self.wp), x0.data_ptr(), self.wall.data_ptr(), self.ball.data_ptr(),
+                self.fcw.data_ptr(), self.fcb, vals.data_ptr(), pw.data_ptr(), pb.data_ptr(), P, 1 if relu else 0,
+                pout.data_ptr())
+        if count is None:
+            _native.check(L.zc_net_tower_policy_ex_async(*args, s))
+        else:
+            _native.check(L.zc_net_tower_policy_counted_async(*args, _count_ptr(count, self.dev), s))
         return vals
 
-    def __call__(self, planes, fused: bool = True):
+    def __call__(self, planes, fused: bool = True, count=None):
         """fp64 values [n]: the tower and the value head in one launch (fused), or the layered
-        tower + zc_net_value_head_async — bit-identical."""
+        tower + zc_net_value_head_async — bit-identical.  count: as tower's."""
         from . import _native
         if fused:
-            return self.tower(planes, head=True, activation=False)[1]
+            return self.tower(planes, head=True, activation=False, count=count)[1]
+        if count is not None:
+            raise ValueError("count needs the fused tower")
         a, vals = self.tower(planes, fused=False)
         n, hw = a.shape[0], a.shape[1]
         _native.check(_native.lib().zc_net_value_head_async(n, hw, a.data_ptr(), self.fcw.data_ptr(), self.fcb,
                                                             vals.data_ptr(), ctypes_stream(self.dev)))
         return vals
+
+
+def _count_ptr(count, dev) -> int:
+    """The device address of a counted call's row count."""
+    import torch
+    dev = torch.device(dev)
+    if not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.numel() != 1 or \
+            count.device.type != dev.type or (dev.index is not None and count.device.index != dev.index):
+        raise ValueError("count must be a one-element int32 tensor on the network's device")
+    return count.data_ptr()
 
 
 def ctypes_stream(dev):
@@ -374,8 +397,13 @@ class MfmaPolicyValueNetwork:
         r._pout = {}
         return r
 
-    def __call__(self, planes, fused: bool = True):
+    def __call__(self, planes, fused: bool = True, count=None):
+        """count: a device row count (MfmaValueNetwork.tower): the tower launch evaluates the
+        rows below it alone, and the outputs' rows past it hold nothing.  The linear head's GEMM
+        still runs over all n rows of the conv output."""
         import torch
+        if count is not None and not (self.conv_head or (fused and self.fused)):
+            raise ValueError("count needs the fused tower")
         if planes.dim() == 3:   # NHWC planes in the tower's input layout (ChessPuctSearch(planes_nhwc=True))
             if not self.conv_head:
                 raise ValueError("NHWC planes need the convolutional head")
@@ -387,14 +415,14 @@ class MfmaPolicyValueNetwork:
             if key not in self._pout:
                 self._pout[key] = torch.empty((n, h * w, 64), dtype=torch.float16, device=self.tower.dev)
             p = self._pout[key]
-            vals = self.tower.tower_policy(planes, self.pw, self.pb, p, relu=False)
+            vals = self.tower.tower_policy(planes, self.pw, self.pb, p, relu=False, count=count)
             return vals, p.view(n, h * w * 64)
         if fused and self.fused:
             key = (n, h * w)
             if key not in self._pout:
                 self._pout[key] = torch.empty((n, h * w, 32), dtype=torch.float16, device=self.tower.dev)
             p = self._pout[key]
-            vals = self.tower.tower_policy(planes, self.pw, self.pb, p)
+            vals = self.tower.tower_policy(planes, self.pw, self.pb, p, count=count)
             return vals, torch.addmm(self.b2, p.view(n, -1), self.w2)
         a, vals = self.tower.tower(planes, head=True)  # the activation and the values, one launch
         hw = a.shape[1]

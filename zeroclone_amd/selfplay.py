@@ -399,7 +399,10 @@ def _warm(search, fn, sims: int):
     for i, f in enumerate(fns):
         lo, hi = i * n // k, (i + 1) * n // k
         if nb and hasattr(f, "rows"):
-            f.rows(search.planes[lo * bs:hi * bs], hi - lo, bs, nb, search.values[lo * bs:hi * bs])
+            kw = {}
+            if getattr(f, "wants_leaves", False):
+                kw["leaves"] = search.leaves[lo * bs:hi * bs] if search.leaves is not None else None
+            f.rows(search.planes[lo * bs:hi * bs], hi - lo, bs, nb, search.values[lo * bs:hi * bs], **kw)
 
 
 class _SelfPlayPool:
@@ -424,8 +427,12 @@ class _SelfPlayPool:
     def __init__(self, games: int, sims: int, c: float, batch_size: int, seed: int, rank: int, device,
                  temperature: float, record_policy: bool, init_row: torch.Tensor, max_len: int,
                  games_cap: int | None, pi_slot_cap: int | None, pi_pool_cap: int | None,
-                 record: bool = True, max_sims: int | None = None, fused_policy: bool = False):
+                 record: bool = True, max_sims: int | None = None, fused_policy: bool = False,
+                 eval_cache: int = 0):
         """The refusals come before the engine: they need no GPU."""
+        if int(eval_cache) < 0:
+            raise ValueError(f"eval_cache is a number of entries: 0 (off) or positive (got {eval_cache})")
+        self.eval_cache, self._caches = int(eval_cache), []
         if record_policy and sims > _native.ZC_TRAJ_PI_MAX_COUNT:   # an entry's count field is 16 bits
             raise ValueError(f"record_policy stores visit counts in 16 bits: sims {sims} > "
                              f"{_native.ZC_TRAJ_PI_MAX_COUNT}")
@@ -460,17 +467,50 @@ class _SelfPlayPool:
         """`net=`: the value search and its network; `puct_net=`: the PUCT search and its.  With
         more than one stream, a list of replicas: the games in parts on their own streams
         (valued._split_flushes)."""
+        if self.eval_cache and net is None and puct_net is None:
+            raise ValueError("eval_cache caches a network's evaluations: it needs net= or puct_net=")
         if net is not None:
-            self.vs = value_search(self.eng, self.G, self.bs, leaves=False, **value_kw)
-            self.value_fn = valued.NetValue(net)
-            if streams > 1:
-                self.value_fn = [valued.NetValue(net.replica() if hasattr(net, "replica") else net)
-                                 for _ in range(streams)]
+            self.vs = value_search(self.eng, self.G, self.bs, leaves=bool(self.eval_cache), **value_kw)
+            self.value_fn = self._callables(net, streams, False)
         if puct_net is not None:
-            self.ps = puct_search(self.eng, self.G, self.bs, leaves=False, **puct_kw)
-            self.net_fn = valued.PolicyNet(puct_net)
-            if puct_streams > 1:
-                self.net_fn = [valued.PolicyNet(puct_net.replica()) for _ in range(puct_streams)]
+            self.ps = puct_search(self.eng, self.G, self.bs, leaves=bool(self.eval_cache), **puct_kw)
+            self.net_fn = self._callables(puct_net, puct_streams, True)
+
+    def _callables(self, net, k: int, puct: bool):
+        """The search's callable over `net`: one, or with k > 1 streams a list over k replicas
+        (weights shared, buffers their own).  With eval_cache, evalcache.CachedValue /
+        CachedPolicy, every stream's over a table of its own of eval_cache / k entries — parts
+        on different streams never share a table — and every table empty: a cache belongs to
+        one set of weights."""
+        reps = [net] if k <= 1 else [net.replica() if hasattr(net, "replica") else net for _ in range(k)]
+        if not self.eval_cache:
+            fns = [(valued.PolicyNet if puct else valued.NetValue)(r) for r in reps]
+            return fns[0] if k <= 1 else fns
+        from . import evalcache, nets
+        if not isinstance(net, nets.MfmaPolicyValueNetwork if puct else nets.MfmaValueNetwork):
+            raise ValueError("eval_cache needs the MFMA form of the network (its tower takes the row count from "
+                             "the device): a torch module cannot be cached")
+        logit_bytes = 2 * (64 * 64 if net.conv_head else net.w2.shape[1]) if puct else 0
+        if [c.logit_bytes for c in self._caches] != [logit_bytes] * len(reps):
+            row, dtype = (self.ps if puct else self.vs).LEAF
+            key_bytes = int(np.prod(row)) * torch.empty(0, dtype=dtype).element_size()
+            self._caches = [evalcache.EvalCache(max(self.eval_cache // len(reps), _native.EVALCACHE_WAYS), key_bytes,
+                                                logit_bytes, self.dev) for _ in reps]
+        for c in self._caches:
+            c.clear()
+        fns = [(evalcache.CachedPolicy if puct else evalcache.CachedValue)(r, c) for r, c in zip(reps, self._caches)]
+        return fns[0] if k <= 1 else fns
+
+    def eval_cache_stats(self) -> dict:
+        """The evaluation caches' counters summed over the streams' tables: {"probed", "hits",
+        "inserts", "dropped"} rows since the pool was built.  Synchronises."""
+        if not self._caches:
+            raise ValueError("this pool was built without eval_cache")
+        out = dict.fromkeys(_native.EVALCACHE_STATS, 0)
+        for c in self._caches:
+            for k, v in c.stats().items():
+                out[k] += v
+        return out
 
     def _stream(self, stream: int | None) -> int:
         return stream if stream is not None else torch.cuda.current_stream(self.dev).cuda_stream
@@ -589,7 +629,8 @@ class _SelfPlayPool:
         learner's loop (learner.full_training_run).  `model` is the trainable module — a
         `nets.ValueNetwork` for a pool built with `net=`, a `nets.PolicyValueNetwork` for one
         built with `puct_net=`; its inference form is built here (learner.inference_form) and
-        replaces the pool's value / PUCT callable, every stream's replica included.  Kept PUCT
+        replaces the pool's value / PUCT callable, every stream's replica included, and every
+        evaluation cache (eval_cache) is emptied: a cache belongs to one set of weights.  Kept PUCT
         trees (reuse_tree) hold the old network's priors and values and are dropped.  A step graph
         captured before (`capture_step()`; the caller holds it) has the old network's launches
         baked in: it is not this pool's to drop — capture again.  A pool built without a network
@@ -602,11 +643,8 @@ class _SelfPlayPool:
             raise TypeError("a puct_net= pool takes a PolicyValueNetwork, a net= pool a ValueNetwork")
         net = learner.inference_form(model, self.dev)
         old = self.net_fn if puct else self.value_fn
-        wrap = valued.PolicyNet if puct else valued.NetValue
-        if isinstance(old, (list, tuple)):   # one replica a stream: weights shared, buffers its own
-            new = [wrap(net.replica() if hasattr(net, "replica") else net) for _ in old]
-        else:
-            new = wrap(net)
+        # one replica a stream: weights shared, buffers its own
+        new = self._callables(net, len(old) if isinstance(old, (list, tuple)) else 1, puct)
         if puct:
             self.net_fn = new
             if getattr(self, "reuse_tree", False):
@@ -648,9 +686,14 @@ class C4SelfPlay(_SelfPlayPool):
                  net=None, puct_net=None, temperature: float = 1.0, puct_seed: int = 1, streams: int = 1,
                  record_policy: bool = False, pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
                  reuse_tree: bool = False, tree_nodes: int | None = None, fused_policy: bool = False,
-                 puct_args: dict | None = None):
+                 puct_args: dict | None = None, eval_cache: int = 0):
         """record_policy: every step()'s root visit counts go with the positions into the
         trajectories (TrajBatch.pi / policy_targets(7)), in every search mode.
+        eval_cache (net= / puct_net=, MFMA networks): the entries of a device-resident evaluation
+        cache (zeroclone_amd/evalcache.py), split evenly over the streams; a leaf whose position
+        was evaluated before takes the stored value and logits and the network runs on the
+        others alone.  The moves, visit counts and trajectories are those of the pool without
+        it.  0 = off.
         puct_args: C4PuctSearch's c_puct / dirichlet_alpha / dirichlet_eps, where its defaults
         are not wanted.
         fused_policy (needs record_policy): run(), run_pooled() (carry=True too) and drain()
@@ -673,7 +716,7 @@ class C4SelfPlay(_SelfPlayPool):
                          torch.zeros(24, dtype=torch.uint8), self.MAX_LEN, games_cap, pi_slot_cap, pi_pool_cap,
                          record=record,
                          max_sims=(tree_nodes or min(2 * sims, 65534)) if reuse_tree else None,
-                         fused_policy=fused_policy)
+                         fused_policy=fused_policy, eval_cache=eval_cache)
         self.reuse_tree = bool(reuse_tree)
         self.record = record
         self.roots = torch.zeros((games, 3), dtype=torch.int64, device=self.dev)
@@ -841,9 +884,10 @@ class ChessSelfPlay(_SelfPlayPool):
                  puct_streams: int = 1, streams: int = 1, record_policy: bool = False,
                  pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
                  reuse_tree: bool = False, tree_nodes: int | None = None, fused_policy: bool = False,
-                 puct_args: dict | None = None):
+                 puct_args: dict | None = None, eval_cache: int = 0):
         """record_policy: every step()'s root visit counts go with the positions into the
         trajectories (TrajBatch.pi / policy_targets(4096)), in every search mode.
+        eval_cache: as C4SelfPlay's (with the convolutional head an entry holds 8 KB of logits).
         puct_args: ChessPuctSearch's c_puct / dirichlet_alpha / dirichlet_eps, where its defaults
         are not wanted.
         fused_policy (needs record_policy): run() and run_pooled() record them as well — the
@@ -870,7 +914,7 @@ class ChessSelfPlay(_SelfPlayPool):
         super().__init__(games, sims, c, batch_size, seed, rank, device, temperature, record_policy,
                          init, max_len, games_cap, pi_slot_cap, pi_pool_cap,
                          max_sims=(tree_nodes or min(2 * sims, 65534)) if reuse_tree else None,
-                         fused_policy=fused_policy)
+                         fused_policy=fused_policy, eval_cache=eval_cache)
         self.reuse_tree = bool(reuse_tree)
         self.eng.chess_reserve()
         self.policy, self.freedom = int(policy), float(freedom)

@@ -73,14 +73,18 @@ def _split_flushes(search, nfl: int, fns: list, first_game: int, select, evaluat
 def _value_backup(sims: int, bs: int, backup):
     """evaluate_backup of a value search's part (_split_flushes): fn.flush_values(first, n,
     flush, stream) where fn has it (values computed on the device from the tree itself), else
-    the part's network on its leaves (a short last flush on its nb leaves only, NetValue.rows),
-    then backup(first, n, flush, values, stream)."""
+    the part's network on its leaves (a short last flush on its nb leaves only, NetValue.rows;
+    a function with wants_leaves gets the leaf rows there too), then backup(first, n, flush,
+    values, stream)."""
     def evaluate_backup(first, m, f, fn, lv, pv, cv, vv, st):
         nb = min(bs, sims - f * bs)   # every game's pending leaves (0 after an error)
         if hasattr(fn, "flush_values"):
             v = fn.flush_values(first, m, f, st)
         elif nb < bs and hasattr(fn, "rows") and pv is not None:
-            v = fn.rows(pv, m, bs, nb, vv)
+            if getattr(fn, "wants_leaves", False):
+                v = fn.rows(pv, m, bs, nb, vv, leaves=lv)
+            else:
+                v = fn.rows(pv, m, bs, nb, vv)
         else:
             v = fn(lv, pv, cv)
         if v.data_ptr() != vv.data_ptr():
@@ -105,11 +109,15 @@ class PolicyNet:
 def _puct_backup(bs: int, backup):
     """evaluate_backup of a PUCT search (part): fn on the flush's planes, then backup(first, n,
     flush, values, logits, logits_f16, stream, rows).  Flush 0 holds the roots only: a
-    roots_only fn evaluates the n root positions alone (rows = 1)."""
+    roots_only fn evaluates the n root positions alone (rows = 1), and gets their leaf rows
+    when it has wants_leaves (and the search keeps leaf rows)."""
     def evaluate_backup(first, m, f, fn, lv, pv, cv, vv, st):
         if f == 0 and getattr(fn, "roots_only", False):
             roots = pv.view(m, bs, *pv.shape[1:])[:, 0].contiguous()
-            v, logits = fn(None, roots, cv)
+            rl = None
+            if getattr(fn, "wants_leaves", False) and lv is not None:
+                rl = lv.view(m, bs, *lv.shape[1:])[:, 0].contiguous()
+            v, logits = fn(rl, roots, cv)
             v = v.reshape(-1).to(torch.float64).contiguous()
             logits = logits.contiguous()
             backup(first, m, f, v.data_ptr(), logits.data_ptr(), logits.dtype == torch.float16, st, rows=1)
@@ -131,7 +139,10 @@ def _warm_parts(search, fns):
         fn(search.leaves[lo * bs:hi * bs] if search.leaves is not None else None,
            search.planes[lo * bs:hi * bs] if search.planes is not None else None, search.counts[lo:hi])
         if getattr(fn, "roots_only", False):
-            fn(None, search.planes[lo * bs:hi * bs:bs].contiguous(), search.counts[lo:hi])
+            rl = None
+            if getattr(fn, "wants_leaves", False) and search.leaves is not None:
+                rl = search.leaves[lo * bs:hi * bs:bs].contiguous()
+            fn(rl, search.planes[lo * bs:hi * bs:bs].contiguous(), search.counts[lo:hi])
 
 
 class _StepSearch:
