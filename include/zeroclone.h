@@ -971,6 +971,58 @@ int zc_evalcache_commit_async(void *d_table, int64_t entries, int32_t key_bytes,
                               int32_t *d_count, const double *d_dense_values, const void *d_dense_logits,
                               double *d_out_values, void *d_out_logits, int64_t *d_stats, void *hip_stream);
 
+/* ---- evaluation cache, merged flush: a key pending several times in one flush is evaluated
+ * once (evalcache.hip) ------------------------------------------------------------------------
+ * The calls above evaluate a key twice when two rows of one flush carry it: both miss in the
+ * same probe.  The merged calls stand where they stand (probe -> counted network -> commit,
+ * three launches as before) and take the same arguments plus a flush-local scratch and a fifth
+ * counter.  Among the rows that miss the table, rows with an equal key — EVERY KEY WORD EQUAL,
+ * the rule of a hit — share one evaluation: one of them, the key's leader, takes the dense slot
+ * and the others, its followers, get a copy of the leader's outputs in the commit.  The network
+ * computing every board on its own, the copy is what evaluating the follower gives, bit for bit.
+ * Which of the equal rows leads may differ from run to run, like the dense order; no output
+ * depends on it.
+ *
+ * d_table == NULL with entries == 0: NO TABLE.  Nothing hits and nothing is inserted; every
+ * taking-part row goes to the merge, which then costs the scratch alone.
+ *
+ * zc_evalcache_merge_scratch_bytes: *bytes = the scratch for flushes of n_rows rows: a claim
+ * table of S int32 words, S the power of two with 2 * n_rows <= S < 4 * n_rows (at least 2),
+ * and one int32 leader word per taking-part row.  The scratch is 4-byte aligned and ALL ZEROS
+ * BEFORE ITS FIRST FLUSH; a flush (probe + commit) leaves it all zeros where it matters — the
+ * commit's last launch zeroes the claim words, the probe writes every leader word before any is
+ * read — so it serves flush after flush of that n_rows, and graph replays, with no host-side
+ * clear.  One scratch belongs to one stream, as the table does.
+ *
+ * zc_evalcache_probe_merged_async: as zc_evalcache_probe_async for a row that hits.  A row that
+ * misses hashes its key into the claim table and claims a slot with one atomicCAS that writes
+ * its row number.  It wins an empty slot: it is the leader and goes on as a miss does above
+ * (dense slot, planes, d_miss_rows).  The slot is taken: it compares its key with the
+ * claimant's, read from d_keys (no kernel writes them during the flush; the claimant comes back
+ * from the CAS itself); equal, it is a follower, records the claimant's row in its leader word,
+ * takes no dense slot and copies no planes; unequal, it goes to the next slot.  d_stats: FIVE
+ * int64 counters; adds to PROBED, HITS and MERGED (the followers).
+ *
+ * zc_evalcache_commit_merged_async: the commit launch of zc_evalcache_commit_async over the
+ * dense slots (without a table its scatter alone), then one launch over the taking-part rows:
+ * a follower's value and logits are copied from its leader's output slots, the claim words are
+ * zeroed, *d_count = 0 and the table moves to its next epoch.  No two waves of one commit insert
+ * the same key any more: DROPPED counts tag collisions and lost victim claims alone, and
+ * PROBED = HITS + MERGED + INSERTS + DROPPED (without a table HITS = INSERTS = DROPPED = 0 and
+ * PROBED - MERGED rows were evaluated). */
+#define ZC_EVALCACHE_STAT_MERGED 4
+int zc_evalcache_merge_scratch_bytes(int32_t n_rows, int64_t *bytes);
+int zc_evalcache_probe_merged_async(void *d_table, int64_t entries, int32_t key_bytes, int32_t logit_bytes,
+                                    int32_t n_rows, int32_t rows_per_game, int32_t game_rows, const void *d_keys,
+                                    const void *d_planes, int64_t plane_bytes, double *d_out_values,
+                                    void *d_out_logits, void *d_dense_planes, int32_t *d_miss_rows, int32_t *d_count,
+                                    int64_t *d_stats, void *d_scratch, void *hip_stream);
+int zc_evalcache_commit_merged_async(void *d_table, int64_t entries, int32_t key_bytes, int32_t logit_bytes,
+                                     int32_t n_rows, int32_t rows_per_game, int32_t game_rows, const void *d_keys,
+                                     const int32_t *d_miss_rows, int32_t *d_count, const double *d_dense_values,
+                                     const void *d_dense_logits, double *d_out_values, void *d_out_logits,
+                                     int64_t *d_stats, void *d_scratch, void *hip_stream);
+
 /* ---- any game backend: SURVEY §8(b)'s fallback (gen_search.hip) ----------------------
  * mcts.get_move (mcts.cpp:102-160) for a backend the device knows nothing about: the caller
  * keeps the game states and move objects (backend.get_legal_moves / play_move, the policy

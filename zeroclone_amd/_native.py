@@ -342,6 +342,19 @@ SIGNATURES = [
                                                  ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_evalcache_merge_scratch_bytes", ctypes.c_int, [ctypes.c_int32, P(ctypes.c_int64)]),
+    ("zc_evalcache_probe_merged_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_evalcache_commit_merged_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p]),
     ("zc_chess_from_fen", ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
     ("zc_chess_init", ctypes.c_int, [ctypes.c_void_p]),
     ("zc_c4_from_rows", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, P(C4State)]),
@@ -590,6 +603,64 @@ def evalcache_commit(d_table: int, entries: int, key_bytes: int, logit_bytes: in
         int(game_rows), ctypes.c_void_p(d_keys), ctypes.c_void_p(d_miss_rows), ctypes.c_void_p(d_count),
         ctypes.c_void_p(d_dense_values), ctypes.c_void_p(d_dense_logits or None), ctypes.c_void_p(d_out_values),
         ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_stats or None), ctypes.c_void_p(stream or None)))
+
+
+# ZC_EVALCACHE_STAT_* of the merged calls: the five int64 counters
+EVALCACHE_MERGED_STATS = EVALCACHE_STATS + ("merged",)
+
+
+def evalcache_check_merged_sizes(entries: int, key_bytes: int, logit_bytes: int):
+    """evalcache_check_sizes for the merged calls: entries 0 is "no table"."""
+    evalcache_check_sizes(entries or EVALCACHE_WAYS, key_bytes, logit_bytes)
+
+
+def evalcache_merge_scratch_bytes(n_rows: int) -> int:
+    """zc_evalcache_merge_scratch_bytes: the flush-local scratch of the merged calls, in bytes."""
+    if not 0 <= n_rows < 1 << 31:
+        raise ValueError(f"n_rows must be in [0, 2^31) (got {n_rows})")
+    b = ctypes.c_int64(0)
+    _arena_rc("zc_evalcache_merge_scratch_bytes", lib().zc_evalcache_merge_scratch_bytes(int(n_rows), ctypes.byref(b)))
+    return b.value
+
+
+def evalcache_probe_merged(d_table: int, entries: int, key_bytes: int, logit_bytes: int, n_rows: int,
+                           rows_per_game: int, game_rows: int, d_keys: int, d_planes: int, plane_bytes: int,
+                           d_out_values: int, d_out_logits: int, d_dense_planes: int, d_miss_rows: int, d_count: int,
+                           d_stats: int, d_scratch: int, stream: int = 0):
+    """zc_evalcache_probe_merged_async (include/zeroclone.h) on device pointers; d_table 0 with
+    entries 0: no table.  Only enqueues."""
+    name = "zc_evalcache_probe_merged_async"
+    _evalcache_rows(name, n_rows, rows_per_game, game_rows)
+    if plane_bytes < 2 or plane_bytes % 2:
+        raise ValueError(f"{name}: plane_bytes must be a positive multiple of 2 (got {plane_bytes})")
+    if not d_count or (n_rows and not (d_keys and d_planes and d_out_values and d_dense_planes and d_miss_rows
+                                       and d_scratch and (d_out_logits or not logit_bytes))):
+        raise ValueError(f"{name}: null device pointer")
+    _arena_rc(name, lib().zc_evalcache_probe_merged_async(
+        ctypes.c_void_p(d_table or None), int(entries), int(key_bytes), int(logit_bytes), int(n_rows),
+        int(rows_per_game), int(game_rows), ctypes.c_void_p(d_keys), ctypes.c_void_p(d_planes), int(plane_bytes),
+        ctypes.c_void_p(d_out_values), ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_dense_planes),
+        ctypes.c_void_p(d_miss_rows), ctypes.c_void_p(d_count), ctypes.c_void_p(d_stats or None),
+        ctypes.c_void_p(d_scratch or None), ctypes.c_void_p(stream or None)))
+
+
+def evalcache_commit_merged(d_table: int, entries: int, key_bytes: int, logit_bytes: int, n_rows: int,
+                            rows_per_game: int, game_rows: int, d_keys: int, d_miss_rows: int, d_count: int,
+                            d_dense_values: int, d_dense_logits: int, d_out_values: int, d_out_logits: int,
+                            d_stats: int, d_scratch: int, stream: int = 0):
+    """zc_evalcache_commit_merged_async (include/zeroclone.h) on device pointers; leaves *d_count
+    = 0 and the scratch ready for the next flush.  Only enqueues."""
+    name = "zc_evalcache_commit_merged_async"
+    _evalcache_rows(name, n_rows, rows_per_game, game_rows)
+    if not d_count or (n_rows and not (d_keys and d_miss_rows and d_dense_values and d_out_values and d_scratch
+                                       and ((d_dense_logits and d_out_logits) or not logit_bytes))):
+        raise ValueError(f"{name}: null device pointer")
+    _arena_rc(name, lib().zc_evalcache_commit_merged_async(
+        ctypes.c_void_p(d_table or None), int(entries), int(key_bytes), int(logit_bytes), int(n_rows),
+        int(rows_per_game), int(game_rows), ctypes.c_void_p(d_keys), ctypes.c_void_p(d_miss_rows),
+        ctypes.c_void_p(d_count), ctypes.c_void_p(d_dense_values), ctypes.c_void_p(d_dense_logits or None),
+        ctypes.c_void_p(d_out_values), ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_stats or None),
+        ctypes.c_void_p(d_scratch or None), ctypes.c_void_p(stream or None)))
 
 
 def _train_rc(name: str, rc: int):

@@ -100,6 +100,9 @@ class _ArenaPool:
         if kw.get("eval_cache"):
             raise ValueError("an arena routes the planes alone, without the leaf rows an evaluation cache keys on "
                              "(eval_cache)")
+        if kw.get("eval_merge"):
+            raise ValueError("an arena routes the planes alone, without the leaf rows a merged flush keys on "
+                             "(eval_merge)")
         if kw.get("streams", 1) > 1 or kw.get("puct_streams", 1) > 1:
             raise ValueError("an arena searches on one stream (streams / puct_streams > 1): the two groups are not "
                              "contiguous game ranges")

@@ -16,6 +16,9 @@
 // One table belongs to one stream: probe and commit are ordered by the stream, so a probe never
 // runs beside a commit and there is no reader / writer protocol.  Within a commit launch no
 // wave reads a key or a payload; the meta words are read and claimed with device-scope atomics.
+//
+// The merged entry points (further down) carry a flush through the same three launches and
+// evaluate a key that several of its rows hold once, with or without a table.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -255,6 +258,191 @@ __global__ void evalcache_finish_kernel(uint32_t *epoch, int32_t *d_count) {
     *epoch += 1;
 }
 
+// ---- merging: a key pending several times in one flush is evaluated once -------------------
+//
+// The flush-local scratch: [claim int32 x S][leader int32 x n_rows], S the power of two with
+// 2 * n_rows <= S < 4 * n_rows.  A claim word is 0 while its slot is empty, else 1 + the
+// taking-part row that claimed it; leader[r] is the buffer row whose outputs row r takes, or -1
+// for a row that takes its own (a hit or a leader).  The probe writes every taking-part row's
+// leader word, and the flush's last launch zeroes the claim words again: the scratch is all
+// zeros between flushes, and only before the first one does the caller have to make it so.
+
+struct Merge {
+    int32_t *claim;
+    int32_t *leader;
+    uint32_t claim_mask;
+};
+
+int64_t claim_slots(int32_t n_rows) {
+    int64_t s = 2;
+    while (s < 2 * (int64_t)n_rows) s *= 2;
+    return s;
+}
+
+// The probe kernel with a claim step between the lookup and the dense slot.  has_table false:
+// t holds the key and logit sizes alone and every row goes to the claim table.  A row that
+// misses walks the claim table from the slot its hash picks: an empty slot is claimed with one
+// atomicCAS (the row is its key's leader and goes on as a miss does in the plain probe); a
+// taken slot's claimant comes back from the CAS, and its key is read from `keys`, which no
+// kernel writes during the flush — equal in every word: this row is a follower and records the
+// claimant's buffer row; else the next slot.  At most n_rows claims in 2 * n_rows slots or more
+// end the walk; it is bounded by the table's size all the same (a scratch that was not zero),
+// and a row whose walk runs out leads without a claim.
+__global__ __launch_bounds__(BLOCK) void evalcache_probe_merged_kernel(
+    Table t, bool has_table, Merge m, int n_rows, int rows_per_game, int game_rows, const uint64_t *__restrict__ keys,
+    const uint8_t *__restrict__ planes, int64_t plane_bytes, double *__restrict__ out_values,
+    uint8_t *__restrict__ out_logits, uint8_t *__restrict__ dense_planes, int32_t *__restrict__ miss_rows,
+    int32_t *d_count, int64_t *stats) {
+    __shared__ int s_miss[WAVES], s_merged[WAVES];
+    __shared__ int s_base;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * WAVES + wave;
+    const bool live = r < n_rows;
+    int64_t row = 0, entry = -1, lead = -1;
+    if (live) {
+        const int g = r / rows_per_game;
+        row = (int64_t)g * game_rows + (r - g * rows_per_game);
+        const uint64_t word = lane < t.kw ? keys[row * t.kw + lane] : 0;
+        const uint64_t h = key_hash(word, lane, t.kw);
+        if (has_table) {
+            const int64_t e0 = (int64_t)((uint32_t)h & t.set_mask) * WAYS;
+            const uint32_t tag = hash_tag(h);
+            const uint32_t meta = lane < WAYS ? t.meta[e0 + lane] : 0u;
+            unsigned long long cand = __ballot(lane < WAYS && (meta >> 16) == tag);   // an empty way's tag is 0
+            while (cand) {
+                const int w = __builtin_ctzll(cand);
+                cand &= cand - 1;
+                const bool eq = lane < t.kw ? t.keys[(e0 + w) * t.kw + lane] == word : true;
+                if (__all(eq)) {
+                    entry = e0 + w;
+                    break;
+                }
+            }
+        }
+        if (entry < 0) {
+            uint32_t i = (uint32_t)(h >> 24) & m.claim_mask;   // not the bits that pick the table's set
+            for (uint64_t step = 0; step <= m.claim_mask; ++step, i = (i + 1) & m.claim_mask) {
+                int old = 0;
+                if (lane == 0) old = atomicCAS(m.claim + i, 0, r + 1);
+                old = __shfl(old, 0, 64);
+                if (old == 0) break;   // claimed: this row leads
+                const int cr = old - 1;
+                if (cr < 0 || cr >= n_rows) continue;   // no row of this flush: the scratch was not zero
+                const int cg = cr / rows_per_game;
+                const int64_t crow = (int64_t)cg * game_rows + (cr - cg * rows_per_game);
+                const bool eq = lane < t.kw ? keys[crow * t.kw + lane] == word : true;
+                if (__all(eq)) {
+                    lead = crow;
+                    break;
+                }
+            }
+        }
+        if (lane == 0) m.leader[r] = (int32_t)lead;
+    }
+    if (lane == 0) {
+        s_miss[wave] = live && entry < 0 && lead < 0;
+        s_merged[wave] = live && lead >= 0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int nm = 0, nf = 0;
+        for (int w = 0; w < WAVES; ++w) {
+            nm += s_miss[w];
+            nf += s_merged[w];
+        }
+        const int nlive = min(WAVES, n_rows - (int)blockIdx.x * WAVES);
+        s_base = nm ? atomicAdd(d_count, nm) : 0;
+        if (stats) {
+            count_add(stats + ZC_EVALCACHE_STAT_PROBED, nlive);
+            count_add(stats + ZC_EVALCACHE_STAT_HITS, nlive - nm - nf);
+            count_add(stats + ZC_EVALCACHE_STAT_MERGED, nf);
+        }
+    }
+    __syncthreads();
+    if (!live || lead >= 0) return;   // a follower takes no dense slot and copies no planes
+    if (entry >= 0) {
+        if (lane == 0) out_values[row] = t.values[entry];
+        if (t.logit_bytes)
+            wave_copy(out_logits + row * t.logit_bytes, t.logits + entry * t.lstride, t.logit_bytes, lane);
+    } else {
+        int slot = s_base;
+        for (int w = 0; w < wave; ++w) slot += s_miss[w];
+        if (slot < 0 || slot >= n_rows) return;   // *d_count was not 0 before the flush: no slot is this row's
+        wave_copy(dense_planes + (int64_t)slot * plane_bytes, planes + row * plane_bytes, plane_bytes, lane);
+        if (lane == 0) miss_rows[slot] = (int32_t)row;
+    }
+}
+
+// Without a table the commit kernel's scatter alone: one wave per dense slot below
+// min(*d_count, cap), the slot's payload to its row's output slots.
+__global__ __launch_bounds__(BLOCK) void evalcache_scatter_kernel(
+    int cap, int64_t total_rows, int64_t logit_bytes, const int32_t *__restrict__ miss_rows,
+    const int32_t *__restrict__ d_count, const double *__restrict__ dense_values,
+    const uint8_t *__restrict__ dense_logits, double *__restrict__ out_values, uint8_t *__restrict__ out_logits) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int slot = blockIdx.x * WAVES + wave;
+    const int count = min(max(*d_count, 0), cap);
+    const int64_t row = slot < count ? miss_rows[slot] : -1;
+    if (row < 0 || row >= total_rows) return;
+    if (lane == 0) out_values[row] = dense_values[slot];
+    if (logit_bytes)
+        wave_copy(out_logits + row * logit_bytes, dense_logits + (int64_t)slot * logit_bytes, logit_bytes, lane);
+}
+
+// The merged flush's last launch, after the commit's scatter: one wave per taking-part row; a
+// follower's value and logits come from its leader's output slots (a leader is no follower, so
+// no wave reads a slot that this launch writes).  Every thread zeroes its share of the claim
+// words (the grid has 64 threads a row, the table fewer than 4 words a row), and one thread
+// does evalcache_finish_kernel's work (epoch NULL: no table).
+__global__ __launch_bounds__(BLOCK) void evalcache_finish_merged_kernel(
+    Merge m, int n_rows, int rows_per_game, int game_rows, int64_t total_rows, int64_t logit_bytes,
+    double *out_values, uint8_t *out_logits, uint32_t *epoch, int32_t *d_count) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * WAVES + wave;
+    if (r < n_rows) {
+        const int64_t lead = m.leader[r];
+        if (lead >= 0 && lead < total_rows) {
+            const int g = r / rows_per_game;
+            const int64_t row = (int64_t)g * game_rows + (r - g * rows_per_game);
+            if (lane == 0) out_values[row] = out_values[lead];
+            if (logit_bytes)
+                wave_copy(out_logits + row * logit_bytes, out_logits + lead * logit_bytes, logit_bytes, lane);
+        }
+    }
+    if (m.claim) {   // NULL: a flush of no rows
+        const int64_t slots = (int64_t)m.claim_mask + 1;
+        for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < slots; i += (int64_t)gridDim.x * BLOCK)
+            m.claim[i] = 0;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *d_count = 0;
+        if (epoch) *epoch += 1;
+    }
+}
+
+// The merged calls' table: d_table NULL with entries 0 is "no table" (*has_table false, t's
+// sizes alone set).
+bool make_table_or_none(void *d_table, int64_t entries, int32_t key_bytes, int32_t logit_bytes, Table *t,
+                        bool *has_table) {
+    *has_table = d_table || entries;
+    if (*has_table) return make_table(d_table, entries, key_bytes, logit_bytes, t);
+    if (!layout(WAYS, key_bytes, logit_bytes, nullptr, nullptr)) return false;
+    *t = Table{};
+    t->kw = key_bytes / 8;
+    t->logit_bytes = logit_bytes;
+    t->lstride = ((int64_t)logit_bytes + 15) & ~(int64_t)15;
+    return true;
+}
+
+bool make_merge(void *d_scratch, int32_t n_rows, Merge *m) {
+    if (!d_scratch || ((uintptr_t)d_scratch & 3)) return false;
+    const int64_t slots = claim_slots(n_rows);
+    m->claim = (int32_t *)d_scratch;
+    m->leader = m->claim + slots;
+    m->claim_mask = (uint32_t)(slots - 1);
+    return true;
+}
+
 int done() { return hipGetLastError() == hipSuccess ? ZC_OK : ZC_EHIP; }
 
 }  // namespace
@@ -322,6 +510,79 @@ int zc_evalcache_commit_async(void *d_table, int64_t entries, int32_t key_bytes,
                            (int)n_rows, total_rows, (const uint64_t *)d_keys, d_miss_rows, (const int32_t *)d_count, d_dense_values,
                            (const uint8_t *)d_dense_logits, d_out_values, (uint8_t *)d_out_logits, d_stats);
     hipLaunchKernelGGL(evalcache_finish_kernel, dim3(1), dim3(1), 0, s, t.epoch, d_count);
+    return done();
+}
+
+int zc_evalcache_merge_scratch_bytes(int32_t n_rows, int64_t *bytes) {
+    if (n_rows < 0 || !bytes) return ZC_EINVAL;
+    *bytes = (claim_slots(n_rows) + n_rows) * (int64_t)sizeof(int32_t);
+    return ZC_OK;
+}
+
+int zc_evalcache_probe_merged_async(void *d_table, int64_t entries, int32_t key_bytes, int32_t logit_bytes,
+                                    int32_t n_rows, int32_t rows_per_game, int32_t game_rows, const void *d_keys,
+                                    const void *d_planes, int64_t plane_bytes, double *d_out_values,
+                                    void *d_out_logits, void *d_dense_planes, int32_t *d_miss_rows, int32_t *d_count,
+                                    int64_t *d_stats, void *d_scratch, void *hip_stream) {
+    Table t;
+    Merge m;
+    bool has_table;
+    if (!make_table_or_none(d_table, entries, key_bytes, logit_bytes, &t, &has_table)) return ZC_EINVAL;
+    if (n_rows < 0 || rows_per_game < 1 || game_rows < rows_per_game || n_rows % rows_per_game) return ZC_EINVAL;
+    if ((int64_t)(n_rows / rows_per_game) * game_rows >= ((int64_t)1 << 31)) return ZC_EINVAL;
+    if (plane_bytes < 2 || (plane_bytes & 1) || !d_count || ((uintptr_t)d_count & 3) || ((uintptr_t)d_stats & 7))
+        return ZC_EINVAL;
+    if (!n_rows) return ZC_OK;
+    if (!d_keys || !d_planes || !d_out_values || !d_dense_planes || !d_miss_rows || (logit_bytes && !d_out_logits))
+        return ZC_EINVAL;
+    if (((uintptr_t)d_keys & 7) || ((uintptr_t)d_out_values & 7) || ((uintptr_t)d_miss_rows & 3) ||
+        (((uintptr_t)d_planes | (uintptr_t)d_dense_planes | (uintptr_t)d_out_logits) & 1))
+        return ZC_EINVAL;
+    if (!make_merge(d_scratch, n_rows, &m)) return ZC_EINVAL;
+    (void)hipGetLastError();   // an earlier call's error is not this launch's
+    hipLaunchKernelGGL(evalcache_probe_merged_kernel, dim3((n_rows + WAVES - 1) / WAVES), dim3(BLOCK), 0,
+                       (hipStream_t)hip_stream, t, has_table, m, (int)n_rows, (int)rows_per_game, (int)game_rows,
+                       (const uint64_t *)d_keys, (const uint8_t *)d_planes, plane_bytes, d_out_values,
+                       (uint8_t *)d_out_logits, (uint8_t *)d_dense_planes, d_miss_rows, d_count, d_stats);
+    return done();
+}
+
+int zc_evalcache_commit_merged_async(void *d_table, int64_t entries, int32_t key_bytes, int32_t logit_bytes,
+                                     int32_t n_rows, int32_t rows_per_game, int32_t game_rows, const void *d_keys,
+                                     const int32_t *d_miss_rows, int32_t *d_count, const double *d_dense_values,
+                                     const void *d_dense_logits, double *d_out_values, void *d_out_logits,
+                                     int64_t *d_stats, void *d_scratch, void *hip_stream) {
+    Table t;
+    Merge m{};
+    bool has_table;
+    if (!make_table_or_none(d_table, entries, key_bytes, logit_bytes, &t, &has_table)) return ZC_EINVAL;
+    if (n_rows < 0 || !d_count || ((uintptr_t)d_count & 3) || ((uintptr_t)d_stats & 7)) return ZC_EINVAL;
+    if (rows_per_game < 1 || game_rows < rows_per_game || n_rows % rows_per_game) return ZC_EINVAL;
+    const int64_t total_rows = (int64_t)(n_rows / rows_per_game) * game_rows;
+    if (total_rows >= ((int64_t)1 << 31)) return ZC_EINVAL;
+    if (n_rows) {
+        if (!d_keys || !d_miss_rows || !d_dense_values || !d_out_values ||
+            (logit_bytes && (!d_dense_logits || !d_out_logits)))
+            return ZC_EINVAL;
+        if (((uintptr_t)d_keys & 7) || ((uintptr_t)d_out_values & 7) || ((uintptr_t)d_dense_values & 7) ||
+            ((uintptr_t)d_miss_rows & 3) || (((uintptr_t)d_dense_logits | (uintptr_t)d_out_logits) & 1))
+            return ZC_EINVAL;
+        if (!make_merge(d_scratch, n_rows, &m)) return ZC_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)hip_stream;
+    const dim3 grid(n_rows ? (n_rows + WAVES - 1) / WAVES : 1);
+    (void)hipGetLastError();   // an earlier call's error is not this launch's
+    if (n_rows && has_table)
+        hipLaunchKernelGGL(evalcache_commit_kernel, grid, dim3(BLOCK), 0, s, t, (int)n_rows, total_rows,
+                           (const uint64_t *)d_keys, d_miss_rows, (const int32_t *)d_count, d_dense_values,
+                           (const uint8_t *)d_dense_logits, d_out_values, (uint8_t *)d_out_logits, d_stats);
+    else if (n_rows)
+        hipLaunchKernelGGL(evalcache_scatter_kernel, grid, dim3(BLOCK), 0, s, (int)n_rows, total_rows,
+                           (int64_t)logit_bytes, d_miss_rows, (const int32_t *)d_count, d_dense_values,
+                           (const uint8_t *)d_dense_logits, d_out_values, (uint8_t *)d_out_logits);
+    hipLaunchKernelGGL(evalcache_finish_merged_kernel, grid, dim3(BLOCK), 0, s, m, (int)n_rows, (int)rows_per_game,
+                       (int)game_rows, total_rows, (int64_t)logit_bytes, d_out_values, (uint8_t *)d_out_logits,
+                       has_table ? t.epoch : (uint32_t *)nullptr, d_count);
     return done();
 }
 

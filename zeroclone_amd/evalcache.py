@@ -15,6 +15,11 @@ can be captured in a HIP graph as before.
 cache)` where `valued.PolicyNet(net)` does.  Both need the leaf rows: allocate the search with
 leaves=True.  One EvalCache belongs to one stream and to one set of weights: give every
 stream's replica of the network a cache of its own, and `clear()` it when the weights change.
+
+`EvalCache(..., merge=True)` runs the merged calls (zc_evalcache_probe_merged_async / ..._commit_
+merged_async): among a flush's rows that miss the table, rows with an equal key are evaluated
+once and the others take a copy.  With entries = 0 there is no table and merging is all the
+cache does, at no memory beyond a few words a row.
 """
 from __future__ import annotations
 
@@ -32,38 +37,57 @@ class EvalCache:
     """The table (zc_evalcache_*), its miss counter, its four counters and the dense buffers of
     the misses (allocated per flush shape at first use).  entries: the table holds the largest
     power-of-two number of 8-way sets within it.  key_bytes: the leaf row's size (24: zc_c4_state,
-    72: zc_chess_state).  logit_bytes: the logits of one row (0: a value network)."""
+    72: zc_chess_state).  logit_bytes: the logits of one row (0: a value network).  merge: equal
+    rows of one flush are evaluated once (a fifth counter, "merged", and a scratch per flush
+    shape); entries = 0, with merge alone: no table."""
 
-    def __init__(self, entries: int, key_bytes: int, logit_bytes: int = 0, device="cuda"):
-        _native.evalcache_check_sizes(entries, key_bytes, logit_bytes)
+    def __init__(self, entries: int, key_bytes: int, logit_bytes: int = 0, device="cuda", merge: bool = False):
+        if merge:
+            _native.evalcache_check_merged_sizes(entries, key_bytes, logit_bytes)
+        else:
+            _native.evalcache_check_sizes(entries, key_bytes, logit_bytes)
         self.entries, self.key_bytes, self.logit_bytes = int(entries), int(key_bytes), int(logit_bytes)
+        self.merge = bool(merge)
+        self._stat_names = _native.EVALCACHE_MERGED_STATS if merge else _native.EVALCACHE_STATS
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
             raise ValueError("the evaluation cache lives on a GPU")
-        self.table = None    # allocated at first use
+        self.table = self.count = None    # allocated at first use
         self._bufs = {}
 
     def _sizes(self):
         return self.entries, self.key_bytes, self.logit_bytes
 
     def _ensure(self):
-        if self.table is None:
+        if self.count is None:
             if torch.cuda.is_current_stream_capturing():   # the zero fill would be replayed with the graph
                 raise RuntimeError("the evaluation cache must exist before a graph capture: call clear() first")
-            nbytes, self.sets = _native.evalcache_bytes(*self._sizes())
-            self.table = torch.zeros(nbytes, dtype=torch.uint8, device=self.dev)   # all zeros: empty
+            if self.entries:
+                nbytes, self.sets = _native.evalcache_bytes(*self._sizes())
+                self.table = torch.zeros(nbytes, dtype=torch.uint8, device=self.dev)   # all zeros: empty
             self.count = torch.zeros(1, dtype=torch.int32, device=self.dev)
-            self.counters = torch.zeros(len(_native.EVALCACHE_STATS), dtype=torch.int64, device=self.dev)
+            self.counters = torch.zeros(len(self._stat_names), dtype=torch.int64, device=self.dev)
+
+    def _table_ptr(self) -> int:
+        return self.table.data_ptr() if self.table is not None else 0
 
     def clear(self):
-        """Empty the table (stream-ordered; the counters keep counting)."""
+        """Empty the table (stream-ordered; the counters keep counting).  Without a table
+        (entries = 0) there is nothing to empty."""
         self._ensure()
-        _native.evalcache_clear(self.table.data_ptr(), *self._sizes(), _stream(self.dev))
+        if self.table is not None:
+            _native.evalcache_clear(self.table.data_ptr(), *self._sizes(), _stream(self.dev))
 
     def stats(self) -> dict:
-        """{"probed", "hits", "inserts", "dropped"} so far.  Synchronises."""
+        """{"probed", "hits", "inserts", "dropped"} so far, and "merged" with merge=True.
+        Synchronises."""
         self._ensure()
-        return dict(zip(_native.EVALCACHE_STATS, (int(x) for x in self.counters.cpu())))
+        return dict(zip(self._stat_names, (int(x) for x in self.counters.cpu())))
+
+    def _scratch(self, n_rows: int) -> torch.Tensor:
+        """The merged calls' scratch for flushes of n_rows rows: zeros at first, and every flush
+        leaves it so."""
+        return self._buf("merge", (_native.evalcache_merge_scratch_bytes(n_rows) // 4,), torch.int32)
 
     def _buf(self, name: str, shape: tuple, dtype) -> torch.Tensor:
         key = (name, tuple(shape), dtype)
@@ -92,15 +116,20 @@ class EvalCache:
         n_rows = leaves.shape[0] // game_rows * rows
         dense = self._buf("planes", (n_rows, *planes.shape[1:]), planes.dtype)
         miss = self._buf("miss", (n_rows,), torch.int32)
-        _native.evalcache_probe(self.table.data_ptr(), *self._sizes(), n_rows, rows, game_rows, leaves.data_ptr(),
-                                planes.data_ptr(), planes[0].numel() * planes.element_size(), out_values.data_ptr(),
-                                out_logits.data_ptr() if out_logits is not None else 0, dense.data_ptr(),
-                                miss.data_ptr(), self.count.data_ptr(), self.counters.data_ptr(), _stream(self.dev))
+        args = (self._table_ptr(), *self._sizes(), n_rows, rows, game_rows, leaves.data_ptr(), planes.data_ptr(),
+                planes[0].numel() * planes.element_size(), out_values.data_ptr(),
+                out_logits.data_ptr() if out_logits is not None else 0, dense.data_ptr(), miss.data_ptr(),
+                self.count.data_ptr(), self.counters.data_ptr())
+        if self.merge:
+            _native.evalcache_probe_merged(*args, self._scratch(n_rows).data_ptr(), _stream(self.dev))
+        else:
+            _native.evalcache_probe(*args, _stream(self.dev))
         return dense, self.count
 
     def commit(self, leaves, rows: int, game_rows: int, dense_values, dense_logits, out_values, out_logits=None):
         """After the network ran on probe's dense planes: the misses' outputs go to their rows'
-        slots of out_values / out_logits and into the table; self.count is 0 again."""
+        slots of out_values / out_logits and into the table (with merge, their followers' slots
+        too); self.count is 0 again."""
         n_rows = leaves.shape[0] // game_rows * rows
         miss = self._buf("miss", (n_rows,), torch.int32)
         if dense_values.dtype != torch.float64 or dense_values.numel() < n_rows:
@@ -109,11 +138,14 @@ class EvalCache:
             if dense_logits is None or not dense_logits.is_contiguous() or dense_logits.shape[0] < n_rows or \
                     dense_logits[0].numel() * dense_logits.element_size() != self.logit_bytes:
                 raise ValueError(f"the network must return contiguous logits of {self.logit_bytes} bytes a row")
-        _native.evalcache_commit(self.table.data_ptr(), *self._sizes(), n_rows, rows, game_rows, leaves.data_ptr(),
-                                 miss.data_ptr(), self.count.data_ptr(), dense_values.data_ptr(),
-                                 dense_logits.data_ptr() if self.logit_bytes else 0, out_values.data_ptr(),
-                                 out_logits.data_ptr() if out_logits is not None else 0, self.counters.data_ptr(),
-                                 _stream(self.dev))
+        args = (self._table_ptr(), *self._sizes(), n_rows, rows, game_rows, leaves.data_ptr(), miss.data_ptr(),
+                self.count.data_ptr(), dense_values.data_ptr(), dense_logits.data_ptr() if self.logit_bytes else 0,
+                out_values.data_ptr(), out_logits.data_ptr() if out_logits is not None else 0,
+                self.counters.data_ptr())
+        if self.merge:
+            _native.evalcache_commit_merged(*args, self._scratch(n_rows).data_ptr(), _stream(self.dev))
+        else:
+            _native.evalcache_commit(*args, _stream(self.dev))
 
 
 class CachedValue:

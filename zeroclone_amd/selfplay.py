@@ -405,6 +405,19 @@ def _warm(search, fn, sims: int):
             f.rows(search.planes[lo * bs:hi * bs], hi - lo, bs, nb, search.values[lo * bs:hi * bs], **kw)
 
 
+def _check_eval_merge(eval_merge: bool, net, puct_net):
+    """eval_merge's refusals, before the engine: they need no GPU."""
+    if not eval_merge:
+        return
+    if net is None and puct_net is None:
+        raise ValueError("eval_merge merges a network's evaluations: it needs net= or puct_net=")
+    from . import nets
+    for n, kind in ((net, nets.MfmaValueNetwork), (puct_net, nets.MfmaPolicyValueNetwork)):
+        if n is not None and not isinstance(n, kind):
+            raise ValueError("eval_merge needs the MFMA form of the network (its tower takes the row count from "
+                             "the device): a torch module cannot be merged")
+
+
 class _SelfPlayPool:
     """What `C4SelfPlay` and `ChessSelfPlay` share: G games of one GPU, the engine and its game
     streams, the three-way search choice of a step (the game's own search kernel, a value
@@ -428,11 +441,11 @@ class _SelfPlayPool:
                  temperature: float, record_policy: bool, init_row: torch.Tensor, max_len: int,
                  games_cap: int | None, pi_slot_cap: int | None, pi_pool_cap: int | None,
                  record: bool = True, max_sims: int | None = None, fused_policy: bool = False,
-                 eval_cache: int = 0):
+                 eval_cache: int = 0, eval_merge: bool = False):
         """The refusals come before the engine: they need no GPU."""
         if int(eval_cache) < 0:
             raise ValueError(f"eval_cache is a number of entries: 0 (off) or positive (got {eval_cache})")
-        self.eval_cache, self._caches = int(eval_cache), []
+        self.eval_cache, self.eval_merge, self._caches = int(eval_cache), bool(eval_merge), []
         if record_policy and sims > _native.ZC_TRAJ_PI_MAX_COUNT:   # an entry's count field is 16 bits
             raise ValueError(f"record_policy stores visit counts in 16 bits: sims {sims} > "
                              f"{_native.ZC_TRAJ_PI_MAX_COUNT}")
@@ -469,11 +482,12 @@ class _SelfPlayPool:
         (valued._split_flushes)."""
         if self.eval_cache and net is None and puct_net is None:
             raise ValueError("eval_cache caches a network's evaluations: it needs net= or puct_net=")
+        leaves = bool(self.eval_cache or self.eval_merge)
         if net is not None:
-            self.vs = value_search(self.eng, self.G, self.bs, leaves=bool(self.eval_cache), **value_kw)
+            self.vs = value_search(self.eng, self.G, self.bs, leaves=leaves, **value_kw)
             self.value_fn = self._callables(net, streams, False)
         if puct_net is not None:
-            self.ps = puct_search(self.eng, self.G, self.bs, leaves=bool(self.eval_cache), **puct_kw)
+            self.ps = puct_search(self.eng, self.G, self.bs, leaves=leaves, **puct_kw)
             self.net_fn = self._callables(puct_net, puct_streams, True)
 
     def _callables(self, net, k: int, puct: bool):
@@ -481,21 +495,23 @@ class _SelfPlayPool:
         (weights shared, buffers their own).  With eval_cache, evalcache.CachedValue /
         CachedPolicy, every stream's over a table of its own of eval_cache / k entries — parts
         on different streams never share a table — and every table empty: a cache belongs to
-        one set of weights."""
+        one set of weights.  With eval_merge the caches merge a flush's equal rows
+        (EvalCache(merge=True)); without eval_cache they hold no table."""
         reps = [net] if k <= 1 else [net.replica() if hasattr(net, "replica") else net for _ in range(k)]
-        if not self.eval_cache:
+        if not self.eval_cache and not self.eval_merge:
             fns = [(valued.PolicyNet if puct else valued.NetValue)(r) for r in reps]
             return fns[0] if k <= 1 else fns
         from . import evalcache, nets
         if not isinstance(net, nets.MfmaPolicyValueNetwork if puct else nets.MfmaValueNetwork):
-            raise ValueError("eval_cache needs the MFMA form of the network (its tower takes the row count from "
-                             "the device): a torch module cannot be cached")
+            raise ValueError("eval_cache / eval_merge need the MFMA form of the network (its tower takes the row "
+                             "count from the device): a torch module cannot be cached")
         logit_bytes = 2 * (64 * 64 if net.conv_head else net.w2.shape[1]) if puct else 0
         if [c.logit_bytes for c in self._caches] != [logit_bytes] * len(reps):
             row, dtype = (self.ps if puct else self.vs).LEAF
             key_bytes = int(np.prod(row)) * torch.empty(0, dtype=dtype).element_size()
-            self._caches = [evalcache.EvalCache(max(self.eval_cache // len(reps), _native.EVALCACHE_WAYS), key_bytes,
-                                                logit_bytes, self.dev) for _ in reps]
+            entries = max(self.eval_cache // len(reps), _native.EVALCACHE_WAYS) if self.eval_cache else 0
+            self._caches = [evalcache.EvalCache(entries, key_bytes, logit_bytes, self.dev, merge=self.eval_merge)
+                            for _ in reps]
         for c in self._caches:
             c.clear()
         fns = [(evalcache.CachedPolicy if puct else evalcache.CachedValue)(r, c) for r, c in zip(reps, self._caches)]
@@ -503,10 +519,11 @@ class _SelfPlayPool:
 
     def eval_cache_stats(self) -> dict:
         """The evaluation caches' counters summed over the streams' tables: {"probed", "hits",
-        "inserts", "dropped"} rows since the pool was built.  Synchronises."""
+        "inserts", "dropped"} rows since the pool was built, and with eval_merge "merged".
+        Synchronises."""
         if not self._caches:
-            raise ValueError("this pool was built without eval_cache")
-        out = dict.fromkeys(_native.EVALCACHE_STATS, 0)
+            raise ValueError("this pool was built without eval_cache or eval_merge")
+        out = dict.fromkeys(_native.EVALCACHE_MERGED_STATS if self.eval_merge else _native.EVALCACHE_STATS, 0)
         for c in self._caches:
             for k, v in c.stats().items():
                 out[k] += v
@@ -686,7 +703,7 @@ class C4SelfPlay(_SelfPlayPool):
                  net=None, puct_net=None, temperature: float = 1.0, puct_seed: int = 1, streams: int = 1,
                  record_policy: bool = False, pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
                  reuse_tree: bool = False, tree_nodes: int | None = None, fused_policy: bool = False,
-                 puct_args: dict | None = None, eval_cache: int = 0):
+                 puct_args: dict | None = None, eval_cache: int = 0, eval_merge: bool = False):
         """record_policy: every step()'s root visit counts go with the positions into the
         trajectories (TrajBatch.pi / policy_targets(7)), in every search mode.
         eval_cache (net= / puct_net=, MFMA networks): the entries of a device-resident evaluation
@@ -694,6 +711,10 @@ class C4SelfPlay(_SelfPlayPool):
         was evaluated before takes the stored value and logits and the network runs on the
         others alone.  The moves, visit counts and trajectories are those of the pool without
         it.  0 = off.
+        eval_merge (net= / puct_net=, MFMA networks): among the rows of one flush that miss the
+        cache, rows holding the same position are evaluated once and the others take a copy
+        (EvalCache(merge=True)).  With eval_cache=0 it works alone, without a table and at no
+        memory cost.  The pool plays what it plays without it.
         puct_args: C4PuctSearch's c_puct / dirichlet_alpha / dirichlet_eps, where its defaults
         are not wanted.
         fused_policy (needs record_policy): run(), run_pooled() (carry=True too) and drain()
@@ -705,6 +726,7 @@ class C4SelfPlay(_SelfPlayPool):
         (C4PuctSearch(reuse=True)) and adds sims - 1 visits to it; a tree holds up to
         `tree_nodes` nodes (default min(2 * sims, 65534)), and a search whose kept nodes leave
         no room for its own starts afresh.  start() and adopt() drop the kept trees."""
+        _check_eval_merge(eval_merge, net, puct_net)
         if reuse_tree:
             if puct_net is None:
                 raise ValueError("reuse_tree keeps the PUCT search's tree: it needs puct_net")
@@ -716,7 +738,7 @@ class C4SelfPlay(_SelfPlayPool):
                          torch.zeros(24, dtype=torch.uint8), self.MAX_LEN, games_cap, pi_slot_cap, pi_pool_cap,
                          record=record,
                          max_sims=(tree_nodes or min(2 * sims, 65534)) if reuse_tree else None,
-                         fused_policy=fused_policy, eval_cache=eval_cache)
+                         fused_policy=fused_policy, eval_cache=eval_cache, eval_merge=eval_merge)
         self.reuse_tree = bool(reuse_tree)
         self.record = record
         self.roots = torch.zeros((games, 3), dtype=torch.int64, device=self.dev)
@@ -884,10 +906,11 @@ class ChessSelfPlay(_SelfPlayPool):
                  puct_streams: int = 1, streams: int = 1, record_policy: bool = False,
                  pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
                  reuse_tree: bool = False, tree_nodes: int | None = None, fused_policy: bool = False,
-                 puct_args: dict | None = None, eval_cache: int = 0):
+                 puct_args: dict | None = None, eval_cache: int = 0, eval_merge: bool = False):
         """record_policy: every step()'s root visit counts go with the positions into the
         trajectories (TrajBatch.pi / policy_targets(4096)), in every search mode.
         eval_cache: as C4SelfPlay's (with the convolutional head an entry holds 8 KB of logits).
+        eval_merge: as C4SelfPlay's.
         puct_args: ChessPuctSearch's c_puct / dirichlet_alpha / dirichlet_eps, where its defaults
         are not wanted.
         fused_policy (needs record_policy): run() and run_pooled() record them as well — the
@@ -903,6 +926,7 @@ class ChessSelfPlay(_SelfPlayPool):
         adopt() drop the kept trees.  With record_policy a kept root's visit counts can exceed
         sims (a chess game has no fixed length, so no bound is refused here): a count beyond 16
         bits is recorded saturated and sets the recorder's ZC_TRAJ_PI_OVERFLOW bit 2."""
+        _check_eval_merge(eval_merge, net, puct_net)
         if reuse_tree and puct_net is None:
             raise ValueError("reuse_tree keeps the PUCT search's tree: it needs puct_net")
         init = _native.chess_from_fen(init_fen) if init_fen else _native.chess_init()
@@ -914,7 +938,7 @@ class ChessSelfPlay(_SelfPlayPool):
         super().__init__(games, sims, c, batch_size, seed, rank, device, temperature, record_policy,
                          init, max_len, games_cap, pi_slot_cap, pi_pool_cap,
                          max_sims=(tree_nodes or min(2 * sims, 65534)) if reuse_tree else None,
-                         fused_policy=fused_policy, eval_cache=eval_cache)
+                         fused_policy=fused_policy, eval_cache=eval_cache, eval_merge=eval_merge)
         self.reuse_tree = bool(reuse_tree)
         self.eng.chess_reserve()
         self.policy, self.freedom = int(policy), float(freedom)
