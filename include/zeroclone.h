@@ -922,6 +922,7 @@ int zc_arena_scatter_async(int32_t n, int32_t rows, int32_t game_rows, int64_t r
  * 16-bit hash tag in an entry's meta word only pre-filters.  ZC_EVALCACHE_WAYS ways per set;
  * the number of sets is the largest power of two with ways * sets <= entries.  Layout:
  *   [header 64 B][meta u32 x E][keys key_bytes x E][values f64 x E][logits round16(logit_bytes) x E]
+ * The header's first uint32 is the epoch (the number of commit launches since the clear); the rest is 0.
  * key_bytes: a multiple of 8 in [8, 512]; logit_bytes: even, >= 0.  The calls take the table's
  * three sizes every time (the block itself holds no description), keep no engine and record no
  * message: ZC_EINVAL names a violated condition below.  They only enqueue on hip_stream (no
