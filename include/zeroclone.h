@@ -867,8 +867,10 @@ int zc_train_batch_async(const zc_train_set *set, int32_t B, const int64_t *d_in
 /* zc_train_loss_async: value and policy loss of B >= 1 rows with their gradients, fp32
  * arithmetic throughout, the row maximum subtracted before exp.
  *   Lv = mean_b (v_b - z_b)^2                      d_grad_v[b] = 2 (v_b - z_b) / B
- *   a row is a policy row when its targets sum to more than 0; P = their number
- *   p_b = softmax of row b's logits over its legal moves (d_legal[b][0 .. d_n_legal[b]))
+ *   a row's legal slots are d_legal[b][0 .. n) with n = d_n_legal[b] clamped to [0, stride]
+ *   (a value outside that range is not an error), less the slots whose id names no logit
+ *   a row is a policy row when its legal slots' targets sum to more than 0; P = their number
+ *   p_b = softmax of row b's logits over its legal slots' moves
  *   Lp = 1/P sum over policy rows of -sum_j target_bj log p_bj          (0 when P = 0)
  *   d_grad_logits[b][index(j)] = (p_bj - target_bj) / P on policy rows, 0 everywhere else
  * d_logits [B][width], logits_dtype ZC_F32 / ZC_F16; d_grad_logits the same shape and type,

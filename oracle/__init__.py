@@ -256,9 +256,19 @@ def chess_from_fen(fen: str) -> ZccState:
     return s
 
 
+def chess_move_count(s: ZccState) -> int:
+    """The number of legal moves of any 64-byte board, beyond ZCC_MAX_MOVES too."""
+    out = (ZccMove * ZCC_MAX_MOVES)()
+    return _chess_lib().zcc_legal_moves(ctypes.byref(s), out)
+
+
 def chess_moves(s: ZccState):
+    """The ordered legal moves; OverflowError where there are more than ZCC_MAX_MOVES (no
+    position of a game: `chess_move_count` counts them)."""
     out = (ZccMove * ZCC_MAX_MOVES)()
     n = _chess_lib().zcc_legal_moves(ctypes.byref(s), out)
+    if n > ZCC_MAX_MOVES:
+        raise OverflowError(f"{n} legal moves, more than ZCC_MAX_MOVES = {ZCC_MAX_MOVES}")
     return [(m.fr, m.fc, m.tr, m.tc, m.value) for m in out[:n]]
 
 
@@ -278,7 +288,8 @@ def chess_draw(s: ZccState) -> bool:
 
 def chess_rollout(s: ZccState, mt: "MT"):
     """Value('random_rollout') on the chess rules from s on the stream mt (advanced):
-    (value, plies); value 2 = a history outgrew the restatement's ZCC_HIST."""
+    (value, plies); value 2 = a history outgrew the restatement's ZCC_HIST, 3 = a position with
+    more than ZCC_MAX_MOVES legal moves."""
     L = _chess_lib()
     L.zcc_rollout.argtypes = [ctypes.POINTER(ZccState), ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
     q = ctypes.c_int(0)
@@ -336,6 +347,8 @@ def chess_get_move(s: ZccState, mt: MT, sims: int, c: float, bs: int, policy: st
     best = L.zcc_get_move(ctypes.byref(chess_light(s)), ctypes.cast(ctypes.byref(mt.s), ctypes.c_void_p), sims, c, bs,
                           1 if policy == "immediate_value" else 0, float(freedom), fn, None, na,
                           mv, ctypes.byref(n))
+    if best == -2:
+        raise OverflowError(f"a searched position has more than ZCC_MAX_MOVES = {ZCC_MAX_MOVES} legal moves")
     moves = [(m.fr, m.fc, m.tr, m.tc, m.value) for m in mv[:n.value]]
     return best, moves, list(na[:n.value])
 

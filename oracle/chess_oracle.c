@@ -23,6 +23,7 @@
 
 #include <ctype.h>
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -203,8 +204,14 @@ void zcc_play(const zcc_state *s, const zcc_move *m, zcc_state *o) {
     if (tr == 7 && pc == 'p') b[tr * 8 + tc] = 'q';
 }
 
+/* Any 64 bytes are a board here: at most 64 pieces with at most 27 moves each (a queen's), so
+ * the pseudo-legal scratch cannot overflow.  `out` holds ZCC_MAX_MOVES: the first
+ * ZCC_MAX_MOVES legal moves are written and the TRUE count is returned, so a caller sees a
+ * count above its buffer (no position of a chess game has one) and must not read past it. */
+#define ZCC_MAX_PSEUDO (64 * 27)
+
 int zcc_legal_moves(const zcc_state *s, zcc_move *out) {
-    zcc_move ps[ZCC_MAX_MOVES];
+    zcc_move ps[ZCC_MAX_PSEUDO];
     const int np = pseudo_moves(s, ps);
     int n = 0;
     zcc_state t;
@@ -219,9 +226,22 @@ int zcc_legal_moves(const zcc_state *s, zcc_move *out) {
         zcc_play(&t, &ps[i], &t);
         int kr, kc;
         king_square(&t, s->turn, &kr, &kc);
-        if (!attacked(&t, s->turn, kr, kc)) out[n++] = ps[i];
+        if (!attacked(&t, s->turn, kr, kc)) {
+            if (n < ZCC_MAX_MOVES) out[n] = ps[i];
+            n++;
+        }
     }
     return n;
+}
+
+/* The internal callers' form: the list of a position of a game.  More than ZCC_MAX_MOVES legal
+ * moves: a message on stderr and -1 (the first ZCC_MAX_MOVES moves are in `out`). */
+static int game_moves(const zcc_state *s, zcc_move *out) {
+    const int n = zcc_legal_moves(s, out);
+    if (n <= ZCC_MAX_MOVES) return n;
+    fprintf(stderr, "chess_oracle: a position with %d legal moves (more than ZCC_MAX_MOVES = %d)\n", n,
+            ZCC_MAX_MOVES);
+    return -1;
 }
 
 static int in_check(const zcc_state *s) {
@@ -330,8 +350,9 @@ void zcc_state_to_tensor(const zcc_state *s, float *out) {
 uint64_t zcc_perft(const zcc_state *s, int depth) {
     if (depth == 0) return 1;
     zcc_move m[ZCC_MAX_MOVES];
-    const int n = zcc_legal_moves(s, m);
-    if (depth == 1) return (uint64_t)n;
+    if (depth == 1) return (uint64_t)zcc_legal_moves(s, m);
+    const int n = game_moves(s, m);
+    if (n < 0) return UINT64_MAX;   /* the list does not fit: no count below this position */
     uint64_t total = 0;
     zcc_state t;
     for (int i = 0; i < n; i++) {
@@ -372,13 +393,19 @@ static void light_to_state(const zcc_light *l, zcc_state *s) {
     s->overflow = 0;
 }
 
+static __thread int t_chess_overcap;   /* a node of the calling thread's search had more than ZCC_MAX_MOVES moves */
+
 static int cnode_new(cnode *P, int *np, const zcc_light *l, int parent, int pact) {
     cnode *x = &P[*np];
     static __thread zcc_state tmp;
     zcc_move buf[ZCC_MAX_MOVES];
     light_to_state(l, &tmp);
     x->s = *l;
-    x->n = zcc_legal_moves(&tmp, buf);
+    x->n = game_moves(&tmp, buf);
+    if (x->n < 0) {   /* the node keeps the moves that fit; zcc_get_move returns -2 */
+        x->n = ZCC_MAX_MOVES;
+        t_chess_overcap = 1;
+    }
     x->nu = x->n;
     x->mv = (zcc_move *)malloc(sizeof(zcc_move) * (size_t)(x->n ? x->n : 1));
     memcpy(x->mv, buf, sizeof(zcc_move) * (size_t)x->n);
@@ -500,6 +527,7 @@ int zcc_get_move(const zcc_light *root, void *rv, int sims, double c, int bs, in
     if (bs < 1) bs = 1;
     cnode *P = (cnode *)malloc(sizeof(cnode) * (size_t)(sims + 1));
     int np = 0;
+    t_chess_overcap = 0;
     cnode_new(P, &np, root, -1, -1);
     int *pend = (int *)malloc(sizeof(int) * (size_t)bs);
     double *vals = (double *)malloc(sizeof(double) * (size_t)bs);
@@ -549,7 +577,7 @@ int zcc_get_move(const zcc_light *root, void *rv, int sims, double c, int bs, in
     free(vals);
     free(pend);
     free(P);
-    return best;
+    return t_chess_overcap ? -2 : best;
 }
 
 /* Value('random_rollout') (value_functions.py:35-45) with the chess backend, on the CPython
@@ -573,7 +601,11 @@ int zcc_rollout(const zcc_state *start, void *rv, int *plies) {
             out = 0;
             break;
         }
-        const int n = zcc_legal_moves(s, m);
+        const int n = game_moves(s, m);
+        if (n < 0) {
+            out = 3;
+            break;
+        }
         const zcc_move mv = m[zco_randbelow(r, (uint32_t)n)];
         zcc_play(s, &mv, s);
         ++q;

@@ -34,7 +34,11 @@ typedef struct {
 
 void     zcc_init(zcc_state *s);                                       /* create_init_state */
 int      zcc_from_fen(const char *fen, zcc_state *s);                  /* state_from_fen    */
-int      zcc_legal_moves(const zcc_state *s, zcc_move *out);           /* get_legal_moves   */
+/* get_legal_moves of any 64-byte board: writes the first min(count, ZCC_MAX_MOVES) legal moves
+ * to out[ZCC_MAX_MOVES] and returns the TRUE count, which can exceed ZCC_MAX_MOVES on boards no
+ * game reaches.  The callers below that keep a list (perft below depth 1, get_move, rollout)
+ * report such a position on stderr and return UINT64_MAX / -2 / 3. */
+int      zcc_legal_moves(const zcc_state *s, zcc_move *out);
 void     zcc_play(const zcc_state *s, const zcc_move *m, zcc_state *o); /* play_move (o may be s) */
 int      zcc_check_win(const zcc_state *s);
 int      zcc_check_draw(const zcc_state *s);
@@ -48,7 +52,7 @@ double   zcc_crude_score(const zcc_light *l);
  * Policy('immediate_value', policy_freedom=freedom); vfn NULL = crude_chess_score, else
  * vfn(ctx, n, leaves, out) is Value.batch over the flush's pending leaves.  r is a
  * zco_mt* (c4_oracle.h).  Writes the root's moves and visits; returns the index of the
- * chosen root move (-1 if none). */
+ * chosen root move (-1 if none; -2 if a node had more than ZCC_MAX_MOVES legal moves). */
 typedef void (*zcc_value_fn)(void *ctx, int n, const zcc_light *leaves, double *out);
 int      zcc_get_move(const zcc_light *root, void *r, int sims, double c, int bs, int policy, double freedom,
                       zcc_value_fn vfn, void *ctx, int *root_na, zcc_move *root_moves, int *n_root);
@@ -60,7 +64,8 @@ int      zcc_selfplay_batch(int n, const zcc_light *roots, void *mts, int moves,
                             double freedom, int n_threads, uint64_t *out_expansions);
 
 /* Value('random_rollout') (value_functions.py:35-45) on the chess rules, stream r (zco_mt*):
- * -1 / +1 / 0 for the start's side to move, 2 if a history outgrew ZCC_HIST; *plies played. */
+ * -1 / +1 / 0 for the start's side to move, 2 if a history outgrew ZCC_HIST, 3 at a position
+ * with more than ZCC_MAX_MOVES legal moves; *plies played. */
 int      zcc_rollout(const zcc_state *s, void *r, int *plies);
 
 #ifdef __cplusplus

@@ -28,6 +28,8 @@ def _chess_lists(row: np.ndarray):
     from zeroclone_amd import _native
     raw = row.view(np.uint8)
     s = oracle.chess_state(raw[:64].tobytes().decode("latin-1"), int(raw[64]), int(raw[65]), int(raw[66]))
+    if oracle.chess_move_count(s) > STRIDE[CHESS]:   # status bit 2: no list
+        return oracle.chess_tensor(s), None
     moves = [_native.pack_chess_move(fr, fc, tr, tc, val) for fr, fc, tr, tc, val in oracle.chess_moves(s)]
     return oracle.chess_tensor(s), moves
 
@@ -53,6 +55,9 @@ def batch_ref(game: str, rows: np.ndarray, labels: np.ndarray, pi_off, pi, index
         else:
             assert not mirror, "a chess position has no mirror image"
             out["planes"][b], moves = _chess_lists(rows[i])
+            if moves is None:   # more legal moves than the row holds: n_legal 0, planes and label decoded
+                out["status"] |= 4
+                moves = []
         ent = [] if pi_off is None else [int(e) & 0xFFFFFFFF for e in pi[int(pi_off[i]):int(pi_off[i + 1])]]
         total = np.float32(sum(e >> 16 for e in ent))
         key = (lambda m: m) if game == C4 else (lambda m: m & 0xFFF)   # chess: by from / to
@@ -75,7 +80,10 @@ def batch_ref(game: str, rows: np.ndarray, labels: np.ndarray, pi_off, pi, index
 
 def loss_ref(v, logits, z, legal, n_legal, target):
     """zc_train_loss_async in fp64: (Lv, Lp, grad_v [B], grad_logits [B, width] or None).
-    logits None: a value-only model."""
+    logits None: a value-only model.  The header's rules for rows no minibatch holds: n_legal is
+    clamped to [0, stride]; a width-7 id above 6 names no logit and is ignored, in the softmax and
+    in the target sum alike; a policy row is one whose legal slots' targets (the slots below the
+    clamped n_legal whose id is not ignored) sum to more than 0."""
     v, z = np.asarray(v, np.float64).reshape(-1), np.asarray(z, np.float64)
     B = len(v)
     Lv = float(np.mean((v - z) ** 2))
@@ -85,17 +93,49 @@ def loss_ref(v, logits, z, legal, n_legal, target):
     x = np.asarray(logits, np.float64)
     width = x.shape[1]
     t = np.asarray(target, np.float64)
-    policy = [b for b in range(B) if t[b, :max(int(n_legal[b]), 0)].sum() > 0]
+    stride = t.shape[1]
+
+    def slots(b):
+        """The legal slots of row b that name a logit, and those logits' indices."""
+        n = min(max(int(n_legal[b]), 0), stride)
+        idx = logit_index(np.asarray(legal[b, :n]), width)
+        keep = np.flatnonzero(idx < width)
+        return keep, idx[keep]
+    policy = [b for b in range(B) if t[b, slots(b)[0]].sum() > 0]
     P = len(policy)
     grad = np.zeros_like(x)
     Lp = 0.0
     for b in policy:
-        n = int(n_legal[b])
-        idx = logit_index(np.asarray(legal[b, :n]), width)
+        at, idx = slots(b)
         xs = x[b, idx]
         m = xs.max()
         e = np.exp(xs - m)
         logp = (xs - m) - np.log(e.sum())
-        Lp += -(t[b, :n] * logp).sum() / P
-        grad[b, idx] = (e / e.sum() - t[b, :n]) / P
+        Lp += -(t[b, at] * logp).sum() / P
+        grad[b, idx] = (e / e.sum() - t[b, at]) / P
     return Lv, Lp, grad_v, grad
+
+
+def hand_made_rule_rows(seed=21):
+    """Eight width-7, stride-7 rows that no minibatch holds, one per rule of zc_train_loss_async's
+    header: rows 0-2 carry an id of 7, 63 and 0xFFFF in a legal slot with a target (ignored: row
+    0's list also holds column 6, which a clamp would count twice); row 3 has targets past n_legal
+    only and row 5 on an ignored id only (no policy rows); row 6 has n_legal -3 (no legal slot,
+    no policy row), row 7 n_legal stride + 5 (all 7 slots).  The targets are dyadic and sum to 1
+    over the slots that count, where (p - t) / P is also autograd's gradient."""
+    g = np.random.default_rng(seed)
+    nl = np.asarray([4, 3, 5, 2, 7, 3, 2, 4], np.int32)
+    legal, target = np.zeros((8, 7), np.uint16), np.zeros((8, 7), np.float32)
+    for b in range(8):
+        legal[b, :nl[b]] = np.sort(g.choice(7, nl[b], replace=False))
+    legal[0, :4], target[0, :4] = [2, 7, 5, 6], [0.25, 0.25, 0.25, 0.5]
+    legal[1, 1], target[1, :3] = 63, [0.5, 0.5, 0.5]
+    legal[2, 1], target[2, :5] = 0xFFFF, [0.25] * 5
+    target[3, 4] = 0.5
+    target[4, :7] = [0.125, 0.125, 0.25, 0, 0.25, 0.125, 0.125]
+    legal[5, :3], target[5, 1] = [1, 9, 4], 1.0
+    target[6, :2] = [0.5, 0.5]
+    nl[6], nl[7] = -3, 12
+    legal[7], target[7] = np.arange(7), [0.125] * 6 + [0.25]
+    return dict(v=np.tanh(g.normal(size=8)), z=g.integers(-1, 2, 8).astype(np.float32),
+                logits=g.normal(size=(8, 7)) * 2.0, legal=legal, n_legal=nl, target=target)

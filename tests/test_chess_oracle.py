@@ -118,3 +118,82 @@ def test_chess_selfplay_batch_equals_get_move_play_judge():
             if not oracle.chess_moves(s) or oracle.chess_draw(s):
                 s = oracle.chess_init()
         assert ref[i].state() == mts[i].state(), i
+
+
+# A ring of queens round an empty centre: more legal moves than any list holds (no game reaches it).
+QUEEN_RING = "KQQQQQQQQ      QQ      QQ      QQ      QQ      QQ      QQQQQQQQk"
+WIDEST = "R6R/3Q4/1Q4Q1/4Q3/2Q4Q/Q4Q2/pp1Q4/kBNN1KB1 w - - 0 1"   # 218 legal moves, the most of a legal position
+
+
+def _pseudo_moves(board, t):
+    """(from, to) of side t's pseudo-legal queen, rook, bishop, knight and king moves on `board`
+    (no pawns): every target that is empty or an enemy piece other than the king."""
+    mine = (lambda x: x.isupper()) if t == 0 else (lambda x: x.islower())
+    diag, orth = [(-1, -1), (-1, 1), (1, -1), (1, 1)], [(-1, 0), (1, 0), (0, -1), (0, 1)]
+    knight = [(-2, -1), (-2, 1), (-1, -2), (-1, 2), (1, -2), (1, 2), (2, -1), (2, 1)]
+    out = []
+    for s, x in enumerate(board):
+        if x == " " or not mine(x):
+            continue
+        u = x.upper()
+        for dr, dc in {"B": diag, "R": orth, "Q": diag + orth, "K": diag + orth, "N": knight}[u]:
+            r, c = s // 8 + dr, s % 8 + dc
+            while 0 <= r < 8 and 0 <= c < 8:
+                y = board[r * 8 + c]
+                if y == " " or (not mine(y) and y.upper() != "K"):
+                    out.append((s, r * 8 + c))
+                if y != " " or u in "KN":
+                    break
+                r, c = r + dr, c + dc
+    return out
+
+
+def _king_attacked(board, t):
+    """Is side t's king attacked on `board`?  A king is never a target, so a queen of its colour
+    stands in for it and the other side's pseudo-legal targets are asked for its square."""
+    k = board.index("K" if t == 0 else "k")
+    probe = board[:k] + ("Q" if t == 0 else "q") + board[k + 1:]
+    return any(to == k for _, to in _pseudo_moves(probe, 1 - t))
+
+
+def test_more_moves_than_a_list_holds_raise():
+    """A board with more legal moves than ZCC_MAX_MOVES: `chess_moves` refuses, and so does every
+    caller that keeps a list (get_move: OverflowError, perft below depth 1: 2^64 - 1, the
+    rollout: 3); the terminal tests, which only ask whether a move exists, answer."""
+    s = oracle.chess_state(QUEEN_RING)
+    with pytest.raises(OverflowError, match="277"):
+        oracle.chess_moves(s)
+    with pytest.raises(OverflowError):
+        oracle.chess_get_move(s, oracle.MT(1), 8, 1.4, 4)
+    assert oracle.chess_perft(s, 1) == 277 and oracle.chess_perft(s, 2) == 2 ** 64 - 1
+    assert oracle.chess_rollout(s, oracle.MT(1)) == (3, 0)
+    assert not oracle.chess_win(s) and not oracle.chess_draw(s)
+
+
+def test_more_moves_than_a_list_holds_are_counted():
+    """The true count: the pseudo-legal moves less those after which the mover's king is attacked
+    (the oracle's `chess_play`, then the attack read off the board)."""
+    from test_gpu_chess import _count_runs
+    s = oracle.chess_state(QUEEN_RING)
+    pseudo = _pseudo_moves(QUEEN_RING, 0)
+    assert len(pseudo) == _count_runs(list(QUEEN_RING), 0)[1] == 277
+    rejected = 0
+    for f, t in pseudo:
+        after = oracle.chess_play(s, (f // 8, f % 8, t // 8, t % 8, 0.0))
+        rejected += _king_attacked(bytes(after.board).decode("latin-1"), 0)
+    n = oracle.chess_move_count(s)
+    assert n > oracle.ZCC_MAX_MOVES and n == len(pseudo) - rejected == 277
+    # a pinned queen: the count drops by the moves that leave the pin's line
+    pinned = "KQr" + QUEEN_RING[3:]
+    m = oracle.chess_move_count(oracle.chess_state(pinned))
+    want = sum(not _king_attacked(bytes(oracle.chess_play(oracle.chess_state(pinned), (f // 8, f % 8, t // 8, t % 8, 0.0))
+                                       .board).decode("latin-1"), 0) for f, t in _pseudo_moves(pinned, 0))
+    assert m == want < len(_pseudo_moves(pinned, 0))
+
+
+def test_the_widest_legal_position_still_returns_its_list():
+    s = oracle.chess_from_fen(WIDEST)
+    moves = oracle.chess_moves(s)
+    assert len(moves) == oracle.chess_move_count(s) == 218
+    assert len({m[:4] for m in moves}) == 218
+    assert oracle.chess_perft(s, 1) == 218

@@ -343,6 +343,116 @@ def _count_runs(b, t):
     return runs, moves
 
 
+# Boards at and above the generator's capacity of 256 legal moves (white to move; found by a
+# hill-climb from the ring of queens, one queen removed, added or moved at a time).  Name:
+# (board, legal moves, runs of the run-parallel generator).  The boards without a white king go
+# through the byte view, whose generator is always the per-piece one; every pseudo-legal move of
+# theirs is legal (find_king gives -1, -1).
+QUEEN_RING = "KQQQQQQQQ      QQ      QQ      QQ      QQ      QQ      QQQQQQQQk"
+CAPACITY_BOARDS = {
+    "218": ("KQQQ QQQQ  Q   Q   Q    Q   Q  QQ      Q   Q      QQ    QQQQQ Qk", 218, 80),
+    "230": ("KQQQQQQ Q      Q Q Q   QQ   Q  QQ      QQ  Q    Q Q     QQQ Q Qk", 230, 90),
+    "256": ("KQQQQQQQQ      Q       QQ      QQ      QQ  Q Q QQ Q    QQQQQQQQk", 256, 82),
+    "257": ("KQQQQQQQQ      Q       QQ      QQ      QQ  Q   QQ Q    QQQQQQQQk", 257, 74),
+    "ring": (QUEEN_RING, 277, 67),
+    "200, 129 runs": ("KQ  Q QQ   Q  Q QQQ Q Q   Q Q Q Q Q    Q  Q QQ  Q Q   QQQ Q  Q k", 200, 129),
+    "227, 129 runs": ("K Q Q Q   Q Q Q QQ     Q   Q Q QQQ   Q Q   Q Q QQ Q    QQpQbQQQk", 227, 129),
+    "256, no king": ("QQQQQQQQQ      Q       QQ      QQ      QQ Q  Q Q Q     Q QQQQ Qk", 256, 81),
+    "257, no king": (" QQQQQQQQ      QQ      QQ      QQ      QQ Q    QQ  Q  QQQQQQQ Qk", 257, 76),
+    "ring, no king": ("Q" + QUEEN_RING[1:], 282, 67),
+}
+ORDINARY = ["rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1",
+            "r3k2r/p1ppqpb1/bn2pnp1/3PN3/1p2P3/2N2Q1p/PPPBBPPP/R3K2R w KQkq - 0 1",
+            "R6R/3Q4/1Q4Q1/4Q3/2Q4Q/Q4Q2/pp1Q4/kBNN1KB1 w - - 0 1",
+            "4k3/8/8/8/8/8/4r3/4K3 w - - 0 1"]
+
+
+def _capacity_positions():
+    """(name, oracle state) with every capacity board, for white and (colours swapped, the board
+    turned upside down) for black, between ordinary positions."""
+    import oracle
+    out = []
+    k = 0
+    for name, (b, n, runs) in CAPACITY_BOARDS.items():
+        assert _count_runs(list(b), 0)[0] == runs, name
+        for t in (0, 1):
+            out.append(("ordinary", oracle.chess_from_fen(ORDINARY[k % len(ORDINARY)])))
+            k += 1
+            bb = b if t == 0 else "".join(b[(7 - i // 8) * 8 + i % 8] for i in range(64)).swapcase()
+            s = oracle.chess_state(bb, t, 3, 0)
+            assert oracle.chess_move_count(s) == n, (name, t)
+            out.append((name, s))
+    out.append(("ordinary", oracle.chess_from_fen(ORDINARY[0])))
+    return out
+
+
+def _states(sts):
+    from zeroclone_amd._native import CHESS_STATE_DTYPE
+    a = np.zeros(len(sts), CHESS_STATE_DTYPE)
+    for i, s in enumerate(sts):
+        a[i]["board"] = np.frombuffer(bytes(s.board), np.uint8)
+        a[i]["turn"], a[i]["fifty"], a[i]["castle"] = s.turn, s.fifty, s.castle
+    return a
+
+
+def test_the_generator_at_and_above_its_capacity(eng):
+    """256 legal moves fit, 257 are refused with a count of -1 and nothing written: through
+    zc_chess_legal_moves_async, zc_chess_children_async and the lazy-node probe, for the
+    run-parallel generator (at most 128 runs), the per-piece one above 128 runs (below the
+    capacity: no board with more than 128 runs and more than 256 legal moves was found) and the
+    byte view's, the over-capacity positions between ordinary ones in one launch.  (The refusal of
+    more than 512 pseudo-legal moves stays unexecuted: the search's best board had 282.)  Every output
+    is pre-filled: an over-capacity position's own rows keep the fill, and so do the slots past a
+    neighbour's list."""
+    import oracle
+    pos = _capacity_positions()
+    n = len(pos)
+    want_n = [oracle.chess_move_count(s) for _, s in pos]
+    assert {256, 257, 277} <= set(want_n) and any(192 < w < 256 for w in want_n)
+    st = dev(_states([s for _, s in pos]))
+    FILL = 0x5A5A
+    moves = torch.full((n, MAXM), FILL, dtype=torch.int16, device="cuda")
+    counts = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+    kids = torch.full((n * MAXM, 72), 0xA5, dtype=torch.uint8, device="cuda")
+    kmoves = torch.full((n, MAXM), FILL, dtype=torch.int16, device="cuda")
+    kcounts = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+    kids2 = torch.full((n * MAXM, 72), 0xA5, dtype=torch.uint8, device="cuda")
+    k2counts = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+    probe = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+    flags = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+    eng.chess_legal_moves_async(n, st.data_ptr(), moves.data_ptr(), counts.data_ptr())
+    eng.chess_children_async(n, st.data_ptr(), kids.data_ptr(), kmoves.data_ptr(), kcounts.data_ptr())
+    eng.chess_children_async(n, st.data_ptr(), kids2.data_ptr(), 0, k2counts.data_ptr())
+    eng.debug_chess_probe_async(n, st.data_ptr(), probe.data_ptr())
+    eng.chess_terminal_async(n, st.data_ptr(), flags.data_ptr())
+    torch.cuda.synchronize()
+    moves, kmoves = moves.cpu().numpy().view(np.uint16), kmoves.cpu().numpy().view(np.uint16)
+    counts, kcounts, k2counts = counts.cpu().numpy(), kcounts.cpu().numpy(), k2counts.cpu().numpy()
+    assert torch.equal(kids, kids2)
+    kids = kids.cpu().numpy().reshape(n, MAXM, 72)
+    probe, flags = probe.cpu().numpy(), flags.cpu().numpy()
+    for i, (name, s) in enumerate(pos):
+        if want_n[i] > MAXM:
+            assert counts[i] == kcounts[i] == k2counts[i] == -1, (i, name)
+            assert (moves[i] == FILL).all() and (kmoves[i] == FILL).all() and (kids[i] == 0xA5).all(), (i, name)
+            assert probe[i] in (-1, -2) and flags[i] == 8, (i, name, probe[i], flags[i])
+            if "no king" in name:   # no bit view: the probe generates the list
+                assert probe[i] == -1, (i, name)
+            continue
+        want = oracle.chess_moves(s)
+        k = len(want)
+        assert counts[i] == kcounts[i] == k2counts[i] == k, (i, name)
+        assert [decode(m) for m in moves[i, :k]] == [list(m) for m in want], (i, name)
+        assert (moves[i, :k] == kmoves[i, :k]).all(), (i, name)
+        assert (moves[i, k:] == FILL).all() and (kmoves[i, k:] == FILL).all() and (kids[i, k:] == 0xA5).all(), (i, name)
+        assert probe[i] in (-2, k) and (k > 0 or probe[i] == 0), (i, name, probe[i])
+        assert flags[i] == 0, (i, name, flags[i])   # every position here has a move and a young fifty counter
+        for j, m in enumerate(want):
+            o = oracle.chess_play(s, m)
+            assert bytes(kids[i, j, :64]) == bytes(o.board), (i, name, j)
+            assert kids[i, j, 64:67].tolist() == [o.turn, o.fifty, o.castle] and not kids[i, j, 67:].any(), (i, name, j)
+
+
 def test_crowded_boards_match_oracle(eng):
     """The generator's fallback above 128 runs on crowded boards (and the run-parallel
     generator on their thinned-out twins): move lists vs the oracle."""
@@ -350,19 +460,26 @@ def test_crowded_boards_match_oracle(eng):
     from zeroclone_amd._native import CHESS_STATE_DTYPE
     pos, stats = _dense_boards()
     assert sum(r > 128 for r, _ in stats) >= 100 and sum(r <= 128 for r, _ in stats) >= 100
+    for b, _, _ in CAPACITY_BOARDS.values():   # and the boards at and above 256 legal moves
+        pos.append((b.encode("latin-1"), 0, 0, 0))
+        stats.append(_count_runs(list(b), 0))
     assert max(m for _, m in stats) <= 512
     a = np.zeros(len(pos), CHESS_STATE_DTYPE)
     for i, (b, t, f, c) in enumerate(pos):
         a[i]["board"] = np.frombuffer(b, np.uint8)
         a[i]["turn"], a[i]["fifty"], a[i]["castle"] = t, f, c
     moves, counts = legal(eng, dev(a))
+    over = 0
     for i, (b, t, fifty, c) in enumerate(pos):
-        want = [list(m) for m in oracle.chess_moves(oracle.chess_state(b.decode("latin-1"), t, fifty, c))]
-        if len(want) > MAXM:
+        s = oracle.chess_state(b.decode("latin-1"), t, fifty, c)
+        if oracle.chess_move_count(s) > MAXM:
             assert counts[i] == -1, (i, b)
+            over += 1
             continue
+        want = [list(m) for m in oracle.chess_moves(s)]
         assert counts[i] == len(want), (i, b, stats[i])
         assert [decode(m) for m in moves[i, :counts[i]]] == want, (i, b, stats[i])
+    assert over == 4
 
 
 PROBE_FENS = [

@@ -65,6 +65,31 @@ def test_loss_ref_matches_autograd_of_masked_log_softmax(width, stride, n_legal,
     assert not gl[~mask].any() and not x.grad.numpy()[~mask].any()
 
 
+def test_loss_torch_follows_the_headers_rules_for_hand_made_rows():
+    """Where `loss_torch` once departed from zc_train_loss_async's definition (rows that
+    `minibatch` never makes): a width-7 id above 6 is ignored, not read as column 6; a policy row
+    is decided by the targets of its legal slots, not by the whole target row; n_legal outside
+    [0, stride] is clamped."""
+    c = learner_ref.hand_made_rule_rows()
+    legal, target, nl = c["legal"], c["target"], c["n_legal"]
+    Lv, Lp, gv, gl = learner_ref.loss_ref(c["v"], c["logits"], c["z"], legal, nl, target)
+    v = torch.tensor(c["v"], dtype=torch.float64, requires_grad=True)
+    x = torch.tensor(c["logits"], dtype=torch.float64, requires_grad=True)
+    tv, tp = learner.loss_torch(v, x, _mb(c, 7))
+    (tv + tp).backward()
+    assert abs(tv.item() - Lv) <= 1e-12 and abs(tp.item() - Lp) <= 1e-12
+    np.testing.assert_allclose(x.grad.numpy(), gl, rtol=0, atol=1e-12)
+    np.testing.assert_allclose(v.grad.numpy(), gv, rtol=0, atol=1e-12)
+    # the spec itself: rows 3, 5 and 6 are no policy rows, the ignored ids' columns get no gradient
+    assert not gl[[3, 5, 6]].any() and gl[7].all() and gl[0, 6] != 0
+    assert not gl[0, [0, 1, 3, 4]].any() and np.count_nonzero(gl[1]) == 2 and np.count_nonzero(gl[2]) == 4
+    # by hand, row 0 alone: the softmax over columns 2, 5, 6 and the targets on them
+    one = learner_ref.loss_ref(c["v"][:1], c["logits"][:1], c["z"][:1], legal[:1], nl[:1], target[:1])
+    xs = c["logits"][0, [2, 5, 6]]
+    logp = xs - np.log(np.exp(xs).sum())
+    assert abs(one[1] + (np.asarray([0.25, 0.25, 0.5]) * logp).sum()) <= 1e-12
+
+
 def test_loss_ref_value_only():
     c = _loss_case(5, 6, 7, 7, [7] * 6, set())
     Lv, Lp, gv, gl = learner_ref.loss_ref(c["v"], None, c["z"], None, None, None)
@@ -224,6 +249,80 @@ def test_train_policy_network_on_cpu_learns_and_repeats():
     assert out[0].epoch_losses == out[1].epoch_losses
     assert out[0].epoch_losses[-1] < out[0].epoch_losses[0]
     assert out[0].policy_losses[0] > 0
+
+
+# `train` of the commit before the status of every batch was kept, on the setup above (8 CPU threads)
+EPOCH_LOSSES_BEFORE = [2.979426066080729, 2.6508039633433023, 2.5597496032714844]
+
+
+def _train_checking_the_last_batch_only(model, ts, epochs, lr, batch_size, generator):
+    """`learner.train` as it stood (mirror=True, shuffle=True, CPU): the same calls in the same
+    order, the status word of the epoch's last batch alone."""
+    opt = torch.optim.Adam(model.parameters(), lr=lr)
+    n, losses = len(ts), []
+    for _ in range(epochs):
+        model.train()
+        order = torch.randperm(n, generator=generator)
+        running = torch.zeros((), dtype=torch.float64)
+        for lo in range(0, n, batch_size):
+            idx = order[lo:lo + batch_size]
+            flip = torch.rand(idx.shape[0], generator=generator) < 0.5
+            mb = learner.minibatch(ts, idx, flip)
+            opt.zero_grad()
+            v, logits = model(mb.planes)
+            Lv, Lp = learner.policy_value_loss(v, logits, mb)
+            loss = Lv + Lp
+            loss.backward()
+            opt.step()
+            running = running + loss.detach().double() * idx.shape[0]
+        mb.check()
+        losses.append(float(running) / n)
+    return losses
+
+
+def test_train_on_a_clean_set_is_unchanged_by_keeping_every_status():
+    """Exactly the losses of the loop that checked the last batch only, run here; and the values
+    that loop gave when the change was made, within the spread that the number of CPU threads
+    alone makes in them (1 thread: 2.9794263, 8 threads: 2.9794261: below 1e-7 relative)."""
+    from zeroclone_amd.nets import PolicyValueNetwork
+    ts = _c4_set(13, 96)
+    net = lambda: PolicyValueNetwork(channels=8, blocks=1, in_planes=2, board=(6, 7), n_logits=7)  # noqa: E731
+    torch.manual_seed(3)
+    got = learner.train(net(), ts, epochs=3, lr=3e-3, batch_size=32, generator=torch.Generator().manual_seed(7),
+                        mirror=True, device="cpu")
+    torch.manual_seed(3)
+    before = _train_checking_the_last_batch_only(net(), ts, 3, 3e-3, 32, torch.Generator().manual_seed(7))
+    assert got.epoch_losses == before
+    np.testing.assert_allclose(got.epoch_losses, EPOCH_LOSSES_BEFORE, rtol=1.3e-6, atol=0)
+
+
+def _set_with_an_entry_on_a_full_column(n=64):
+    """A clean set but for row 0, whose first entry names a full column."""
+    ts = _c4_set(17, n)
+    rows = ts.rows.clone()
+    rows[0, 0] |= 0x3F << 14          # column 2 full
+    rows[0, 1] &= ~(0x3F << 14)
+    rows[0, 0] &= ~(0x3F << 28)
+    rows[0, 1] &= ~(0x3F << 28)       # column 4 empty
+    cnt = (ts.pi_off[1:] - ts.pi_off[:-1]).tolist()
+    pi = torch.cat([torch.tensor([2 | 5 << 16, 4 | 3 << 16], dtype=torch.int32), ts.pi[cnt[0]:]])
+    off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(torch.tensor([2] + cnt[1:]), 0)])
+    return TrainingSet("c4", rows, ts.labels, off, pi)
+
+
+def test_train_reports_an_illegal_entry_of_any_batch():
+    """The status word of every batch of the epoch, not the last one's alone: the bad row is in the
+    first of two batches."""
+    from zeroclone_amd.nets import PolicyValueNetwork
+    ts = _set_with_an_entry_on_a_full_column()
+    assert int(learner.minibatch(ts, torch.arange(4)).status) == 1
+    assert int(learner.minibatch(ts, torch.arange(32, 64)).status) == 0
+    torch.manual_seed(3)
+    model = PolicyValueNetwork(channels=8, blocks=1, in_planes=2, board=(6, 7), n_logits=7)
+    with pytest.raises(RuntimeError, match="not legal"):
+        learner.train(model, ts, epochs=1, lr=3e-3, batch_size=32, shuffle=False, device="cpu")
+    good = ts.select(torch.arange(1, 64))
+    learner.train(model, good, epochs=1, lr=3e-3, batch_size=32, shuffle=False, device="cpu")
 
 
 class _StubPool:

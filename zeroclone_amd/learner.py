@@ -135,6 +135,17 @@ class ReplaySet:
         return TrainingSet.cat([old.select(idx), new])
 
 
+def _raise_status(status: torch.Tensor):
+    """Raises what a status word of zc_train_batch_async (or the OR of several) says: one device read."""
+    st = int(status.item())
+    if st & 1:
+        raise RuntimeError("a policy entry names a move that is not legal in its position (the entry was dropped)")
+    if st & 2:
+        raise RuntimeError("a minibatch index lies outside the training set")
+    if st & 4:
+        raise RuntimeError(f"a chess position has more than {_native.CHESS_MAX_MOVES} legal moves")
+
+
 @dataclass
 class Minibatch:
     """One decoded minibatch (zc_train_batch_async): planes [B, C, H, W], z [B] float, legal
@@ -150,13 +161,7 @@ class Minibatch:
 
     def check(self):
         """Raises what the batch kernel flagged (one device read)."""
-        st = int(self.status.item())
-        if st & 1:
-            raise RuntimeError("a policy entry names a move that is not legal in its position (the entry was dropped)")
-        if st & 2:
-            raise RuntimeError("a minibatch index lies outside the training set")
-        if st & 4:
-            raise RuntimeError(f"a chess position has more than {_native.CHESS_MAX_MOVES} legal moves")
+        _raise_status(self.status)
 
 
 def _c4_planes_torch(rows: torch.Tensor, mirror: torch.Tensor | None) -> tuple[torch.Tensor, torch.Tensor]:
@@ -276,18 +281,22 @@ def logit_index(legal: torch.Tensor, width: int) -> torch.Tensor:
 def loss_torch(v: torch.Tensor, logits: torch.Tensor | None, mb: Minibatch):
     """(Lv, Lp) by torch ops and autograd, the loss's definition (zc_train_loss_async) in the
     tensors' own precision: the masked log_softmax formulation.  The CPU path of
-    `policy_value_loss`, and what the kernel is compared against."""
+    `policy_value_loss`, and what the kernel is compared against.  The header's rules for rows
+    `minibatch` never makes: n_legal outside [0, stride] is clamped, a width-7 id above 6 is in
+    neither the softmax nor the target sum, and a policy row is one whose legal slots' targets
+    sum to more than 0."""
     v = v.reshape(-1)
     Lv = torch.nn.functional.mse_loss(v, mb.z.to(v.dtype))
     if logits is None:
         return Lv, torch.zeros((), dtype=v.dtype, device=v.device)
     B, stride = mb.legal.shape
-    live = torch.arange(stride, device=v.device).view(1, -1) < mb.n_legal.view(-1, 1)
-    x = logits.gather(1, logit_index(mb.legal, logits.shape[1]).clamp(max=logits.shape[1] - 1))
+    at = logit_index(mb.legal, logits.shape[1])
+    live = (torch.arange(stride, device=v.device).view(1, -1) < mb.n_legal.view(-1, 1)) & (at < logits.shape[1])
+    x = logits.gather(1, at.clamp(max=logits.shape[1] - 1))
     # (a row without legal moves keeps its slots: a softmax over nothing is NaN, in backward too)
-    lsm = torch.log_softmax(x.masked_fill(~(live | (mb.n_legal.view(-1, 1) <= 0)), float("-inf")), dim=1)
+    lsm = torch.log_softmax(x.masked_fill(~(live | ~live.any(1, keepdim=True)), float("-inf")), dim=1)
     t = mb.target.to(x.dtype)
-    rows = t.sum(1) > 0
+    rows = torch.where(live, t, torch.zeros_like(t)).sum(1) > 0
     P = int(rows.sum())
     if P == 0:
         return Lv, (logits * 0).sum()
@@ -388,10 +397,12 @@ def train(model, ts: TrainingSet, epochs: int = 10, lr: float = 1e-3, batch_size
         model.train()
         order = torch.randperm(n, generator=generator) if shuffle else torch.arange(n)
         running = running_v = running_p = torch.zeros((), dtype=torch.float64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)   # every batch's status word, OR-ed on the device
         for lo in range(0, n, batch_size):
             idx = order[lo:lo + batch_size]
             flip = (torch.rand(idx.shape[0], generator=generator) < 0.5) if mirror else None
             mb = minibatch(ts, idx, flip)
+            status |= mb.status
             opt.zero_grad()
             out = model(mb.planes)
             v, logits = out if isinstance(out, tuple) else (out, None)
@@ -403,7 +414,7 @@ def train(model, ts: TrainingSet, epochs: int = 10, lr: float = 1e-3, batch_size
             running = running + last.double() * idx.shape[0]
             running_v = running_v + Lv.detach().double() * idx.shape[0]
             running_p = running_p + Lp.detach().double() * idx.shape[0]
-        mb.check()
+        _raise_status(status)
         res.epoch_losses.append(float(running) / n)
         res.value_losses.append(float(running_v) / n)
         res.policy_losses.append(float(running_p) / n)
