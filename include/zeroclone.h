@@ -618,6 +618,11 @@ int zc_debug_c4_puct_tree(zc_engine *eng, int32_t game, int32_t max_nodes, void 
  *   zc_net_value_head_async: mean over pixels -> dot(fc_w[128]) + fc_b -> tanh, as fp64
  *     values[n] (the input of zc_*_ext_backup).  d_act = [n][hw][128] fp16 (exactly 128
  *     channels), 16-byte aligned (ZC_EINVAL otherwise).
+ * Non-finite values propagate to the outputs of every zc_net_* launch: a sum past the fp16
+ * range is stored as the infinity, every ReLU keeps a NaN (and stores 0 for -inf), so a NaN
+ * input, weight or bias, or an overflowed activation's inf - inf, reaches the activation, the
+ * values and the policy outputs of its board — and of no other board.  The PUCT backups end such
+ * a game with ZC_STATUS_INTERNAL.
  * Device pointers, enqueued on hip_stream (NULL = null stream); no engine needed. */
 int zc_net_conv3x3_async(int32_t n_boards, int32_t h, int32_t w, int32_t cin, const void *d_in, const void *d_weight,
                          const float *d_bias, const void *d_residual, void *d_out, int32_t relu, void *hip_stream);

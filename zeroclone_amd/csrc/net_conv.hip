@@ -58,6 +58,18 @@ typedef float f4x __attribute__((ext_vector_type(4)));
 constexpr int kCout = 128;
 constexpr int kTilePix = 256;
 
+// Every epilogue's ReLU.  fmaxf returns its other operand for a NaN, so a bare fmaxf(v, 0)
+// would turn a NaN (an overflowed activation's inf - inf in the next layer, a NaN weight or
+// bias of a diverged network) into 0 and the searches would play on with finite, meaningless
+// values: the NaN must reach the values and logits, where the backups stop the game.  This
+// is IEEE 754-2019 maximum (NaN if either operand is), one v_maximum3_f32 on gfx950 where the
+// select-around-fmaxf form took four instructions and 2.5 % of the fused tower
+// (profiles/ab_relu_nan.log).  Every other input gives fmaxf's value.  Bits: the two differ
+// at most on v = -0 (maximum orders -0 below +0), which no epilogue can produce — an MFMA
+// accumulator starts at +0 and a round-to-nearest sum is -0 only when every term is, so
+// acc + bias (+ residual) is never -0.
+__device__ __forceinline__ float relu_nan(float v) { return __builtin_elementwise_maximum(v, 0.0f); }
+
 template <int H, int W, int BPW, int CIN>
 __global__ __launch_bounds__(256) void conv3x3_kernel(int nboards, const _Float16 *__restrict__ in,
                                                       const _Float16 *__restrict__ wt, const float *__restrict__ bias,
@@ -223,10 +235,10 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(int nboards, const _Float1
                     v3 += (float)rv[t][m][g][3];
                 }
                 if (relu) {
-                    v0 = fmaxf(v0, 0.0f);
-                    v1 = fmaxf(v1, 0.0f);
-                    v2 = fmaxf(v2, 0.0f);
-                    v3 = fmaxf(v3, 0.0f);
+                    v0 = relu_nan(v0);
+                    v1 = relu_nan(v1);
+                    v2 = relu_nan(v2);
+                    v3 = relu_nan(v3);
                 }
                 h4 o;
                 o[0] = (_Float16)v0;
@@ -410,7 +422,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 if (res) v[e] += (float)rv8[e];
-                if (relu) v[e] = fmaxf(v[e], 0.0f);
+                if (relu) v[e] = relu_nan(v[e]);
                 ov[e] = (_Float16)v[e];
             }
             *(h8 *)(out + o) = ov;
@@ -760,7 +772,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     if (res) v[e] += (float)rv8[e];
-                    if (relu) v[e] = fmaxf(v[e], 0.0f);
+                    if (relu) v[e] = relu_nan(v[e]);
                     ov[e] = (_Float16)v[e];
                 }
                 *(h8 *)(out + o) = ov;
@@ -898,7 +910,7 @@ __device__ __forceinline__ void tower_epilogue(_Float16 *dst, const float4 (&bv)
             }
             h4 ov;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) ov[e] = (_Float16)fmaxf(v[e], 0.0f);
+            for (int e = 0; e < 4; ++e) ov[e] = (_Float16)relu_nan(v[e]);
             *o = ov;
         }
     }
@@ -926,7 +938,7 @@ __device__ __forceinline__ void tower_epilogue16(_Float16 *dst, const float4 (&b
             }
             h4 ov;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) ov[e] = (_Float16)fmaxf(v[e], 0.0f);
+            for (int e = 0; e < 4; ++e) ov[e] = (_Float16)relu_nan(v[e]);
             *o = ov;
         }
     }
@@ -961,7 +973,7 @@ __device__ __forceinline__ void tower_epilogue16_batch(_Float16 *dst, const floa
             }
             h4 ov;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) ov[e] = (_Float16)fmaxf(v[e], 0.0f);
+            for (int e = 0; e < 4; ++e) ov[e] = (_Float16)relu_nan(v[e]);
             if (!CHECK || n * 16 + l16 < npix) *(h4 *)(base + n * 16 * LD + 16 * m) = ov;
         }
     }
@@ -1012,7 +1024,7 @@ __device__ __forceinline__ void tower_epilogue16_swap(_Float16 *dst, const float
             }
             h4 ov;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) ov[e] = (_Float16)fmaxf(v[e], 0.0f);
+            for (int e = 0; e < 4; ++e) ov[e] = (_Float16)relu_nan(v[e]);
             __builtin_memcpy(pk[m], &ov, 8);
         }
         const auto s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
@@ -1054,7 +1066,7 @@ __device__ __forceinline__ void tower_epilogue16_swz(_Float16 *dst, const float 
         for (int e = 0; e < 8; ++e) {
             float y = v[e] + bv8[e];
             if constexpr (RES) y += (float)rv[n][e];
-            ov[e] = (_Float16)fmaxf(y, 0.0f);
+            ov[e] = (_Float16)relu_nan(y);
         }
         const int P = n * 16 + l16;
         if (!CHECK || P < npix) *(h8 *)(dst + swz(P, c8)) = ov;
@@ -1310,9 +1322,9 @@ __global__ __launch_bounds__(256 * PG) __attribute__((amdgpu_waves_per_eu(WPE, W
                         const float bb[4] = {pbv[g].x, pbv[g].y, pbv[g].z, pbv[g].w};
                         h4 ov;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {  // logits (relu = 0): no floor, a NaN stays a NaN
+                        for (int e = 0; e < 4; ++e) {  // a NaN stays a NaN, with the ReLU or (logits) without
                             const float y = acc[4 * g + e] + bb[e];
-                            ov[e] = (_Float16)(relu ? fmaxf(y, 0.0f) : y);
+                            ov[e] = (_Float16)(relu ? relu_nan(y) : y);
                         }
                         *(h4 *)(pol.out + ((size_t)b0 * HW + P) * nout + 32 * mb + 8 * g + 4 * hh) = ov;
                     }
