@@ -691,8 +691,10 @@ int zc_net_value_head_async(int32_t n, int32_t hw, const void *d_act, const floa
  *   d_ctl      [8] int64            ZC_TRAJ_* counters below
  *   d_init     one row              the opening (create_init_state)
  * Rows are opaque records of row_bytes (a multiple of 8): a zc_c4_state is 24 bytes, a
- * zc_chess_state 72.  Games land in the pool in completion order (atomics); the game
- * records give each game's place. */
+ * zc_chess_state 72.  Games land in the pool in the order they finish, step after step and in
+ * slot order inside a step (a prefix sum over the slots, no atomics: the layout is
+ * deterministic); the game records give each game's place.  tests/traj_ref.py restates all of
+ * this in plain Python, the overflow rules below included. */
 typedef struct zc_traj_buffers {
     int32_t row_bytes, max_len;
     int64_t pool_cap;
@@ -714,6 +716,21 @@ typedef struct zc_traj_buffers {
 #define ZC_TRAJ_FINISHED 4   /* games finished                                         */
 #define ZC_TRAJ_OVERFLOW 5   /* bit 0: pool full (games dropped); bit 1: a game longer than max_len;
                               * bit 2: the quota ran out inside a multi-step record */
+/* What an overflow leaves specified.  Always: nothing is written outside the buffers; slots a call
+ * leaves alone keep every word; the counters count every finished game, dropped ones included
+ * (POSITIONS adds its positions, GAMES, NEXT and FINISHED one each: POSITIONS and GAMES may pass
+ * pool_cap and games_cap, NEXT keeps counting past the quota); a game that is not dropped is
+ * pooled exactly as without the overflow.
+ *   bit 0: a game whose place (taken from the counters) has first + positions > pool_cap or whose
+ *     record's place is >= games_cap is dropped, and so is every later game.  A dropped game writes
+ *     nothing to d_pool, d_labels, d_pool_moves or d_games and reserves no policy entries; its slot
+ *     restarts like any finished slot.  Everything stays specified.
+ *   bit 1: the slot keeps positions = max_len and its game number, its rows below max_len - 1 and
+ *     its moves below max_len - 2.  Its last row and move and its policy record are unspecified,
+ *     and once that game finishes so are the pool and the counters (the single step pools it with
+ *     max_len positions, the multi-step call with its true length).
+ *   bit 2: the slot goes idle as in single steps; places and counters stay specified only if the
+ *     table holds no later step for that slot (the call's last step, or ZC_SLOT_SKIP from there). */
 #define ZC_SLOT_IDLE 3       /* result of an idle slot                                 */
 #define ZC_SLOT_SKIP 4       /* Connect4 pooled self-play: no move at this step (slot untouched) */
 /* After a move was played on every slot (d_states = positions after the move, d_moves =
@@ -772,6 +789,12 @@ typedef struct zc_traj_policy_buffers {
 #define ZC_TRAJ_PI_ENTRIES 0   /* pool entries reserved                                       */
 #define ZC_TRAJ_PI_OVERFLOW 1  /* bit 0: a slot's history full (slot_cap); bit 1: the entry pool
                                 * full (the game's entries dropped); bit 2: a count saturated */
+/* Every bit leaves the record specified, the same through single steps and the multi-step call.
+ *   bit 0: the entries below slot_cap are kept, the others are lost, every offset is clamped to
+ *     slot_cap, and the pooled game carries the clamped record.
+ *   bit 1: ENTRIES still adds the dropped game's entries, so every later game with entries is
+ *     dropped too; a dropped game's d_pool_first / d_pool_count are 0 and d_pool_pi is not written.
+ *   bit 2: the count is stored as 65535. */
 /* After the search and before the play and record kernels of a step: for every slot with a
  * live game (d_slot[g][1] >= 0) the non-zero (move, Na) pairs of row g of d_root_na
  * [n][stride] become the entries of history position d_slot[g][0] - 1, the position the
@@ -803,8 +826,8 @@ int zc_traj_policy_commit_async(int32_t n, const zc_traj_buffers *buf, const zc_
  * that of games and positions), a game that starts and ends inside the launch goes straight
  * from the staging to the pool, a game's last position has count 0, a finished game's slot
  * restarts with off[0] = 0, and a game the trajectory pool drops reserves no entries.  The
- * same ZC_TRAJ_PI_OVERFLOW bits are set for the same causes (the contents are then
- * unspecified; nothing is written out of bounds).  Four launches whatever `steps` is.
+ * same ZC_TRAJ_PI_OVERFLOW bits are set for the same causes (with the same contents, see the
+ * bits above; nothing is written out of bounds).  Four launches whatever `steps` is.
  * d_reached as for zc_traj_record_steps_async.  d_scratch: device scratch of at least
  * zc_traj_policy_steps_scratch_bytes(n, steps) bytes, 16-byte aligned. */
 int zc_traj_policy_steps_scratch_bytes(int32_t n, int32_t steps, int64_t *bytes);
