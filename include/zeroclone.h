@@ -1054,6 +1054,59 @@ int zc_evalcache_commit_merged_async(void *d_table, int64_t entries, int32_t key
                                      const void *d_dense_logits, double *d_out_values, void *d_out_logits,
                                      int64_t *d_stats, void *d_scratch, void *hip_stream);
 
+/* ---- evaluation cache, routed flush: two networks, a table each (evalcache.hip) -------------
+ * An arena's flush holds rows of two networks (arena route keys above): the routed calls carry
+ * it through ONE probe and ONE commit, with a table, a dense list and a set of counters per
+ * network, so that each network's counted launch runs on its own misses and no row is gathered,
+ * scattered or counted on the host.  A flush goes
+ *   probe -> network A counted on d_count[0] -> network B counted on d_count[1] -> commit
+ * with d_count[0] == d_count[1] == 0 before the probe (the commit leaves them so).  No
+ * allocation, no host read: every call can be captured.
+ *
+ * d_table_a, d_table_b: two different tables of one (entries, key_bytes, logit_bytes), each of
+ * the layout above (zc_evalcache_bytes, zc_evalcache_clear_async serve them); both NULL with
+ * entries == 0: NO TABLES, as in the merged calls.  d_route: one int32 per game, BIT 0 = the
+ * network of the game's rows (0: A, 1: B; the other bits are ignored, as in
+ * zc_arena_route_async); the game of taking-part row r is r / rows_per_game.  n_rows,
+ * rows_per_game, game_rows as in zc_evalcache_probe_async.  d_miss_rows: [2][n_rows] int32,
+ * d_count: [2] int32, d_stats (may be NULL): [2][5] int64, network k's ZC_EVALCACHE_STAT_*
+ * counters at d_stats + 5 k.  d_scratch: the merged calls' scratch for n_rows rows
+ * (zc_evalcache_merge_scratch_bytes, all zeros between flushes), or NULL: NO MERGING.
+ *
+ * zc_evalcache_probe_routed_async: one launch, one wave per taking-part row.  The row is looked
+ * up in its network's table alone.  Hit: as zc_evalcache_probe_async.  Miss, with a scratch:
+ * the claim walk of zc_evalcache_probe_merged_async, where two rows share one evaluation only
+ * if EVERY KEY WORD IS EQUAL AND THEIR ROUTE BITS ARE EQUAL — a claimant of the other network is
+ * passed like an unequal key — and a follower records its leader.  A miss that leads (every
+ * miss without a scratch) takes the next dense slot s of its network k (one atomic on
+ * d_count[k] per workgroup and network): its planes go to d_dense_planes_a or _b + s *
+ * plane_bytes (two buffers of n_rows rows) and d_miss_rows[k * n_rows + s] = row.  Adds to
+ * network k's PROBED, HITS and MERGED.  The dense orders and the leaders may differ from run to
+ * run; no output depends on either.
+ *
+ * zc_evalcache_commit_routed_async: one grid of n_rows waves over both dense lists (d_count[0]
+ * + d_count[1] <= n_rows): wave w serves network A's slot w < min(d_count[0], n_rows), else
+ * network B's slot w - d_count[0]; the slot's d_dense_values_k[s] and d_dense_logits_k + s *
+ * logit_bytes go to its row's output slots and into table k, by zc_evalcache_commit_async's
+ * claim, epoch and drop rules (without tables the scatter alone).  Adds to network k's INSERTS
+ * and DROPPED.  A second launch — over the taking-part rows with a scratch, where it copies the
+ * followers' outputs from their leaders' output slots and zeroes the claim words — sets both
+ * counts to 0 and moves both tables to their next epoch.  Per network, PROBED = HITS + MERGED +
+ * INSERTS + DROPPED with tables. */
+int zc_evalcache_probe_routed_async(void *d_table_a, void *d_table_b, int64_t entries, int32_t key_bytes,
+                                    int32_t logit_bytes, int32_t n_rows, int32_t rows_per_game, int32_t game_rows,
+                                    const int32_t *d_route, const void *d_keys, const void *d_planes,
+                                    int64_t plane_bytes, double *d_out_values, void *d_out_logits,
+                                    void *d_dense_planes_a, void *d_dense_planes_b, int32_t *d_miss_rows,
+                                    int32_t *d_count, int64_t *d_stats, void *d_scratch, void *hip_stream);
+int zc_evalcache_commit_routed_async(void *d_table_a, void *d_table_b, int64_t entries, int32_t key_bytes,
+                                     int32_t logit_bytes, int32_t n_rows, int32_t rows_per_game, int32_t game_rows,
+                                     const void *d_keys, const int32_t *d_miss_rows, int32_t *d_count,
+                                     const double *d_dense_values_a, const void *d_dense_logits_a,
+                                     const double *d_dense_values_b, const void *d_dense_logits_b,
+                                     double *d_out_values, void *d_out_logits, int64_t *d_stats, void *d_scratch,
+                                     void *hip_stream);
+
 /* ---- any game backend: SURVEY §8(b)'s fallback (gen_search.hip) ----------------------
  * mcts.get_move (mcts.cpp:102-160) for a backend the device knows nothing about: the caller
  * keeps the game states and move objects (backend.get_legal_moves / play_move, the policy

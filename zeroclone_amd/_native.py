@@ -355,6 +355,20 @@ SIGNATURES = [
                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                         ctypes.c_void_p]),
+    ("zc_evalcache_probe_routed_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                       ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_evalcache_commit_routed_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                        ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p]),
     ("zc_chess_from_fen", ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
     ("zc_chess_init", ctypes.c_int, [ctypes.c_void_p]),
     ("zc_c4_from_rows", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, P(C4State)]),
@@ -661,6 +675,64 @@ def evalcache_commit_merged(d_table: int, entries: int, key_bytes: int, logit_by
         ctypes.c_void_p(d_count), ctypes.c_void_p(d_dense_values), ctypes.c_void_p(d_dense_logits or None),
         ctypes.c_void_p(d_out_values), ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_stats or None),
         ctypes.c_void_p(d_scratch or None), ctypes.c_void_p(stream or None)))
+
+
+def _evalcache_routed_tables(name: str, d_table_a: int, d_table_b: int, entries: int, key_bytes: int,
+                             logit_bytes: int):
+    evalcache_check_merged_sizes(entries, key_bytes, logit_bytes)
+    if bool(d_table_a) != bool(d_table_b) or bool(d_table_a) != bool(entries) or (d_table_a and d_table_a == d_table_b):
+        raise ValueError(f"{name}: need two different tables of `entries` entries, or none with entries 0")
+
+
+def evalcache_probe_routed(d_table_a: int, d_table_b: int, entries: int, key_bytes: int, logit_bytes: int, n_rows: int,
+                           rows_per_game: int, game_rows: int, d_route: int, d_keys: int, d_planes: int,
+                           plane_bytes: int, d_out_values: int, d_out_logits: int, d_dense_planes_a: int,
+                           d_dense_planes_b: int, d_miss_rows: int, d_count: int, d_stats: int = 0,
+                           d_scratch: int = 0, stream: int = 0):
+    """zc_evalcache_probe_routed_async (include/zeroclone.h) on device pointers: d_miss_rows
+    [2][n_rows], d_count [2], d_stats [2][5]; both tables 0 with entries 0: no tables; d_scratch 0:
+    no merging.  Only enqueues."""
+    name = "zc_evalcache_probe_routed_async"
+    _evalcache_routed_tables(name, d_table_a, d_table_b, entries, key_bytes, logit_bytes)
+    _evalcache_rows(name, n_rows, rows_per_game, game_rows)
+    if plane_bytes < 2 or plane_bytes % 2:
+        raise ValueError(f"{name}: plane_bytes must be a positive multiple of 2 (got {plane_bytes})")
+    if not d_count or (n_rows and not (d_route and d_keys and d_planes and d_out_values and d_dense_planes_a
+                                       and d_dense_planes_b and d_miss_rows and (d_out_logits or not logit_bytes))):
+        raise ValueError(f"{name}: null device pointer")
+    if n_rows and d_dense_planes_a == d_dense_planes_b:
+        raise ValueError(f"{name}: the two networks' dense planes must be two buffers")
+    _arena_rc(name, lib().zc_evalcache_probe_routed_async(
+        ctypes.c_void_p(d_table_a or None), ctypes.c_void_p(d_table_b or None), int(entries), int(key_bytes),
+        int(logit_bytes), int(n_rows), int(rows_per_game), int(game_rows), ctypes.c_void_p(d_route or None),
+        ctypes.c_void_p(d_keys), ctypes.c_void_p(d_planes), int(plane_bytes), ctypes.c_void_p(d_out_values),
+        ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_dense_planes_a), ctypes.c_void_p(d_dense_planes_b),
+        ctypes.c_void_p(d_miss_rows), ctypes.c_void_p(d_count), ctypes.c_void_p(d_stats or None),
+        ctypes.c_void_p(d_scratch or None), ctypes.c_void_p(stream or None)))
+
+
+def evalcache_commit_routed(d_table_a: int, d_table_b: int, entries: int, key_bytes: int, logit_bytes: int,
+                            n_rows: int, rows_per_game: int, game_rows: int, d_keys: int, d_miss_rows: int,
+                            d_count: int, d_dense_values_a: int, d_dense_logits_a: int, d_dense_values_b: int,
+                            d_dense_logits_b: int, d_out_values: int, d_out_logits: int, d_stats: int = 0,
+                            d_scratch: int = 0, stream: int = 0):
+    """zc_evalcache_commit_routed_async (include/zeroclone.h) on device pointers; leaves both counts
+    0 and the scratch ready for the next flush.  Only enqueues."""
+    name = "zc_evalcache_commit_routed_async"
+    _evalcache_routed_tables(name, d_table_a, d_table_b, entries, key_bytes, logit_bytes)
+    _evalcache_rows(name, n_rows, rows_per_game, game_rows)
+    if not d_count or (n_rows and not (d_keys and d_miss_rows and d_dense_values_a and d_dense_values_b
+                                       and d_out_values and ((d_dense_logits_a and d_dense_logits_b and d_out_logits)
+                                                             or not logit_bytes))):
+        raise ValueError(f"{name}: null device pointer")
+    _arena_rc(name, lib().zc_evalcache_commit_routed_async(
+        ctypes.c_void_p(d_table_a or None), ctypes.c_void_p(d_table_b or None), int(entries), int(key_bytes),
+        int(logit_bytes), int(n_rows), int(rows_per_game), int(game_rows), ctypes.c_void_p(d_keys),
+        ctypes.c_void_p(d_miss_rows), ctypes.c_void_p(d_count), ctypes.c_void_p(d_dense_values_a),
+        ctypes.c_void_p(d_dense_logits_a or None), ctypes.c_void_p(d_dense_values_b),
+        ctypes.c_void_p(d_dense_logits_b or None), ctypes.c_void_p(d_out_values),
+        ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_stats or None), ctypes.c_void_p(d_scratch or None),
+        ctypes.c_void_p(stream or None)))
 
 
 def _train_rc(name: str, rc: int):

@@ -21,6 +21,13 @@ The group size is data: after the first refill the side to move no longer follow
 and how many slots hold which side changes every step.  The networks' batch shapes are host
 values, so each step reads one int32 back (d_count[0]) and a step cannot be captured into a
 graph.
+
+With eval_cache= / eval_merge= the arena takes another path (evalcache.RoutedCachedValue /
+RoutedCachedPolicy over a RoutedEvalCache): the keys go to the evaluation cache's routed flush
+as they are, whose probe picks each row's table and dense list by its game's key — a table per
+network, never a shared entry — and whose counted towers take the two group sizes from the
+device.  There is no partition, no gather, no scatter and no host read: such an arena's step
+can be captured (`capture_step()`), and it plays the games the plain arena plays, bit for bit.
 """
 from __future__ import annotations
 
@@ -85,8 +92,10 @@ class _ArenaPool:
                  dirichlet_alpha: float = 0.3, **kw):
         """net_a=, net_b=: the value search with two value networks; puct_net_a=, puct_net_b=:
         the PUCT search with two policy + value networks, by default without root noise and at
-        temperature 0 (a gate measures the networks, not the exploration).  The pool's other
-        arguments are its own.  The refusals come before the engine: they need no GPU."""
+        temperature 0 (a gate measures the networks, not the exploration).  eval_cache=N /
+        eval_merge=True (MFMA networks): an evaluation cache per network, N // 2 entries each,
+        routed on the device (the module's last paragraph).  The pool's other arguments are its
+        own.  The refusals come before the engine: they need no GPU."""
         value, puct = (net_a, net_b), (puct_net_a, puct_net_b)
         has_value, has_puct = any(x is not None for x in value), any(x is not None for x in puct)
         if has_value == has_puct or None in (value if has_value else puct):
@@ -97,12 +106,6 @@ class _ArenaPool:
                              "network's values (reuse_tree)")
         if kw.get("record_policy"):
             raise ValueError("an arena records no policy targets (record_policy)")
-        if kw.get("eval_cache"):
-            raise ValueError("an arena routes the planes alone, without the leaf rows an evaluation cache keys on "
-                             "(eval_cache)")
-        if kw.get("eval_merge"):
-            raise ValueError("an arena routes the planes alone, without the leaf rows a merged flush keys on "
-                             "(eval_merge)")
         if kw.get("streams", 1) > 1 or kw.get("puct_streams", 1) > 1:
             raise ValueError("an arena searches on one stream (streams / puct_streams > 1): the two groups are not "
                              "contiguous game ranges")
@@ -114,23 +117,80 @@ class _ArenaPool:
             if bool(getattr(puct_net_a, "conv_head", False)) != bool(getattr(puct_net_b, "conv_head", False)):
                 raise ValueError("the two PUCT networks must take the planes in one layout (conv_head)")
             kw["puct_args"] = dict(c_puct=c_puct, dirichlet_alpha=dirichlet_alpha, dirichlet_eps=dirichlet_eps)
+        self._nets = value if has_value else puct
+        self._cached = bool(kw.get("eval_cache") or kw.get("eval_merge"))
+        if self._cached:
+            from . import nets
+            kind = nets.MfmaValueNetwork if has_value else nets.MfmaPolicyValueNetwork
+            if not all(isinstance(n, kind) for n in self._nets):
+                raise ValueError("eval_cache / eval_merge need the MFMA form of both networks (its tower takes the "
+                                 "row count from the device): a torch module cannot be cached")
+        self._counted = None   # the routed cache's (steps, mixed steps) on the device
         super().__init__(games, sims, *args, net=net_a, puct_net=puct_net_a, temperature=temperature, **kw)
+        self._steps = self._mixed_steps = 0   # on the host: the plain arena's
+        self.key = torch.zeros(games, dtype=torch.int32, device=self.dev)
+        if self._cached:
+            self.routed = self.value_fn if self.vs is not None else self.net_fn   # _callables below
+            self.routed.set_route(self.key)
+            self._counted = torch.zeros(2, dtype=torch.int64, device=self.dev)
+            return
         if self.vs is not None:
-            self._nets, self._wrap = value, valued.NetValue
+            self._wrap = valued.NetValue
             self.value_fn = self.routed = valued.RoutedValue(valued.NetValue(net_a), valued.NetValue(net_b))
         else:
-            self._nets, self._wrap = puct, valued.PolicyNet
+            self._wrap = valued.PolicyNet
             self.net_fn = self.routed = valued.RoutedPolicy(valued.PolicyNet(puct_net_a), valued.PolicyNet(puct_net_b))
         self._n_a = None   # the group size the networks' buffers were last allocated for
-        self.key = torch.zeros(games, dtype=torch.int32, device=self.dev)
         self.perm = torch.zeros(games, dtype=torch.int32, device=self.dev)
         self.count = torch.zeros(2, dtype=torch.int32, device=self.dev)
-        self.steps = self.mixed_steps = 0   # searches so far, and those with both groups non-empty
+
+    def _callables(self, net, k: int, puct: bool):
+        """With eval_cache / eval_merge the search's callable is the routed cached one over both
+        networks and a RoutedEvalCache: a table of max(eval_cache // 2, ways) entries per network
+        (eval_cache = 0, eval_merge alone: no tables), both empty."""
+        if not self._cached:
+            return super()._callables(net, k, puct)
+        from . import evalcache
+        a = self._nets[0]
+        logit_bytes = 2 * (64 * 64 if a.conv_head else a.w2.shape[1]) if puct else 0
+        row, dtype = (self.ps if puct else self.vs).LEAF
+        key_bytes = int(np.prod(row)) * torch.empty(0, dtype=dtype).element_size()
+        entries = max(self.eval_cache // 2, _native.EVALCACHE_WAYS) if self.eval_cache else 0
+        cache = evalcache.RoutedEvalCache(entries, key_bytes, logit_bytes, self.dev, merge=self.eval_merge)
+        cache.clear()
+        self._caches = [cache]
+        return (evalcache.RoutedCachedPolicy if puct else evalcache.RoutedCachedValue)(*self._nets, cache)
+
+    @property
+    def steps(self) -> int:
+        """Searches so far.  With the routed cache the count lives on the device: reading it
+        synchronises (a step does not)."""
+        return self._steps + (int(self._counted[0]) if self._counted is not None else 0)
+
+    @property
+    def mixed_steps(self) -> int:
+        """The searches in which both networks had games (`steps`' note applies)."""
+        return self._mixed_steps + (int(self._counted[1]) if self._counted is not None else 0)
+
+    def eval_cache_stats(self, by_network: bool = False):
+        """The pools' counters, summed over the two networks' tables; by_network=True: the pair
+        (network A's, network B's).  Synchronises."""
+        if not self._caches:
+            raise ValueError("this pool was built without eval_cache or eval_merge")
+        a, b = self._caches[0].stats()
+        return (a, b) if by_network else {k: a[k] + b[k] for k in a}
 
     def _route(self):
-        """key -> partition -> the routed callable's group sizes: one small device read."""
+        """key -> the routed cache's flush as it is; or -> partition -> the routed callable's
+        group sizes: one small device read."""
         gno = self.traj.slot[:, 1]
         torch.where(gno >= 0, self._turn() ^ ((gno & 1) ^ 1), torch.zeros_like(gno), out=self.key)
+        if self._cached:
+            self.routed.set_route(self.key)
+            n_b = self.key.sum()
+            self._counted[0] += 1
+            self._counted[1] += (n_b > 0) & (n_b < self.G)
+            return
         _native.arena_route(self.G, self.key.data_ptr(), self.perm.data_ptr(), self.count.data_ptr(),
                             torch.cuda.current_stream(self.dev).cuda_stream)
         n_a = int(self.count[0])
@@ -141,8 +201,8 @@ class _ArenaPool:
                                     for net in self._nets)
             self._n_a = n_a
         self.routed.set_route(self.perm, n_a)
-        self.steps += 1
-        self.mixed_steps += 0 < n_a < self.G
+        self._steps += 1
+        self._mixed_steps += 0 < n_a < self.G
 
     def step_search(self, stream: int | None = None) -> torch.Tensor:
         if stream is not None and stream != torch.cuda.current_stream(self.dev).cuda_stream:
@@ -151,10 +211,20 @@ class _ArenaPool:
         return super().step_search(stream)
 
     def capture_step(self):
-        """Refuses: the two groups' sizes are host values read back every step (the networks'
-        batch shapes), so one captured step cannot stand for the next."""
-        raise ValueError("an arena step cannot be captured: the two networks' group sizes change every step "
-                         "and are read back from the device")
+        """With the routed cache (eval_cache / eval_merge) the pool's capture: the step reads
+        nothing back.  The warm-up before the capture runs the networks on whatever the search's
+        buffers hold, so its probes are taken out again: the tables are emptied and the counters
+        put back.  The plain arena refuses: its two groups' sizes are host values read back every
+        step (the networks' batch shapes), so one captured step cannot stand for the next."""
+        if not self._cached:
+            raise ValueError("an arena step cannot be captured without eval_cache or eval_merge: the two "
+                             "networks' group sizes change every step and are read back from the device")
+        cache = self._caches[0]
+        counters = cache.counters.clone()
+        g = super().capture_step()
+        cache.clear()
+        cache.counters.copy_(counters)
+        return g
 
     def play(self, total_games: int, max_steps: int | None = None) -> ArenaResult:
         """evaluate_pair's games: `total_games` games under simulate_games' quota (games 0 ..

@@ -20,6 +20,12 @@ stream's replica of the network a cache of its own, and `clear()` it when the we
 merged_async): among a flush's rows that miss the table, rows with an equal key are evaluated
 once and the others take a copy.  With entries = 0 there is no table and merging is all the
 cache does, at no memory beyond a few words a row.
+
+`RoutedEvalCache` with `RoutedCachedValue(net_a, net_b, cache)` / `RoutedCachedPolicy(net_a, net_b,
+cache)` is the same for an arena's two networks (arena.py): a table per network behind one routed
+probe and one routed commit, each network counted on its own misses.  They stand where
+valued.RoutedValue / RoutedPolicy stand, and take the route bits themselves (`set_route(key)`),
+not a partition.
 """
 from __future__ import annotations
 
@@ -209,4 +215,183 @@ class CachedPolicy:
         dense, count = c.probe(leaves, planes, 1, 1, vo, lo)
         v, lg = self.net(dense, count=count)
         c.commit(leaves, 1, 1, v, lg.contiguous(), vo, lo)
+        return vo, lo
+
+
+class RoutedEvalCache(EvalCache):
+    """Two tables for an arena's two networks behind one routed flush (zc_evalcache_probe_routed_
+    async / ..._commit_routed_async): bit 0 of a game's route word picks the table, the dense list
+    and the counters of its rows, so that each network runs counted on its own misses with no
+    gather, no scatter and no host read.  entries: per table.  It holds the two tables, the two
+    counts, the [2][5] counters, two dense buffers per flush shape and, with merge, the scratch;
+    entries = 0 with merge: no tables.  Rows of different networks never merge and never hit each
+    other's table."""
+
+    def __init__(self, entries: int, key_bytes: int, logit_bytes: int = 0, device="cuda", merge: bool = False):
+        super().__init__(entries, key_bytes, logit_bytes, device, merge)
+        self.tables = None
+
+    def _ensure(self):
+        if self.count is None:
+            if torch.cuda.is_current_stream_capturing():   # the zero fill would be replayed with the graph
+                raise RuntimeError("the evaluation cache must exist before a graph capture: call clear() first")
+            if self.entries:
+                nbytes, self.sets = _native.evalcache_bytes(*self._sizes())
+                self.tables = tuple(torch.zeros(nbytes, dtype=torch.uint8, device=self.dev) for _ in range(2))
+            self.count = torch.zeros(2, dtype=torch.int32, device=self.dev)
+            self.counters = torch.zeros((2, len(_native.EVALCACHE_MERGED_STATS)), dtype=torch.int64, device=self.dev)
+
+    def _table_ptrs(self) -> tuple[int, int]:
+        return tuple(t.data_ptr() for t in self.tables) if self.tables is not None else (0, 0)
+
+    def clear(self):
+        """Empty both tables (stream-ordered; the counters keep counting)."""
+        self._ensure()
+        for ptr in self._table_ptrs():
+            if ptr:
+                _native.evalcache_clear(ptr, *self._sizes(), _stream(self.dev))
+
+    def stats(self) -> tuple[dict, dict]:
+        """(network A's, network B's) counters, each with EvalCache.stats()'s keys.  Synchronises."""
+        self._ensure()
+        return tuple(dict(zip(self._stat_names, (int(x) for x in row))) for row in self.counters.cpu())
+
+    def _route(self, route, n_games: int):
+        if route is None or route.dtype != torch.int32 or route.dim() != 1 or not route.is_contiguous() or \
+                route.shape[0] != n_games or route.device != self.count.device:
+            raise ValueError(f"the route must be a contiguous int32 [{n_games}] tensor on the cache's device: one "
+                             "word per game of the flush")
+
+    def probe(self, leaves, planes, rows: int, game_rows: int, route, out_values, out_logits=None):
+        """EvalCache.probe with route [n_games] int32 (bit 0: the game's network): returns ((the
+        misses' planes of network A, of network B), each packed from row 0 of a buffer of
+        n_games * rows rows; self.count [2] = their numbers on the device)."""
+        self._keys(leaves, planes, game_rows)
+        self._ensure()
+        n_games = leaves.shape[0] // game_rows
+        self._route(route, n_games)
+        n_rows = n_games * rows
+        dense = tuple(self._buf(f"planes{k}", (n_rows, *planes.shape[1:]), planes.dtype) for k in range(2))
+        miss = self._buf("miss", (2, n_rows), torch.int32)
+        _native.evalcache_probe_routed(
+            *self._table_ptrs(), *self._sizes(), n_rows, rows, game_rows, route.data_ptr(), leaves.data_ptr(),
+            planes.data_ptr(), planes[0].numel() * planes.element_size(), out_values.data_ptr(),
+            out_logits.data_ptr() if out_logits is not None else 0, dense[0].data_ptr(), dense[1].data_ptr(),
+            miss.data_ptr(), self.count.data_ptr(), self.counters.data_ptr(),
+            self._scratch(n_rows).data_ptr() if self.merge else 0, _stream(self.dev))
+        return dense, self.count
+
+    def commit(self, leaves, rows: int, game_rows: int, dense_values, dense_logits, out_values, out_logits=None):
+        """EvalCache.commit with dense_values = (network A's, network B's) and dense_logits the
+        same (None for value networks); both counts are 0 again."""
+        n_rows = leaves.shape[0] // game_rows * rows
+        miss = self._buf("miss", (2, n_rows), torch.int32)
+        for v in dense_values:
+            if v.dtype != torch.float64 or v.numel() < n_rows:
+                raise ValueError(f"the network must return fp64 values for {n_rows} rows")
+        if dense_values[0].data_ptr() == dense_values[1].data_ptr():
+            raise ValueError("the two networks must return their values in two buffers (one network on both sides: "
+                             "give one side a replica())")
+        if self.logit_bytes:
+            for lg in dense_logits or (None, None):
+                if lg is None or not lg.is_contiguous() or lg.shape[0] < n_rows or \
+                        lg[0].numel() * lg.element_size() != self.logit_bytes:
+                    raise ValueError(f"the network must return contiguous logits of {self.logit_bytes} bytes a row")
+        lp = [lg.data_ptr() for lg in dense_logits] if self.logit_bytes else [0, 0]
+        _native.evalcache_commit_routed(
+            *self._table_ptrs(), *self._sizes(), n_rows, rows, game_rows, leaves.data_ptr(), miss.data_ptr(),
+            self.count.data_ptr(), dense_values[0].data_ptr(), lp[0], dense_values[1].data_ptr(), lp[1],
+            out_values.data_ptr(), out_logits.data_ptr() if out_logits is not None else 0, self.counters.data_ptr(),
+            self._scratch(n_rows).data_ptr() if self.merge else 0, _stream(self.dev))
+
+
+class _RoutedCached:
+    """What the two routed cached callables share: the two networks (one network on both sides
+    plays through a replica — weights shared, output buffers its own — and still gets two tables)
+    and the route."""
+    wants_leaves = True
+
+    def __init__(self, net_a, net_b, cache: RoutedEvalCache):
+        if not isinstance(cache, RoutedEvalCache):
+            raise ValueError("a routed cached callable needs a RoutedEvalCache")
+        self.nets = (net_a, net_b.replica() if net_b is net_a else net_b)
+        self.cache, self.route = cache, None
+
+    def set_route(self, key: torch.Tensor):
+        """key [n_games] int32 on the device: bit 0 = the network of the game's rows (0: A, 1: B)."""
+        if key.dtype != torch.int32 or key.dim() != 1 or not key.is_contiguous():
+            raise ValueError("the route must be a contiguous int32 [n_games] tensor")
+        self.route = key
+
+    def _games(self, leaves, planes) -> int:
+        if leaves is None:
+            raise ValueError(f"{type(self).__name__} needs the leaf rows: allocate the search with leaves=True")
+        if self.route is None or planes.shape[0] % self.route.shape[0]:
+            raise ValueError("set_route() first, with one word per game of the flush")
+        return self.route.shape[0]
+
+
+class RoutedCachedValue(_RoutedCached):
+    """valued.RoutedValue behind a RoutedEvalCache: an arena value search's value_fn over two
+    MfmaValueNetwork.  The search must be allocated with leaves=True."""
+
+    def __init__(self, net_a, net_b, cache: RoutedEvalCache):
+        for net in (net_a, net_b):
+            if not isinstance(net, MfmaValueNetwork):
+                raise ValueError("RoutedCachedValue needs two MfmaValueNetwork (nets.for_inference(..., "
+                                 "backend='mfma')): a torch module cannot take its row count from the device")
+        if cache.logit_bytes:
+            raise ValueError("a value network's cache holds no logits (logit_bytes = 0)")
+        super().__init__(net_a, net_b, cache)
+
+    def _flush(self, leaves, planes, rows: int, game_rows: int, out):
+        c = self.cache
+        dense, count = c.probe(leaves, planes, rows, game_rows, self.route, out)
+        c.commit(leaves, rows, game_rows, tuple(net(dense[k], count=count[k:k + 1]) for k, net in enumerate(self.nets)),
+                 None, out)
+        return out
+
+    @torch.no_grad()
+    def __call__(self, leaves, planes, counts):
+        rows = planes.shape[0] // self._games(leaves, planes)
+        return self._flush(leaves, planes, rows, rows, self.cache._buf("out", (planes.shape[0],), torch.float64))
+
+    @torch.no_grad()
+    def rows(self, planes, n: int, bs: int, nb: int, out, leaves=None):
+        """NetValue.rows: the short last flush, each game's first nb rows alone."""
+        self._games(leaves, planes)
+        return self._flush(leaves, planes, nb, bs, out)
+
+
+class RoutedCachedPolicy(_RoutedCached):
+    """valued.RoutedPolicy behind a RoutedEvalCache: an arena PUCT search's net_fn over two
+    MfmaPolicyValueNetwork of one head (linear or convolutional, fused) and one logits width.  The
+    search must be allocated with leaves=True; the roots flush gets the roots' rows from the
+    shared driver."""
+    roots_only = True
+
+    def __init__(self, net_a, net_b, cache: RoutedEvalCache):
+        widths = []
+        for net in (net_a, net_b):
+            if not isinstance(net, MfmaPolicyValueNetwork):
+                raise ValueError("RoutedCachedPolicy needs two MfmaPolicyValueNetwork: a torch module cannot take "
+                                 "its row count from the device")
+            if not (net.conv_head or net.fused):
+                raise ValueError("RoutedCachedPolicy needs the fused policy head (32 policy planes on 128 channels)")
+            widths.append(64 * 64 if net.conv_head else net.w2.shape[1])
+        for width in widths:
+            if cache.logit_bytes != 2 * width:
+                raise ValueError(f"the network's logits are {2 * width} bytes a row, the cache's {cache.logit_bytes}")
+        super().__init__(net_a, net_b, cache)
+        self.width = widths[0]
+
+    @torch.no_grad()
+    def __call__(self, leaves, planes, counts):
+        c, L = self.cache, planes.shape[0]
+        rows = L // self._games(leaves, planes)
+        vo = c._buf("vout", (L,), torch.float64)
+        lo = c._buf("lout", (L, self.width), torch.float16)
+        dense, count = c.probe(leaves, planes, rows, rows, self.route, vo, lo)
+        outs = [net(dense[k], count=count[k:k + 1]) for k, net in enumerate(self.nets)]
+        c.commit(leaves, rows, rows, tuple(v for v, _ in outs), tuple(lg.contiguous() for _, lg in outs), vo, lo)
         return vo, lo
