@@ -575,31 +575,33 @@ def evalcache_clear(d_table: int, entries: int, key_bytes: int, logit_bytes: int
         ctypes.c_void_p(d_table), int(entries), int(key_bytes), int(logit_bytes), ctypes.c_void_p(stream or None)))
 
 
-def _evalcache_rows(name: str, n_rows: int, rows_per_game: int, game_rows: int):
+def _evalcache_flush(name: str, n_rows: int, rows_per_game: int, game_rows: int, plane_bytes, d_count: int,
+                     needed: tuple, args: tuple, apart: tuple = ()):
+    """What the six flush wrappers share: the checks of the rows, of plane_bytes (None: a commit has
+    none) and of the pointers (d_count always, `needed` in a flush of rows; `apart`: two that must
+    differ), then the call of entry point `name` with args, integers and device pointers alike."""
     if n_rows < 0 or not 1 <= rows_per_game <= game_rows or n_rows % rows_per_game:
         raise ValueError(f"{name}: need 1 <= rows_per_game <= game_rows and n_rows a multiple of rows_per_game "
                          f"(got n_rows {n_rows}, rows_per_game {rows_per_game}, game_rows {game_rows})")
     if n_rows // rows_per_game * game_rows >= 1 << 31:
         raise ValueError(f"{name}: the buffers' rows must number below 2^31")
+    if plane_bytes is not None and (plane_bytes < 2 or plane_bytes % 2):
+        raise ValueError(f"{name}: plane_bytes must be a positive multiple of 2 (got {plane_bytes})")
+    if not d_count or (n_rows and not all(needed)):
+        raise ValueError(f"{name}: null device pointer")
+    if n_rows and apart and apart[0] == apart[1]:
+        raise ValueError(f"{name}: the two networks' dense planes must be two buffers")
+    _arena_rc(name, getattr(lib(), name)(*(int(a or 0) for a in args)))
 
 
 def evalcache_probe(d_table: int, entries: int, key_bytes: int, logit_bytes: int, n_rows: int, rows_per_game: int,
                     game_rows: int, d_keys: int, d_planes: int, plane_bytes: int, d_out_values: int, d_out_logits: int,
                     d_dense_planes: int, d_miss_rows: int, d_count: int, d_stats: int = 0, stream: int = 0):
     """zc_evalcache_probe_async (include/zeroclone.h) on device pointers.  Only enqueues."""
-    name = "zc_evalcache_probe_async"
-    _evalcache_rows(name, n_rows, rows_per_game, game_rows)
-    if plane_bytes < 2 or plane_bytes % 2:
-        raise ValueError(f"{name}: plane_bytes must be a positive multiple of 2 (got {plane_bytes})")
-    if not d_count or (n_rows and not (d_keys and d_planes and d_out_values and d_dense_planes and d_miss_rows
-                                       and (d_out_logits or not logit_bytes))):
-        raise ValueError(f"{name}: null device pointer")
-    _arena_rc(name, lib().zc_evalcache_probe_async(
-        ctypes.c_void_p(d_table), int(entries), int(key_bytes), int(logit_bytes), int(n_rows), int(rows_per_game),
-        int(game_rows), ctypes.c_void_p(d_keys), ctypes.c_void_p(d_planes), int(plane_bytes),
-        ctypes.c_void_p(d_out_values), ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_dense_planes),
-        ctypes.c_void_p(d_miss_rows), ctypes.c_void_p(d_count), ctypes.c_void_p(d_stats or None),
-        ctypes.c_void_p(stream or None)))
+    _evalcache_flush("zc_evalcache_probe_async", n_rows, rows_per_game, game_rows, plane_bytes, d_count,
+                     (d_keys, d_planes, d_out_values, d_dense_planes, d_miss_rows, d_out_logits or not logit_bytes),
+                     (d_table, entries, key_bytes, logit_bytes, n_rows, rows_per_game, game_rows, d_keys, d_planes,
+                      plane_bytes, d_out_values, d_out_logits, d_dense_planes, d_miss_rows, d_count, d_stats, stream))
 
 
 def evalcache_commit(d_table: int, entries: int, key_bytes: int, logit_bytes: int, n_rows: int, rows_per_game: int,
@@ -607,16 +609,11 @@ def evalcache_commit(d_table: int, entries: int, key_bytes: int, logit_bytes: in
                      d_dense_logits: int, d_out_values: int, d_out_logits: int, d_stats: int = 0, stream: int = 0):
     """zc_evalcache_commit_async (include/zeroclone.h) on device pointers; leaves *d_count = 0.
     Only enqueues."""
-    name = "zc_evalcache_commit_async"
-    _evalcache_rows(name, n_rows, rows_per_game, game_rows)
-    if not d_count or (n_rows and not (d_keys and d_miss_rows and d_dense_values and d_out_values
-                                       and ((d_dense_logits and d_out_logits) or not logit_bytes))):
-        raise ValueError(f"{name}: null device pointer")
-    _arena_rc(name, lib().zc_evalcache_commit_async(
-        ctypes.c_void_p(d_table), int(entries), int(key_bytes), int(logit_bytes), int(n_rows), int(rows_per_game),
-        int(game_rows), ctypes.c_void_p(d_keys), ctypes.c_void_p(d_miss_rows), ctypes.c_void_p(d_count),
-        ctypes.c_void_p(d_dense_values), ctypes.c_void_p(d_dense_logits or None), ctypes.c_void_p(d_out_values),
-        ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_stats or None), ctypes.c_void_p(stream or None)))
+    _evalcache_flush("zc_evalcache_commit_async", n_rows, rows_per_game, game_rows, None, d_count,
+                     (d_keys, d_miss_rows, d_dense_values, d_out_values,
+                      (d_dense_logits and d_out_logits) or not logit_bytes),
+                     (d_table, entries, key_bytes, logit_bytes, n_rows, rows_per_game, game_rows, d_keys, d_miss_rows,
+                      d_count, d_dense_values, d_dense_logits, d_out_values, d_out_logits, d_stats, stream))
 
 
 # ZC_EVALCACHE_STAT_* of the merged calls: the five int64 counters
@@ -643,19 +640,12 @@ def evalcache_probe_merged(d_table: int, entries: int, key_bytes: int, logit_byt
                            d_stats: int, d_scratch: int, stream: int = 0):
     """zc_evalcache_probe_merged_async (include/zeroclone.h) on device pointers; d_table 0 with
     entries 0: no table.  Only enqueues."""
-    name = "zc_evalcache_probe_merged_async"
-    _evalcache_rows(name, n_rows, rows_per_game, game_rows)
-    if plane_bytes < 2 or plane_bytes % 2:
-        raise ValueError(f"{name}: plane_bytes must be a positive multiple of 2 (got {plane_bytes})")
-    if not d_count or (n_rows and not (d_keys and d_planes and d_out_values and d_dense_planes and d_miss_rows
-                                       and d_scratch and (d_out_logits or not logit_bytes))):
-        raise ValueError(f"{name}: null device pointer")
-    _arena_rc(name, lib().zc_evalcache_probe_merged_async(
-        ctypes.c_void_p(d_table or None), int(entries), int(key_bytes), int(logit_bytes), int(n_rows),
-        int(rows_per_game), int(game_rows), ctypes.c_void_p(d_keys), ctypes.c_void_p(d_planes), int(plane_bytes),
-        ctypes.c_void_p(d_out_values), ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_dense_planes),
-        ctypes.c_void_p(d_miss_rows), ctypes.c_void_p(d_count), ctypes.c_void_p(d_stats or None),
-        ctypes.c_void_p(d_scratch or None), ctypes.c_void_p(stream or None)))
+    _evalcache_flush("zc_evalcache_probe_merged_async", n_rows, rows_per_game, game_rows, plane_bytes, d_count,
+                     (d_keys, d_planes, d_out_values, d_dense_planes, d_miss_rows, d_scratch,
+                      d_out_logits or not logit_bytes),
+                     (d_table, entries, key_bytes, logit_bytes, n_rows, rows_per_game, game_rows, d_keys, d_planes,
+                      plane_bytes, d_out_values, d_out_logits, d_dense_planes, d_miss_rows, d_count, d_stats, d_scratch,
+                      stream))
 
 
 def evalcache_commit_merged(d_table: int, entries: int, key_bytes: int, logit_bytes: int, n_rows: int,
@@ -664,17 +654,11 @@ def evalcache_commit_merged(d_table: int, entries: int, key_bytes: int, logit_by
                             d_stats: int, d_scratch: int, stream: int = 0):
     """zc_evalcache_commit_merged_async (include/zeroclone.h) on device pointers; leaves *d_count
     = 0 and the scratch ready for the next flush.  Only enqueues."""
-    name = "zc_evalcache_commit_merged_async"
-    _evalcache_rows(name, n_rows, rows_per_game, game_rows)
-    if not d_count or (n_rows and not (d_keys and d_miss_rows and d_dense_values and d_out_values and d_scratch
-                                       and ((d_dense_logits and d_out_logits) or not logit_bytes))):
-        raise ValueError(f"{name}: null device pointer")
-    _arena_rc(name, lib().zc_evalcache_commit_merged_async(
-        ctypes.c_void_p(d_table or None), int(entries), int(key_bytes), int(logit_bytes), int(n_rows),
-        int(rows_per_game), int(game_rows), ctypes.c_void_p(d_keys), ctypes.c_void_p(d_miss_rows),
-        ctypes.c_void_p(d_count), ctypes.c_void_p(d_dense_values), ctypes.c_void_p(d_dense_logits or None),
-        ctypes.c_void_p(d_out_values), ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_stats or None),
-        ctypes.c_void_p(d_scratch or None), ctypes.c_void_p(stream or None)))
+    _evalcache_flush("zc_evalcache_commit_merged_async", n_rows, rows_per_game, game_rows, None, d_count,
+                     (d_keys, d_miss_rows, d_dense_values, d_out_values, d_scratch,
+                      (d_dense_logits and d_out_logits) or not logit_bytes),
+                     (d_table, entries, key_bytes, logit_bytes, n_rows, rows_per_game, game_rows, d_keys, d_miss_rows,
+                      d_count, d_dense_values, d_dense_logits, d_out_values, d_out_logits, d_stats, d_scratch, stream))
 
 
 def _evalcache_routed_tables(name: str, d_table_a: int, d_table_b: int, entries: int, key_bytes: int,
@@ -694,21 +678,13 @@ def evalcache_probe_routed(d_table_a: int, d_table_b: int, entries: int, key_byt
     no merging.  Only enqueues."""
     name = "zc_evalcache_probe_routed_async"
     _evalcache_routed_tables(name, d_table_a, d_table_b, entries, key_bytes, logit_bytes)
-    _evalcache_rows(name, n_rows, rows_per_game, game_rows)
-    if plane_bytes < 2 or plane_bytes % 2:
-        raise ValueError(f"{name}: plane_bytes must be a positive multiple of 2 (got {plane_bytes})")
-    if not d_count or (n_rows and not (d_route and d_keys and d_planes and d_out_values and d_dense_planes_a
-                                       and d_dense_planes_b and d_miss_rows and (d_out_logits or not logit_bytes))):
-        raise ValueError(f"{name}: null device pointer")
-    if n_rows and d_dense_planes_a == d_dense_planes_b:
-        raise ValueError(f"{name}: the two networks' dense planes must be two buffers")
-    _arena_rc(name, lib().zc_evalcache_probe_routed_async(
-        ctypes.c_void_p(d_table_a or None), ctypes.c_void_p(d_table_b or None), int(entries), int(key_bytes),
-        int(logit_bytes), int(n_rows), int(rows_per_game), int(game_rows), ctypes.c_void_p(d_route or None),
-        ctypes.c_void_p(d_keys), ctypes.c_void_p(d_planes), int(plane_bytes), ctypes.c_void_p(d_out_values),
-        ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_dense_planes_a), ctypes.c_void_p(d_dense_planes_b),
-        ctypes.c_void_p(d_miss_rows), ctypes.c_void_p(d_count), ctypes.c_void_p(d_stats or None),
-        ctypes.c_void_p(d_scratch or None), ctypes.c_void_p(stream or None)))
+    _evalcache_flush(name, n_rows, rows_per_game, game_rows, plane_bytes, d_count,
+                     (d_route, d_keys, d_planes, d_out_values, d_dense_planes_a, d_dense_planes_b, d_miss_rows,
+                      d_out_logits or not logit_bytes),
+                     (d_table_a, d_table_b, entries, key_bytes, logit_bytes, n_rows, rows_per_game, game_rows, d_route,
+                      d_keys, d_planes, plane_bytes, d_out_values, d_out_logits, d_dense_planes_a, d_dense_planes_b,
+                      d_miss_rows, d_count, d_stats, d_scratch, stream),
+                     apart=(d_dense_planes_a, d_dense_planes_b))
 
 
 def evalcache_commit_routed(d_table_a: int, d_table_b: int, entries: int, key_bytes: int, logit_bytes: int,
@@ -720,19 +696,12 @@ def evalcache_commit_routed(d_table_a: int, d_table_b: int, entries: int, key_by
     0 and the scratch ready for the next flush.  Only enqueues."""
     name = "zc_evalcache_commit_routed_async"
     _evalcache_routed_tables(name, d_table_a, d_table_b, entries, key_bytes, logit_bytes)
-    _evalcache_rows(name, n_rows, rows_per_game, game_rows)
-    if not d_count or (n_rows and not (d_keys and d_miss_rows and d_dense_values_a and d_dense_values_b
-                                       and d_out_values and ((d_dense_logits_a and d_dense_logits_b and d_out_logits)
-                                                             or not logit_bytes))):
-        raise ValueError(f"{name}: null device pointer")
-    _arena_rc(name, lib().zc_evalcache_commit_routed_async(
-        ctypes.c_void_p(d_table_a or None), ctypes.c_void_p(d_table_b or None), int(entries), int(key_bytes),
-        int(logit_bytes), int(n_rows), int(rows_per_game), int(game_rows), ctypes.c_void_p(d_keys),
-        ctypes.c_void_p(d_miss_rows), ctypes.c_void_p(d_count), ctypes.c_void_p(d_dense_values_a),
-        ctypes.c_void_p(d_dense_logits_a or None), ctypes.c_void_p(d_dense_values_b),
-        ctypes.c_void_p(d_dense_logits_b or None), ctypes.c_void_p(d_out_values),
-        ctypes.c_void_p(d_out_logits or None), ctypes.c_void_p(d_stats or None), ctypes.c_void_p(d_scratch or None),
-        ctypes.c_void_p(stream or None)))
+    _evalcache_flush(name, n_rows, rows_per_game, game_rows, None, d_count,
+                     (d_keys, d_miss_rows, d_dense_values_a, d_dense_values_b, d_out_values,
+                      (d_dense_logits_a and d_dense_logits_b and d_out_logits) or not logit_bytes),
+                     (d_table_a, d_table_b, entries, key_bytes, logit_bytes, n_rows, rows_per_game, game_rows, d_keys,
+                      d_miss_rows, d_count, d_dense_values_a, d_dense_logits_a, d_dense_values_b, d_dense_logits_b,
+                      d_out_values, d_out_logits, d_stats, d_scratch, stream))
 
 
 def _train_rc(name: str, rc: int):

@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from . import _native, valued
-from .selfplay import C4SelfPlay, ChessSelfPlay, simulate_games
+from .selfplay import C4SelfPlay, ChessSelfPlay, _check_mfma, simulate_games
 
 
 def route_ref(key) -> tuple[np.ndarray, np.ndarray]:
@@ -120,11 +120,7 @@ class _ArenaPool:
         self._nets = value if has_value else puct
         self._cached = bool(kw.get("eval_cache") or kw.get("eval_merge"))
         if self._cached:
-            from . import nets
-            kind = nets.MfmaValueNetwork if has_value else nets.MfmaPolicyValueNetwork
-            if not all(isinstance(n, kind) for n in self._nets):
-                raise ValueError("eval_cache / eval_merge need the MFMA form of both networks (its tower takes the "
-                                 "row count from the device): a torch module cannot be cached")
+            _check_mfma(value, puct, whose="both networks")
         self._counted = None   # the routed cache's (steps, mixed steps) on the device
         super().__init__(games, sims, *args, net=net_a, puct_net=puct_net_a, temperature=temperature, **kw)
         self._steps = self._mixed_steps = 0   # on the host: the plain arena's
@@ -151,11 +147,7 @@ class _ArenaPool:
         if not self._cached:
             return super()._callables(net, k, puct)
         from . import evalcache
-        a = self._nets[0]
-        logit_bytes = 2 * (64 * 64 if a.conv_head else a.w2.shape[1]) if puct else 0
-        row, dtype = (self.ps if puct else self.vs).LEAF
-        key_bytes = int(np.prod(row)) * torch.empty(0, dtype=dtype).element_size()
-        entries = max(self.eval_cache // 2, _native.EVALCACHE_WAYS) if self.eval_cache else 0
+        key_bytes, logit_bytes, entries = self._cache_shape(self._nets[0], puct, 2)
         cache = evalcache.RoutedEvalCache(entries, key_bytes, logit_bytes, self.dev, merge=self.eval_merge)
         cache.clear()
         self._caches = [cache]

@@ -1757,81 +1757,67 @@ int zc_net_conv3x3_packed_async(int32_t n, int32_t h, int32_t w, int32_t cin, co
     return ZC_OK;
 }
 
-int zc_net_tower_async(int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv, const void *d_in,
-                       const void *d_packed, const float *d_bias, void *d_out, const float *d_fc_w, float fc_b,
-                       double *d_values, void *hip_stream) {
-    if (n < 0 || (n && (!d_in || !d_packed || !d_bias || (!d_out && !d_values) || (d_values && !d_fc_w))) ||
-        ((uintptr_t)d_packed & 15) || ((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_bias & 15))
-        return fail(ZC_EINVAL, "bad argument");
+// The five tower entry points: the checks, then launch_net_tower.  policy: the forms with a policy
+// head, which need it and the value head whole (d_out: none); the others need d_out or d_values,
+// and d_fc_w with d_values.  ex: the forms that take policy_channels (32 or 64) and relu, and read
+// d_pb 16 bytes at a time.  counted: the forms that take their row count from d_count.
+static int net_tower(bool policy, bool ex, bool counted, int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv,
+                     const void *d_in, const void *d_packed, const float *d_bias, void *d_out, const float *d_fc_w,
+                     float fc_b, double *d_values, const void *d_pw, const float *d_pb, int32_t policy_channels,
+                     int32_t relu, void *d_pout, const int32_t *d_count, void *hip_stream) {
+    bool ok = n >= 0 && !(((uintptr_t)d_packed | (uintptr_t)d_in | (uintptr_t)d_bias) & 15) &&
+              (!n || (d_in && d_packed && d_bias));
+    if (policy)
+        ok = ok && !((uintptr_t)d_pw & 15) && !((uintptr_t)d_pout & 7) &&
+             (!n || (d_fc_w && d_values && d_pw && d_pb && d_pout));
+    else
+        ok = ok && !((uintptr_t)d_out & 15) && (!n || ((d_out || d_values) && (d_fc_w || !d_values)));
+    if (ex) ok = ok && !((uintptr_t)d_pb & 15) && (policy_channels == 32 || policy_channels == 64);
+    if (counted) ok = ok && d_count && !((uintptr_t)d_count & 3);
+    if (!ok) return fail(ZC_EINVAL, "bad argument");
     if (!n) return ZC_OK;
     if (!zc::launch_net_tower(n, h, w, cin0, nconv, d_in, d_packed, d_bias, d_out, d_values ? d_fc_w : nullptr, fc_b,
-                              d_values, nullptr, nullptr, nullptr, (hipStream_t)hip_stream))
+                              d_values, d_pw, d_pb, d_pout, (hipStream_t)hip_stream, policy_channels, relu, d_count))
         return fail(ZC_EINVAL, "tower shape (h %d, w %d, cin0 %d, %d convs) not supported", h, w, cin0, nconv);
     ZC_HIP(hipGetLastError());
     return ZC_OK;
 }
 
+int zc_net_tower_async(int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv, const void *d_in,
+                       const void *d_packed, const float *d_bias, void *d_out, const float *d_fc_w, float fc_b,
+                       double *d_values, void *hip_stream) {
+    return net_tower(false, false, false, n, h, w, cin0, nconv, d_in, d_packed, d_bias, d_out, d_fc_w, fc_b, d_values,
+                     nullptr, nullptr, 32, 1, nullptr, nullptr, hip_stream);
+}
+
 int zc_net_tower_policy_async(int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv, const void *d_in,
                               const void *d_packed, const float *d_bias, const float *d_fc_w, float fc_b,
                               double *d_values, const void *d_pw, const float *d_pb, void *d_pout, void *hip_stream) {
-    if (n < 0 || (n && (!d_in || !d_packed || !d_bias || !d_fc_w || !d_values || !d_pw || !d_pb || !d_pout)) ||
-        ((uintptr_t)d_packed & 15) || ((uintptr_t)d_in & 15) || ((uintptr_t)d_bias & 15) || ((uintptr_t)d_pw & 15) ||
-        ((uintptr_t)d_pout & 7))
-        return fail(ZC_EINVAL, "bad argument");
-    if (!n) return ZC_OK;
-    if (!zc::launch_net_tower(n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b, d_values, d_pw,
-                              d_pb, d_pout, (hipStream_t)hip_stream))
-        return fail(ZC_EINVAL, "tower shape (h %d, w %d, cin0 %d, %d convs) not supported", h, w, cin0, nconv);
-    ZC_HIP(hipGetLastError());
-    return ZC_OK;
+    return net_tower(true, false, false, n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b, d_values,
+                     d_pw, d_pb, 32, 1, d_pout, nullptr, hip_stream);
 }
 
 int zc_net_tower_policy_ex_async(int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv, const void *d_in,
                                  const void *d_packed, const float *d_bias, const float *d_fc_w, float fc_b,
                                  double *d_values, const void *d_pw, const float *d_pb, int32_t policy_channels,
                                  int32_t relu, void *d_pout, void *hip_stream) {
-    if (n < 0 || (n && (!d_in || !d_packed || !d_bias || !d_fc_w || !d_values || !d_pw || !d_pb || !d_pout)) ||
-        ((uintptr_t)d_packed & 15) || ((uintptr_t)d_in & 15) || ((uintptr_t)d_bias & 15) || ((uintptr_t)d_pw & 15) ||
-        ((uintptr_t)d_pb & 15) || ((uintptr_t)d_pout & 7) || (policy_channels != 32 && policy_channels != 64))
-        return fail(ZC_EINVAL, "bad argument");
-    if (!n) return ZC_OK;
-    if (!zc::launch_net_tower(n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b, d_values, d_pw,
-                              d_pb, d_pout, (hipStream_t)hip_stream, policy_channels, relu))
-        return fail(ZC_EINVAL, "tower shape (h %d, w %d, cin0 %d, %d convs) not supported", h, w, cin0, nconv);
-    ZC_HIP(hipGetLastError());
-    return ZC_OK;
+    return net_tower(true, true, false, n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b, d_values,
+                     d_pw, d_pb, policy_channels, relu, d_pout, nullptr, hip_stream);
 }
 
 int zc_net_tower_counted_async(int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv, const void *d_in,
                                const void *d_packed, const float *d_bias, void *d_out, const float *d_fc_w, float fc_b,
                                double *d_values, const int32_t *d_count, void *hip_stream) {
-    if (n < 0 || !d_count || ((uintptr_t)d_count & 3) ||
-        (n && (!d_in || !d_packed || !d_bias || (!d_out && !d_values) || (d_values && !d_fc_w))) ||
-        ((uintptr_t)d_packed & 15) || ((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_bias & 15))
-        return fail(ZC_EINVAL, "bad argument");
-    if (!n) return ZC_OK;
-    if (!zc::launch_net_tower(n, h, w, cin0, nconv, d_in, d_packed, d_bias, d_out, d_values ? d_fc_w : nullptr, fc_b,
-                              d_values, nullptr, nullptr, nullptr, (hipStream_t)hip_stream, 32, 1, d_count))
-        return fail(ZC_EINVAL, "tower shape (h %d, w %d, cin0 %d, %d convs) not supported", h, w, cin0, nconv);
-    ZC_HIP(hipGetLastError());
-    return ZC_OK;
+    return net_tower(false, false, true, n, h, w, cin0, nconv, d_in, d_packed, d_bias, d_out, d_fc_w, fc_b, d_values,
+                     nullptr, nullptr, 32, 1, nullptr, d_count, hip_stream);
 }
 
 int zc_net_tower_policy_counted_async(int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv, const void *d_in,
                                       const void *d_packed, const float *d_bias, const float *d_fc_w, float fc_b,
                                       double *d_values, const void *d_pw, const float *d_pb, int32_t policy_channels,
                                       int32_t relu, void *d_pout, const int32_t *d_count, void *hip_stream) {
-    if (n < 0 || !d_count || ((uintptr_t)d_count & 3) ||
-        (n && (!d_in || !d_packed || !d_bias || !d_fc_w || !d_values || !d_pw || !d_pb || !d_pout)) ||
-        ((uintptr_t)d_packed & 15) || ((uintptr_t)d_in & 15) || ((uintptr_t)d_bias & 15) || ((uintptr_t)d_pw & 15) ||
-        ((uintptr_t)d_pb & 15) || ((uintptr_t)d_pout & 7) || (policy_channels != 32 && policy_channels != 64))
-        return fail(ZC_EINVAL, "bad argument");
-    if (!n) return ZC_OK;
-    if (!zc::launch_net_tower(n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b, d_values, d_pw,
-                              d_pb, d_pout, (hipStream_t)hip_stream, policy_channels, relu, d_count))
-        return fail(ZC_EINVAL, "tower shape (h %d, w %d, cin0 %d, %d convs) not supported", h, w, cin0, nconv);
-    ZC_HIP(hipGetLastError());
-    return ZC_OK;
+    return net_tower(true, true, true, n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b, d_values,
+                     d_pw, d_pb, policy_channels, relu, d_pout, d_count, hip_stream);
 }
 
 int zc_net_planes_to_nhwc_async(int32_t n, int32_t cin, int32_t hw, int32_t cpad, const void *d_planes, void *d_out,

@@ -39,13 +39,13 @@ def _stream(dev) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
 
 
-class EvalCache:
-    """The table (zc_evalcache_*), its miss counter, its four counters and the dense buffers of
-    the misses (allocated per flush shape at first use).  entries: the table holds the largest
-    power-of-two number of 8-way sets within it.  key_bytes: the leaf row's size (24: zc_c4_state,
-    72: zc_chess_state).  logit_bytes: the logits of one row (0: a value network).  merge: equal
-    rows of one flush are evaluated once (a fifth counter, "merged", and a scratch per flush
-    shape); entries = 0, with merge alone: no table."""
+class _Cache:
+    """An evaluation cache over K tables, K = 1 (EvalCache) or 2 (RoutedEvalCache, a table per
+    network): the tables (zc_evalcache_*), a miss count and a row of counters per table, and per
+    flush shape the dense buffers of the misses and, with merge, the scratch, all allocated at
+    first use."""
+    K: int
+    COUNTERS: tuple   # the counters' shape; (): the cache's own stat names
 
     def __init__(self, entries: int, key_bytes: int, logit_bytes: int = 0, device="cuda", merge: bool = False):
         if merge:
@@ -58,7 +58,7 @@ class EvalCache:
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
             raise ValueError("the evaluation cache lives on a GPU")
-        self.table = self.count = None    # allocated at first use
+        self.tables = self.count = None    # allocated at first use
         self._bufs = {}
 
     def _sizes(self):
@@ -70,25 +70,25 @@ class EvalCache:
                 raise RuntimeError("the evaluation cache must exist before a graph capture: call clear() first")
             if self.entries:
                 nbytes, self.sets = _native.evalcache_bytes(*self._sizes())
-                self.table = torch.zeros(nbytes, dtype=torch.uint8, device=self.dev)   # all zeros: empty
-            self.count = torch.zeros(1, dtype=torch.int32, device=self.dev)
-            self.counters = torch.zeros(len(self._stat_names), dtype=torch.int64, device=self.dev)
+                self.tables = tuple(torch.zeros(nbytes, dtype=torch.uint8, device=self.dev)   # all zeros: empty
+                                    for _ in range(self.K))
+            self.count = torch.zeros(self.K, dtype=torch.int32, device=self.dev)
+            self.counters = torch.zeros(self.COUNTERS or len(self._stat_names), dtype=torch.int64, device=self.dev)
 
-    def _table_ptr(self) -> int:
-        return self.table.data_ptr() if self.table is not None else 0
+    def _table_ptrs(self) -> tuple:
+        return tuple(t.data_ptr() for t in self.tables) if self.tables is not None else (0,) * self.K
 
     def clear(self):
-        """Empty the table (stream-ordered; the counters keep counting).  Without a table
-        (entries = 0) there is nothing to empty."""
+        """Empty the tables (stream-ordered; the counters keep counting).  Without tables (entries
+        = 0) there is nothing to empty."""
         self._ensure()
-        if self.table is not None:
-            _native.evalcache_clear(self.table.data_ptr(), *self._sizes(), _stream(self.dev))
+        for t in self.tables or ():
+            _native.evalcache_clear(t.data_ptr(), *self._sizes(), _stream(self.dev))
 
-    def stats(self) -> dict:
-        """{"probed", "hits", "inserts", "dropped"} so far, and "merged" with merge=True.
-        Synchronises."""
+    def _stats(self) -> tuple:
+        """A dict of the counters per table.  Synchronises."""
         self._ensure()
-        return dict(zip(self._stat_names, (int(x) for x in self.counters.cpu())))
+        return tuple(dict(zip(self._stat_names, (int(x) for x in row))) for row in self.counters.view(self.K, -1).cpu())
 
     def _scratch(self, n_rows: int) -> torch.Tensor:
         """The merged calls' scratch for flushes of n_rows rows: zeros at first, and every flush
@@ -113,112 +113,91 @@ class EvalCache:
         if leaves.shape[0] != planes.shape[0] or leaves.shape[0] % game_rows:
             raise ValueError("leaves and planes must hold the same whole number of games' rows")
 
+    def _flush_args(self, n_rows: int) -> tuple:
+        """(the entry points' family, the arguments after the counters) of this cache's flushes."""
+        scratch = self._scratch(n_rows).data_ptr() if self.merge else 0
+        if self.K == 2:
+            return "_routed", (scratch, _stream(self.dev))
+        return ("_merged", (scratch, _stream(self.dev))) if self.merge else ("", (_stream(self.dev),))
+
+    def _probe(self, leaves, planes, rows: int, game_rows: int, route, out_values, out_logits=None):
+        """The first `rows` of each game's game_rows rows through the tables (route: K = 2 alone):
+        the hits' payloads land in out_values / out_logits; returns (per table the misses' planes,
+        packed from row 0 of a buffer of n_games * rows rows; self.count = their numbers on the
+        device)."""
+        self._keys(leaves, planes, game_rows)
+        self._ensure()
+        n_games = leaves.shape[0] // game_rows
+        n_rows = n_games * rows
+        if self.K == 2:
+            self._route(route, n_games)
+        dense = tuple(self._buf(f"planes{k}", (n_rows, *planes.shape[1:]), planes.dtype) for k in range(self.K))
+        family, last = self._flush_args(n_rows)
+        getattr(_native, "evalcache_probe" + family)(
+            *self._table_ptrs(), *self._sizes(), n_rows, rows, game_rows, *((route.data_ptr(),) if self.K == 2 else ()),
+            leaves.data_ptr(), planes.data_ptr(), planes[0].numel() * planes.element_size(), out_values.data_ptr(),
+            out_logits.data_ptr() if out_logits is not None else 0, *(d.data_ptr() for d in dense),
+            self._buf("miss", (self.K, n_rows), torch.int32).data_ptr(), self.count.data_ptr(), self.counters.data_ptr(), *last)
+        return dense, self.count
+
+    def _commit(self, leaves, rows: int, game_rows: int, dense_values, dense_logits, out_values, out_logits=None):
+        """After the networks ran on _probe's dense planes: per table the misses' values and
+        logits (None for value networks) go to their rows' slots of out_values / out_logits and
+        into the table (with merge, their followers' slots too); self.count is 0 again."""
+        n_rows = leaves.shape[0] // game_rows * rows
+        for v in dense_values:
+            if v.dtype != torch.float64 or v.numel() < n_rows:
+                raise ValueError(f"the network must return fp64 values for {n_rows} rows")
+        if self.K == 2 and dense_values[0].data_ptr() == dense_values[1].data_ptr():
+            raise ValueError("the two networks must return their values in two buffers (one network on both sides: "
+                             "give one side a replica())")
+        if self.logit_bytes:
+            for lg in dense_logits or (None,) * self.K:
+                if lg is None or not lg.is_contiguous() or lg.shape[0] < n_rows or \
+                        lg[0].numel() * lg.element_size() != self.logit_bytes:
+                    raise ValueError(f"the network must return contiguous logits of {self.logit_bytes} bytes a row")
+        logits = [lg.data_ptr() for lg in dense_logits] if self.logit_bytes else [0] * self.K
+        family, last = self._flush_args(n_rows)
+        getattr(_native, "evalcache_commit" + family)(
+            *self._table_ptrs(), *self._sizes(), n_rows, rows, game_rows, leaves.data_ptr(),
+            self._buf("miss", (self.K, n_rows), torch.int32).data_ptr(), self.count.data_ptr(),
+            *(p for v, lg in zip(dense_values, logits) for p in (v.data_ptr(), lg)), out_values.data_ptr(),
+            out_logits.data_ptr() if out_logits is not None else 0, self.counters.data_ptr(), *last)
+
+
+class EvalCache(_Cache):
+    """The table (zc_evalcache_*), its miss counter, its four counters and the dense buffers of
+    the misses (allocated per flush shape at first use).  entries: the table holds the largest
+    power-of-two number of 8-way sets within it.  key_bytes: the leaf row's size (24: zc_c4_state,
+    72: zc_chess_state).  logit_bytes: the logits of one row (0: a value network).  merge: equal
+    rows of one flush are evaluated once (a fifth counter, "merged", and a scratch per flush
+    shape); entries = 0, with merge alone: no table."""
+    K, COUNTERS = 1, ()
+
+    @property
+    def table(self):
+        return self.tables[0] if self.tables is not None else None
+
+    def stats(self) -> dict:
+        """{"probed", "hits", "inserts", "dropped"} so far, and "merged" with merge=True.
+        Synchronises."""
+        return self._stats()[0]
+
     def probe(self, leaves, planes, rows: int, game_rows: int, out_values, out_logits=None):
         """The first `rows` of each game's game_rows rows through the table: the hits' payloads
         land in out_values / out_logits; returns (the misses' planes packed from row 0 of a
         buffer of n_games * rows rows, self.count = their number on the device)."""
-        self._keys(leaves, planes, game_rows)
-        self._ensure()
-        n_rows = leaves.shape[0] // game_rows * rows
-        dense = self._buf("planes", (n_rows, *planes.shape[1:]), planes.dtype)
-        miss = self._buf("miss", (n_rows,), torch.int32)
-        args = (self._table_ptr(), *self._sizes(), n_rows, rows, game_rows, leaves.data_ptr(), planes.data_ptr(),
-                planes[0].numel() * planes.element_size(), out_values.data_ptr(),
-                out_logits.data_ptr() if out_logits is not None else 0, dense.data_ptr(), miss.data_ptr(),
-                self.count.data_ptr(), self.counters.data_ptr())
-        if self.merge:
-            _native.evalcache_probe_merged(*args, self._scratch(n_rows).data_ptr(), _stream(self.dev))
-        else:
-            _native.evalcache_probe(*args, _stream(self.dev))
-        return dense, self.count
+        dense, count = self._probe(leaves, planes, rows, game_rows, None, out_values, out_logits)
+        return dense[0], count
 
     def commit(self, leaves, rows: int, game_rows: int, dense_values, dense_logits, out_values, out_logits=None):
         """After the network ran on probe's dense planes: the misses' outputs go to their rows'
         slots of out_values / out_logits and into the table (with merge, their followers' slots
         too); self.count is 0 again."""
-        n_rows = leaves.shape[0] // game_rows * rows
-        miss = self._buf("miss", (n_rows,), torch.int32)
-        if dense_values.dtype != torch.float64 or dense_values.numel() < n_rows:
-            raise ValueError(f"the network must return fp64 values for {n_rows} rows")
-        if self.logit_bytes:
-            if dense_logits is None or not dense_logits.is_contiguous() or dense_logits.shape[0] < n_rows or \
-                    dense_logits[0].numel() * dense_logits.element_size() != self.logit_bytes:
-                raise ValueError(f"the network must return contiguous logits of {self.logit_bytes} bytes a row")
-        args = (self._table_ptr(), *self._sizes(), n_rows, rows, game_rows, leaves.data_ptr(), miss.data_ptr(),
-                self.count.data_ptr(), dense_values.data_ptr(), dense_logits.data_ptr() if self.logit_bytes else 0,
-                out_values.data_ptr(), out_logits.data_ptr() if out_logits is not None else 0,
-                self.counters.data_ptr())
-        if self.merge:
-            _native.evalcache_commit_merged(*args, self._scratch(n_rows).data_ptr(), _stream(self.dev))
-        else:
-            _native.evalcache_commit(*args, _stream(self.dev))
+        self._commit(leaves, rows, game_rows, (dense_values,), (dense_logits,), out_values, out_logits)
 
 
-class CachedValue:
-    """valued.NetValue behind an EvalCache: a value search's value_fn over an MfmaValueNetwork.
-    The search must be allocated with leaves=True."""
-    wants_leaves = True    # the shared driver then passes the leaf rows to rows() too
-
-    def __init__(self, net, cache: EvalCache):
-        if not isinstance(net, MfmaValueNetwork):
-            raise ValueError("CachedValue needs an MfmaValueNetwork (nets.for_inference(..., backend='mfma')): a "
-                             "torch module cannot take its row count from the device")
-        if cache.logit_bytes:
-            raise ValueError("a value network's cache holds no logits (logit_bytes = 0)")
-        self.model, self.cache = net, cache
-
-    def _flush(self, leaves, planes, rows: int, game_rows: int, out):
-        dense, count = self.cache.probe(leaves, planes, rows, game_rows, out)
-        self.cache.commit(leaves, rows, game_rows, self.model(dense, count=count), None, out)
-        return out
-
-    @torch.no_grad()
-    def __call__(self, leaves, planes, counts):
-        if leaves is None:
-            raise ValueError("CachedValue needs the leaf rows: allocate the search with leaves=True")
-        return self._flush(leaves, planes, 1, 1, self.cache._buf("out", (planes.shape[0],), torch.float64))
-
-    @torch.no_grad()
-    def rows(self, planes, n: int, bs: int, nb: int, out, leaves=None):
-        """NetValue.rows: the short last flush, each game's first nb rows alone."""
-        if leaves is None:
-            raise ValueError("CachedValue needs the leaf rows: allocate the search with leaves=True")
-        return self._flush(leaves, planes, nb, bs, out)
-
-
-class CachedPolicy:
-    """valued.PolicyNet behind an EvalCache: a PUCT search's net_fn over an
-    MfmaPolicyValueNetwork (linear or convolutional head, fused).  The cache's logit_bytes is
-    the network's logits row: 2 * n_logits (fp16).  The search must be allocated with
-    leaves=True; the roots flush gets the roots' rows from the shared driver."""
-    roots_only = True
-    wants_leaves = True
-
-    def __init__(self, net, cache: EvalCache):
-        if not isinstance(net, MfmaPolicyValueNetwork):
-            raise ValueError("CachedPolicy needs an MfmaPolicyValueNetwork: a torch module cannot take its row "
-                             "count from the device")
-        if not (net.conv_head or net.fused):
-            raise ValueError("CachedPolicy needs the fused policy head (32 policy planes on 128 channels)")
-        width = 64 * 64 if net.conv_head else net.w2.shape[1]
-        if cache.logit_bytes != 2 * width:
-            raise ValueError(f"the network's logits are {2 * width} bytes a row, the cache's {cache.logit_bytes}")
-        self.net, self.cache, self.width = net, cache, width
-
-    @torch.no_grad()
-    def __call__(self, leaves, planes, counts):
-        if leaves is None:
-            raise ValueError("CachedPolicy needs the leaf rows: allocate the search with leaves=True")
-        c, L = self.cache, planes.shape[0]
-        vo = c._buf("vout", (L,), torch.float64)
-        lo = c._buf("lout", (L, self.width), torch.float16)
-        dense, count = c.probe(leaves, planes, 1, 1, vo, lo)
-        v, lg = self.net(dense, count=count)
-        c.commit(leaves, 1, 1, v, lg.contiguous(), vo, lo)
-        return vo, lo
-
-
-class RoutedEvalCache(EvalCache):
+class RoutedEvalCache(_Cache):
     """Two tables for an arena's two networks behind one routed flush (zc_evalcache_probe_routed_
     async / ..._commit_routed_async): bit 0 of a game's route word picks the table, the dense list
     and the counters of its rows, so that each network runs counted on its own misses with no
@@ -226,35 +205,11 @@ class RoutedEvalCache(EvalCache):
     counts, the [2][5] counters, two dense buffers per flush shape and, with merge, the scratch;
     entries = 0 with merge: no tables.  Rows of different networks never merge and never hit each
     other's table."""
-
-    def __init__(self, entries: int, key_bytes: int, logit_bytes: int = 0, device="cuda", merge: bool = False):
-        super().__init__(entries, key_bytes, logit_bytes, device, merge)
-        self.tables = None
-
-    def _ensure(self):
-        if self.count is None:
-            if torch.cuda.is_current_stream_capturing():   # the zero fill would be replayed with the graph
-                raise RuntimeError("the evaluation cache must exist before a graph capture: call clear() first")
-            if self.entries:
-                nbytes, self.sets = _native.evalcache_bytes(*self._sizes())
-                self.tables = tuple(torch.zeros(nbytes, dtype=torch.uint8, device=self.dev) for _ in range(2))
-            self.count = torch.zeros(2, dtype=torch.int32, device=self.dev)
-            self.counters = torch.zeros((2, len(_native.EVALCACHE_MERGED_STATS)), dtype=torch.int64, device=self.dev)
-
-    def _table_ptrs(self) -> tuple[int, int]:
-        return tuple(t.data_ptr() for t in self.tables) if self.tables is not None else (0, 0)
-
-    def clear(self):
-        """Empty both tables (stream-ordered; the counters keep counting)."""
-        self._ensure()
-        for ptr in self._table_ptrs():
-            if ptr:
-                _native.evalcache_clear(ptr, *self._sizes(), _stream(self.dev))
+    K, COUNTERS = 2, (2, len(_native.EVALCACHE_MERGED_STATS))
 
     def stats(self) -> tuple[dict, dict]:
         """(network A's, network B's) counters, each with EvalCache.stats()'s keys.  Synchronises."""
-        self._ensure()
-        return tuple(dict(zip(self._stat_names, (int(x) for x in row))) for row in self.counters.cpu())
+        return self._stats()
 
     def _route(self, route, n_games: int):
         if route is None or route.dtype != torch.int32 or route.dim() != 1 or not route.is_contiguous() or \
@@ -266,56 +221,127 @@ class RoutedEvalCache(EvalCache):
         """EvalCache.probe with route [n_games] int32 (bit 0: the game's network): returns ((the
         misses' planes of network A, of network B), each packed from row 0 of a buffer of
         n_games * rows rows; self.count [2] = their numbers on the device)."""
-        self._keys(leaves, planes, game_rows)
-        self._ensure()
-        n_games = leaves.shape[0] // game_rows
-        self._route(route, n_games)
-        n_rows = n_games * rows
-        dense = tuple(self._buf(f"planes{k}", (n_rows, *planes.shape[1:]), planes.dtype) for k in range(2))
-        miss = self._buf("miss", (2, n_rows), torch.int32)
-        _native.evalcache_probe_routed(
-            *self._table_ptrs(), *self._sizes(), n_rows, rows, game_rows, route.data_ptr(), leaves.data_ptr(),
-            planes.data_ptr(), planes[0].numel() * planes.element_size(), out_values.data_ptr(),
-            out_logits.data_ptr() if out_logits is not None else 0, dense[0].data_ptr(), dense[1].data_ptr(),
-            miss.data_ptr(), self.count.data_ptr(), self.counters.data_ptr(),
-            self._scratch(n_rows).data_ptr() if self.merge else 0, _stream(self.dev))
-        return dense, self.count
+        return self._probe(leaves, planes, rows, game_rows, route, out_values, out_logits)
 
     def commit(self, leaves, rows: int, game_rows: int, dense_values, dense_logits, out_values, out_logits=None):
         """EvalCache.commit with dense_values = (network A's, network B's) and dense_logits the
         same (None for value networks); both counts are 0 again."""
-        n_rows = leaves.shape[0] // game_rows * rows
-        miss = self._buf("miss", (2, n_rows), torch.int32)
-        for v in dense_values:
-            if v.dtype != torch.float64 or v.numel() < n_rows:
-                raise ValueError(f"the network must return fp64 values for {n_rows} rows")
-        if dense_values[0].data_ptr() == dense_values[1].data_ptr():
-            raise ValueError("the two networks must return their values in two buffers (one network on both sides: "
-                             "give one side a replica())")
-        if self.logit_bytes:
-            for lg in dense_logits or (None, None):
-                if lg is None or not lg.is_contiguous() or lg.shape[0] < n_rows or \
-                        lg[0].numel() * lg.element_size() != self.logit_bytes:
-                    raise ValueError(f"the network must return contiguous logits of {self.logit_bytes} bytes a row")
-        lp = [lg.data_ptr() for lg in dense_logits] if self.logit_bytes else [0, 0]
-        _native.evalcache_commit_routed(
-            *self._table_ptrs(), *self._sizes(), n_rows, rows, game_rows, leaves.data_ptr(), miss.data_ptr(),
-            self.count.data_ptr(), dense_values[0].data_ptr(), lp[0], dense_values[1].data_ptr(), lp[1],
-            out_values.data_ptr(), out_logits.data_ptr() if out_logits is not None else 0, self.counters.data_ptr(),
-            self._scratch(n_rows).data_ptr() if self.merge else 0, _stream(self.dev))
+        self._commit(leaves, rows, game_rows, dense_values, dense_logits, out_values, out_logits)
 
 
-class _RoutedCached:
+class _Cached:
+    """What the four cached callables share: a network per table of the cache, and the rows per
+    game of a whole flush."""
+    wants_leaves = True
+    route = None   # the routed callables': set_route()
+
+    def __init__(self, nets: tuple, cache: _Cache):
+        name, number = type(self).__name__, "two" if len(nets) == 2 else "an"
+        for net in nets:
+            if not isinstance(net, self.KIND):
+                raise ValueError(f"{name} needs {number} {self.KIND.__name__}{self.HOW}: a torch module cannot take "
+                                 "its row count from the device")
+        self._check(nets, cache)
+        self.nets, self.cache = nets, cache
+
+    def _rows(self, leaves, planes) -> int:
+        """The rows per game of a flush of all of planes' rows, after the refusals: with one
+        network every row stands for itself."""
+        if leaves is None:
+            raise ValueError(f"{type(self).__name__} needs the leaf rows: allocate the search with leaves=True")
+        if len(self.nets) == 1:
+            return 1
+        if self.route is None or planes.shape[0] % self.route.shape[0]:
+            raise ValueError("set_route() first, with one word per game of the flush")
+        return planes.shape[0] // self.route.shape[0]
+
+    def _run(self, dense, count) -> list:
+        """Each network on its dense planes, counted on its own misses."""
+        return [net(d, count=count[k:k + 1]) for k, (net, d) in enumerate(zip(self.nets, dense))]
+
+
+class _CachedValue(_Cached):
+    KIND, HOW = MfmaValueNetwork, " (nets.for_inference(..., backend='mfma'))"
+
+    def _check(self, nets, cache):
+        if cache.logit_bytes:
+            raise ValueError("a value network's cache holds no logits (logit_bytes = 0)")
+
+    def _flush(self, leaves, planes, rows: int, game_rows: int, out):
+        dense, count = self.cache._probe(leaves, planes, rows, game_rows, self.route, out)
+        self.cache._commit(leaves, rows, game_rows, self._run(dense, count), None, out)
+        return out
+
+    @torch.no_grad()
+    def __call__(self, leaves, planes, counts):
+        rows = self._rows(leaves, planes)
+        return self._flush(leaves, planes, rows, rows, self.cache._buf("out", (planes.shape[0],), torch.float64))
+
+    @torch.no_grad()
+    def rows(self, planes, n: int, bs: int, nb: int, out, leaves=None):
+        """NetValue.rows: the short last flush, each game's first nb rows alone."""
+        self._rows(leaves, planes)
+        return self._flush(leaves, planes, nb, bs, out)
+
+
+class _CachedPolicy(_Cached):
+    KIND, HOW = MfmaPolicyValueNetwork, ""
+    roots_only = True
+
+    def _check(self, nets, cache):
+        for net in nets:
+            if not (net.conv_head or net.fused):
+                raise ValueError(f"{type(self).__name__} needs the fused policy head (32 policy planes on 128 "
+                                 "channels)")
+        for net in nets:
+            if cache.logit_bytes != 2 * net.logits_width:
+                raise ValueError(f"the network's logits are {2 * net.logits_width} bytes a row, the cache's "
+                                 f"{cache.logit_bytes}")
+        self.width = nets[0].logits_width
+
+    @torch.no_grad()
+    def __call__(self, leaves, planes, counts):
+        c, L = self.cache, planes.shape[0]
+        rows = self._rows(leaves, planes)
+        vo = c._buf("vout", (L,), torch.float64)
+        lo = c._buf("lout", (L, self.width), torch.float16)
+        dense, count = c._probe(leaves, planes, rows, rows, self.route, vo, lo)
+        outs = self._run(dense, count)
+        c._commit(leaves, rows, rows, tuple(v for v, _ in outs), tuple(lg.contiguous() for _, lg in outs), vo, lo)
+        return vo, lo
+
+
+class CachedValue(_CachedValue):
+    """valued.NetValue behind an EvalCache: a value search's value_fn over an MfmaValueNetwork.
+    The search must be allocated with leaves=True (the shared driver then passes the leaf rows to
+    rows() too)."""
+
+    def __init__(self, net, cache: EvalCache):
+        super().__init__((net,), cache)
+        self.model = net
+
+
+class CachedPolicy(_CachedPolicy):
+    """valued.PolicyNet behind an EvalCache: a PUCT search's net_fn over an
+    MfmaPolicyValueNetwork (linear or convolutional head, fused).  The cache's logit_bytes is
+    the network's logits row: 2 * n_logits (fp16).  The search must be allocated with
+    leaves=True; the roots flush gets the roots' rows from the shared driver."""
+
+    def __init__(self, net, cache: EvalCache):
+        super().__init__((net,), cache)
+        self.net = net
+
+
+class _Routed:
     """What the two routed cached callables share: the two networks (one network on both sides
     plays through a replica — weights shared, output buffers its own — and still gets two tables)
     and the route."""
-    wants_leaves = True
 
     def __init__(self, net_a, net_b, cache: RoutedEvalCache):
+        super().__init__((net_a, net_b), cache)
         if not isinstance(cache, RoutedEvalCache):
             raise ValueError("a routed cached callable needs a RoutedEvalCache")
         self.nets = (net_a, net_b.replica() if net_b is net_a else net_b)
-        self.cache, self.route = cache, None
 
     def set_route(self, key: torch.Tensor):
         """key [n_games] int32 on the device: bit 0 = the network of the game's rows (0: A, 1: B)."""
@@ -323,75 +349,14 @@ class _RoutedCached:
             raise ValueError("the route must be a contiguous int32 [n_games] tensor")
         self.route = key
 
-    def _games(self, leaves, planes) -> int:
-        if leaves is None:
-            raise ValueError(f"{type(self).__name__} needs the leaf rows: allocate the search with leaves=True")
-        if self.route is None or planes.shape[0] % self.route.shape[0]:
-            raise ValueError("set_route() first, with one word per game of the flush")
-        return self.route.shape[0]
 
-
-class RoutedCachedValue(_RoutedCached):
+class RoutedCachedValue(_Routed, _CachedValue):
     """valued.RoutedValue behind a RoutedEvalCache: an arena value search's value_fn over two
     MfmaValueNetwork.  The search must be allocated with leaves=True."""
 
-    def __init__(self, net_a, net_b, cache: RoutedEvalCache):
-        for net in (net_a, net_b):
-            if not isinstance(net, MfmaValueNetwork):
-                raise ValueError("RoutedCachedValue needs two MfmaValueNetwork (nets.for_inference(..., "
-                                 "backend='mfma')): a torch module cannot take its row count from the device")
-        if cache.logit_bytes:
-            raise ValueError("a value network's cache holds no logits (logit_bytes = 0)")
-        super().__init__(net_a, net_b, cache)
 
-    def _flush(self, leaves, planes, rows: int, game_rows: int, out):
-        c = self.cache
-        dense, count = c.probe(leaves, planes, rows, game_rows, self.route, out)
-        c.commit(leaves, rows, game_rows, tuple(net(dense[k], count=count[k:k + 1]) for k, net in enumerate(self.nets)),
-                 None, out)
-        return out
-
-    @torch.no_grad()
-    def __call__(self, leaves, planes, counts):
-        rows = planes.shape[0] // self._games(leaves, planes)
-        return self._flush(leaves, planes, rows, rows, self.cache._buf("out", (planes.shape[0],), torch.float64))
-
-    @torch.no_grad()
-    def rows(self, planes, n: int, bs: int, nb: int, out, leaves=None):
-        """NetValue.rows: the short last flush, each game's first nb rows alone."""
-        self._games(leaves, planes)
-        return self._flush(leaves, planes, nb, bs, out)
-
-
-class RoutedCachedPolicy(_RoutedCached):
+class RoutedCachedPolicy(_Routed, _CachedPolicy):
     """valued.RoutedPolicy behind a RoutedEvalCache: an arena PUCT search's net_fn over two
     MfmaPolicyValueNetwork of one head (linear or convolutional, fused) and one logits width.  The
     search must be allocated with leaves=True; the roots flush gets the roots' rows from the
     shared driver."""
-    roots_only = True
-
-    def __init__(self, net_a, net_b, cache: RoutedEvalCache):
-        widths = []
-        for net in (net_a, net_b):
-            if not isinstance(net, MfmaPolicyValueNetwork):
-                raise ValueError("RoutedCachedPolicy needs two MfmaPolicyValueNetwork: a torch module cannot take "
-                                 "its row count from the device")
-            if not (net.conv_head or net.fused):
-                raise ValueError("RoutedCachedPolicy needs the fused policy head (32 policy planes on 128 channels)")
-            widths.append(64 * 64 if net.conv_head else net.w2.shape[1])
-        for width in widths:
-            if cache.logit_bytes != 2 * width:
-                raise ValueError(f"the network's logits are {2 * width} bytes a row, the cache's {cache.logit_bytes}")
-        super().__init__(net_a, net_b, cache)
-        self.width = widths[0]
-
-    @torch.no_grad()
-    def __call__(self, leaves, planes, counts):
-        c, L = self.cache, planes.shape[0]
-        rows = L // self._games(leaves, planes)
-        vo = c._buf("vout", (L,), torch.float64)
-        lo = c._buf("lout", (L, self.width), torch.float16)
-        dense, count = c.probe(leaves, planes, rows, rows, self.route, vo, lo)
-        outs = [net(dense[k], count=count[k:k + 1]) for k, net in enumerate(self.nets)]
-        c.commit(leaves, rows, rows, tuple(v for v, _ in outs), tuple(lg.contiguous() for _, lg in outs), vo, lo)
-        return vo, lo

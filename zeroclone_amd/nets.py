@@ -390,6 +390,11 @@ class MfmaPolicyValueNetwork:
         self.b2 = lin.bias.detach().float().to(device, torch.float16)
         self._pout = {}
 
+    @property
+    def logits_width(self) -> int:
+        """The logits of one row: 64 from x 64 to of the convolutional head, else the linear head's."""
+        return 64 * 64 if self.conv_head else self.w2.shape[1]
+
     def replica(self) -> "MfmaPolicyValueNetwork":
         """Weights shared, buffers (tower activations, policy conv output) of its own."""
         r = copy.copy(self)

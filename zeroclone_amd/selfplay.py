@@ -411,11 +411,16 @@ def _check_eval_merge(eval_merge: bool, net, puct_net):
         return
     if net is None and puct_net is None:
         raise ValueError("eval_merge merges a network's evaluations: it needs net= or puct_net=")
+    _check_mfma((net,), (puct_net,), "eval_merge needs", "the network", "merged")
+
+
+def _check_mfma(value_nets, puct_nets, what="eval_cache / eval_merge need", whose="the network", verb="cached"):
+    """The refusal of a value or a PUCT network (None: passed over) that is not in its MFMA form."""
     from . import nets
-    for n, kind in ((net, nets.MfmaValueNetwork), (puct_net, nets.MfmaPolicyValueNetwork)):
-        if n is not None and not isinstance(n, kind):
-            raise ValueError("eval_merge needs the MFMA form of the network (its tower takes the row count from "
-                             "the device): a torch module cannot be merged")
+    for group, kind in ((value_nets, nets.MfmaValueNetwork), (puct_nets, nets.MfmaPolicyValueNetwork)):
+        if not all(n is None or isinstance(n, kind) for n in group):
+            raise ValueError(f"{what} the MFMA form of {whose} (its tower takes the row count from the device): a "
+                             f"torch module cannot be {verb}")
 
 
 class _SelfPlayPool:
@@ -501,21 +506,24 @@ class _SelfPlayPool:
         if not self.eval_cache and not self.eval_merge:
             fns = [(valued.PolicyNet if puct else valued.NetValue)(r) for r in reps]
             return fns[0] if k <= 1 else fns
-        from . import evalcache, nets
-        if not isinstance(net, nets.MfmaPolicyValueNetwork if puct else nets.MfmaValueNetwork):
-            raise ValueError("eval_cache / eval_merge need the MFMA form of the network (its tower takes the row "
-                             "count from the device): a torch module cannot be cached")
-        logit_bytes = 2 * (64 * 64 if net.conv_head else net.w2.shape[1]) if puct else 0
+        from . import evalcache
+        _check_mfma(() if puct else (net,), (net,) if puct else ())
+        key_bytes, logit_bytes, entries = self._cache_shape(net, puct, len(reps))
         if [c.logit_bytes for c in self._caches] != [logit_bytes] * len(reps):
-            row, dtype = (self.ps if puct else self.vs).LEAF
-            key_bytes = int(np.prod(row)) * torch.empty(0, dtype=dtype).element_size()
-            entries = max(self.eval_cache // len(reps), _native.EVALCACHE_WAYS) if self.eval_cache else 0
             self._caches = [evalcache.EvalCache(entries, key_bytes, logit_bytes, self.dev, merge=self.eval_merge)
                             for _ in reps]
         for c in self._caches:
             c.clear()
         fns = [(evalcache.CachedPolicy if puct else evalcache.CachedValue)(r, c) for r, c in zip(reps, self._caches)]
         return fns[0] if k <= 1 else fns
+
+    def _cache_shape(self, net, puct: bool, tables: int) -> tuple[int, int, int]:
+        """(key_bytes: the search's leaf row, logit_bytes: the network's logits row, the entries of
+        each of `tables` tables that share eval_cache; 0: no table) of the pool's caches."""
+        row, dtype = (self.ps if puct else self.vs).LEAF
+        key_bytes = int(np.prod(row)) * torch.empty(0, dtype=dtype).element_size()
+        entries = max(self.eval_cache // tables, _native.EVALCACHE_WAYS) if self.eval_cache else 0
+        return key_bytes, 2 * net.logits_width if puct else 0, entries
 
     def eval_cache_stats(self) -> dict:
         """The evaluation caches' counters summed over the streams' tables: {"probed", "hits",
