@@ -547,6 +547,13 @@ int zc_chess_puct_begin_reuse(zc_engine *eng, int32_t first_game, int32_t n_game
                               void *hip_stream);
 /* Stream-ordered: the games' kept chess PUCT trees are dropped; their next search starts afresh. */
 int zc_chess_puct_forget(zc_engine *eng, int32_t first_game, int32_t n_games, void *hip_stream);
+/* zc_chess_puct_forget for the games alone whose recorder slot holds a game at its first position
+ * (d_slot = zc_traj_buffers.d_slot of the pool the games play in, row i for game first_game + i:
+ * d_slot[i][0] == 1 and d_slot[i][1] >= 0): after a step's record a refilled slot's tree belongs
+ * to the game that ended, and with a book of openings (zc_traj_openings_async) its next root may
+ * sit below that game's last root.  Stream-ordered, no host read. */
+int zc_chess_puct_forget_fresh(zc_engine *eng, int32_t first_game, int32_t n_games, const int32_t *d_slot,
+                            void *hip_stream);
 
 /* ---- Connect4 PUCT search (AlphaZero-style; no reference counterpart) -----
  * The chess PUCT search's rules (above) on the Connect4 rules of c4_backend.py: moves in
@@ -585,6 +592,13 @@ int zc_c4_puct_begin_reuse(zc_engine *eng, int32_t first_game, int32_t n_games, 
 /* Stream-ordered: the games' kept trees are dropped; their next search starts afresh
  * (new network weights, restarted games). */
 int zc_c4_puct_forget(zc_engine *eng, int32_t first_game, int32_t n_games, void *hip_stream);
+/* zc_c4_puct_forget for the games alone whose recorder slot holds a game at its first position
+ * (d_slot = zc_traj_buffers.d_slot of the pool the games play in, row i for game first_game + i:
+ * d_slot[i][0] == 1 and d_slot[i][1] >= 0): after a step's record a refilled slot's tree belongs
+ * to the game that ended, and with a book of openings (zc_traj_openings_async) its next root may
+ * sit below that game's last root.  Stream-ordered, no host read. */
+int zc_c4_puct_forget_fresh(zc_engine *eng, int32_t first_game, int32_t n_games, const int32_t *d_slot,
+                            void *hip_stream);
 /* Test hook: game `game`'s Connect4 PUCT tree as raw 192-byte node records (stones X/O, move
  * order word, turn, #moves, evaluated, won, parent, parent slot, depth, children[8], N[8],
  * P[8] float, W[8] double); *out_count = nodes.  Synchronises the device. */
@@ -760,6 +774,20 @@ int zc_traj_steps_scratch_bytes(int32_t n, int32_t steps, int64_t *bytes);
 int zc_traj_record_steps_async(int32_t n, const zc_traj_buffers *buf, void *d_states, const int16_t *d_moves,
                                int32_t *d_results, int32_t steps, const int32_t *d_reached, void *d_scratch,
                                int64_t scratch_bytes, void *hip_stream);
+/* A book of openings in place of the one d_init row.  d_book holds book_rows rows of
+ * buf->row_bytes, d_roots the n positions the next search starts from.  Every slot g whose game
+ * has only its first position (d_slot[g][0] == 1) and a game number d_slot[g][1] = game >= 0
+ * takes row (game / share) % book_rows of the book as d_roots[g] and as d_hist[g][0]: share = 1
+ * gives game g opening g % book_rows, share = 2 gives games 2k and 2k + 1 opening k % book_rows
+ * (an arena's pair, colours swapped).  Idle slots stay at d_init, games in progress are not
+ * touched, and a second call changes nothing.  It belongs after zc_traj_record_async (and
+ * zc_traj_policy_commit_async) of a step, and after the pool is started; a chess pool's
+ * repetition histories are already empty for the refilled slots then.  The book's rows are the
+ * caller's to check (a finished position must not be in it).  Stream-ordered: one launch, no host
+ * read, no allocation, no atomics.  ZC_EINVAL: null or unaligned pointers, book_rows < 1,
+ * share < 1.  tests/traj_openings_ref.py restates the rule. */
+int zc_traj_openings_async(int32_t n, const zc_traj_buffers *buf, const void *d_book, int32_t book_rows,
+                           int32_t share, void *d_roots, void *hip_stream);
 
 /* ---- root visit counts as policy targets (pi(a) = N(a) / sum N) ----------------------
  * A sparse record per searched position, kept beside a zc_traj_buffers pool (which it does

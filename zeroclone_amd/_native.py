@@ -252,6 +252,8 @@ SIGNATURES = [
                                                  ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p]),
     ("zc_chess_puct_forget", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
+    ("zc_chess_puct_forget_fresh", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                  ctypes.c_void_p]),
     ("zc_c4_puct_begin", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
                                         ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_float,
                                         ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
@@ -260,6 +262,8 @@ SIGNATURES = [
                                               ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p]),
     ("zc_c4_puct_forget", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
+    ("zc_c4_puct_forget_fresh", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                               ctypes.c_void_p]),
     ("zc_c4_puct_select", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                          ctypes.c_void_p]),
@@ -309,6 +313,8 @@ SIGNATURES = [
                                                ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
     ("zc_traj_record_async", ctypes.c_int, [ctypes.c_int32, P(TrajBuffers), ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_traj_openings_async", ctypes.c_int, [ctypes.c_int32, P(TrajBuffers), ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     ("zc_traj_policy_append_async", ctypes.c_int, [ctypes.c_int32, P(TrajBuffers), P(TrajPolicyBuffers),
                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     ("zc_traj_policy_commit_async", ctypes.c_int, [ctypes.c_int32, P(TrajBuffers), P(TrajPolicyBuffers),
@@ -1079,6 +1085,10 @@ class NativeEngine:
     def chess_puct_forget(self, first_game, n, stream=0):
         check(lib().zc_chess_puct_forget(self._h, first_game, n, ctypes.c_void_p(stream or None)))
 
+    def chess_puct_forget_fresh(self, first_game, n, d_slot, stream=0):
+        check(lib().zc_chess_puct_forget_fresh(self._h, first_game, n, ctypes.c_void_p(d_slot),
+                                               ctypes.c_void_p(stream or None)))
+
     def chess_puct_select(self, first_game, n, flush, d_leaves=0, d_planes=0, planes_f16=True, d_counts=0, stream=0,
                           planes_nhwc=False):
         """planes_nhwc: fp16 planes in the tower's input layout [n*bs][64][32] (ZC_F16_NHWC32)."""
@@ -1115,6 +1125,10 @@ class NativeEngine:
 
     def c4_puct_forget(self, first_game, n, stream=0):
         check(lib().zc_c4_puct_forget(self._h, first_game, n, ctypes.c_void_p(stream or None)))
+
+    def c4_puct_forget_fresh(self, first_game, n, d_slot, stream=0):
+        check(lib().zc_c4_puct_forget_fresh(self._h, first_game, n, ctypes.c_void_p(d_slot),
+                                            ctypes.c_void_p(stream or None)))
 
     def c4_puct_select(self, first_game, n, flush, d_leaves=0, d_planes=0, planes_f16=True, d_counts=0, stream=0):
         check(lib().zc_c4_puct_select(self._h, first_game, n, int(flush), ctypes.c_void_p(d_leaves or None),

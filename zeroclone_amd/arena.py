@@ -85,7 +85,14 @@ class ArenaResult:
 
 class _ArenaPool:
     """What the two arenas add to their self-play pool (they subclass it): the two-network
-    arguments and their refusals, the per-step route, `play()`."""
+    arguments and their refusals, the per-step route, `play()`, `set_networks()`.
+
+    With openings= (the pool's book of openings) games 2k and 2k + 1 start from row k % N of the
+    book: the colours still go by game number, so every opening is played once with network A as
+    the side with turn 0 and once with network B.  An opening at an odd ply is fine: the route's
+    key takes the root's turn, and `ArenaResult.tally` reads +1 as the side with turn 0."""
+
+    _openings_share = 2
 
     def __init__(self, games: int, sims: int, *args, net_a=None, net_b=None, puct_net_a=None, puct_net_b=None,
                  temperature: float = 0.0, dirichlet_eps: float = 0.0, c_puct: float = 1.5,
@@ -118,6 +125,7 @@ class _ArenaPool:
                 raise ValueError("the two PUCT networks must take the planes in one layout (conv_head)")
             kw["puct_args"] = dict(c_puct=c_puct, dirichlet_alpha=dirichlet_alpha, dirichlet_eps=dirichlet_eps)
         self._nets = value if has_value else puct
+        self._conv_head = bool(getattr(self._nets[0], "conv_head", False))
         self._cached = bool(kw.get("eval_cache") or kw.get("eval_merge"))
         if self._cached:
             _check_mfma(value, puct, whose="both networks")
@@ -143,15 +151,67 @@ class _ArenaPool:
     def _callables(self, net, k: int, puct: bool):
         """With eval_cache / eval_merge the search's callable is the routed cached one over both
         networks and a RoutedEvalCache: a table of max(eval_cache // 2, ways) entries per network
-        (eval_cache = 0, eval_merge alone: no tables), both empty."""
+        (eval_cache = 0, eval_merge alone: no tables), both empty.  set_networks comes here again:
+        the tables are kept where the logits row still fits them, emptied, and the counters go on
+        counting."""
         if not self._cached:
             return super()._callables(net, k, puct)
         from . import evalcache
         key_bytes, logit_bytes, entries = self._cache_shape(self._nets[0], puct, 2)
-        cache = evalcache.RoutedEvalCache(entries, key_bytes, logit_bytes, self.dev, merge=self.eval_merge)
+        if not self._caches or self._caches[0].logit_bytes != logit_bytes:
+            self._caches = [evalcache.RoutedEvalCache(entries, key_bytes, logit_bytes, self.dev, merge=self.eval_merge)]
+        cache = self._caches[0]
         cache.clear()
-        self._caches = [cache]
         return (evalcache.RoutedCachedPolicy if puct else evalcache.RoutedCachedValue)(*self._nets, cache)
+
+    def _inference_pair(self, model_a, model_b) -> tuple:
+        """set_networks' two models as the searches evaluate them, or the refusal of a pair that is
+        not of the arena's search and layout.  Needs no GPU unless a trained model is converted."""
+        from . import learner, nets
+        puct = self.ps is not None
+        pair = []
+        for m in (model_a, model_b):
+            is_puct = isinstance(m, (nets.PolicyValueNetwork, nets.MfmaPolicyValueNetwork,
+                                     learner.FoldedPolicyValueNetwork))
+            is_value = isinstance(m, (nets.ValueNetwork, nets.MfmaValueNetwork, nets.FoldedValueNetwork))
+            if (is_puct or is_value) and is_puct != puct:
+                raise ValueError("this arena was built for the " + ("PUCT search: it takes two policy + value "
+                                 "networks" if puct else "value search: it takes two value networks"))
+            head = getattr(m, "conv_head", getattr(m, "head_kind", "linear") == "conv")
+            if puct and bool(head) != self._conv_head:
+                raise ValueError("the arena's search hands over the planes in the layout of the networks it was "
+                                 "built with (conv_head): the new networks must take the same")
+            pair.append(m)
+        trained = (nets.ValueNetwork, nets.PolicyValueNetwork)
+        return tuple(learner.inference_form(m, self.dev) if isinstance(m, trained) else m for m in pair)
+
+    def set_networks(self, model_a, model_b):
+        """Play model_a (network A) against model_b from the next step() on: the gate's hand-over
+        (learner.full_training_run(gate=)).  Trained modules (`nets.ValueNetwork` /
+        `nets.PolicyValueNetwork`) go through learner.inference_form; networks already in their
+        inference form are taken as they are.  Both routed callables are replaced — on the plain
+        path with their buffers, which the next route allocates for its group sizes — and both
+        evaluation caches are emptied: an entry of an old network must never serve a new one.  A
+        pair of another search (value / PUCT) or another conv_head than the arena was built with
+        is refused.  A step graph captured before keeps the old weights, as `set_network`'s."""
+        pair = self._inference_pair(model_a, model_b)
+        puct = self.ps is not None
+        if self._cached:
+            _check_mfma(() if puct else pair, pair if puct else (), whose="both networks")
+        self._nets = pair
+        if self._cached:
+            self.routed = self._callables(pair[0], 1, puct)   # both tables emptied
+            self.routed.set_route(self.key)
+        else:
+            self.routed = (valued.RoutedPolicy if puct else valued.RoutedValue)(*(self._wrap(n) for n in pair))
+            self._n_a = None
+        if puct:
+            self.net_fn = self.routed
+        else:
+            self.value_fn = self.routed
+
+    def set_network(self, model):
+        raise ValueError("an arena plays two networks: set_networks(model_a, model_b)")
 
     @property
     def steps(self) -> int:

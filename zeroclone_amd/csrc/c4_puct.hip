@@ -440,6 +440,9 @@ void launch_c4_puct_reroot(const C4PuctParams &p, hipStream_t s) {
 void launch_c4_puct_forget(const C4PuctParams &p, hipStream_t s) {
     launch_puct_forget(p.ctl, p.first_game, p.n_games, PCtl::done, s);
 }
+void launch_c4_puct_forget_fresh(const C4PuctParams &p, const int32_t *slot, hipStream_t s) {
+    launch_puct_forget_fresh(p.ctl, p.first_game, p.n_games, PCtl::done, slot, s);
+}
 void launch_c4_puct_select(const C4PuctParams &p, hipStream_t s) {
     hipLaunchKernelGGL(c4_puct_select_kernel, dim3(p.n_games), dim3(64), 0, s, p);
 }

@@ -724,6 +724,9 @@ void launch_chess_puct_reroot(const ChessParams &p, hipStream_t s) {
 void launch_chess_puct_forget(const ChessParams &p, hipStream_t s) {
     launch_puct_forget(p.ca.ctl, p.first_game, p.n_games, PCtl::done, s);
 }
+void launch_chess_puct_forget_fresh(const ChessParams &p, const int32_t *slot, hipStream_t s) {
+    launch_puct_forget_fresh(p.ca.ctl, p.first_game, p.n_games, PCtl::done, slot, s);
+}
 void launch_chess_puct_select(const ChessParams &p, hipStream_t s) {
     hipLaunchKernelGGL(puct_select_kernel, dim3(p.n_games), dim3(64), 0, s, p);
     if (p.flush > 0) {  // flush 0 evaluates the root alone: nothing is created

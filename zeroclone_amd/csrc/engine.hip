@@ -963,6 +963,19 @@ int zc_traj_record_async(int32_t n, const zc_traj_buffers *buf, void *d_states, 
     return ZC_OK;
 }
 
+int zc_traj_openings_async(int32_t n, const zc_traj_buffers *buf, const void *d_book, int32_t book_rows,
+                           int32_t share, void *d_roots, void *hip_stream) {
+    if (int r = check_traj(n, buf, d_roots)) return r;
+    if (book_rows < 1 || share < 1)
+        return fail(ZC_EINVAL, "book_rows and share must be >= 1 (got %d, %d)", book_rows, share);
+    if (!d_book || !d_roots) return fail(ZC_EINVAL, "bad argument");
+    if ((uintptr_t)d_book & 7) return fail(ZC_EINVAL, "rows must be 8-byte aligned");
+    if (!n) return ZC_OK;
+    zc::launch_traj_openings(n, *buf, d_book, book_rows, share, d_roots, (hipStream_t)hip_stream);
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+
 namespace {
 int check_traj_policy(const zc_traj_policy_buffers *pol) {
     if (!pol) return fail(ZC_EINVAL, "bad argument");
@@ -1476,6 +1489,7 @@ struct ChessPuct {
     static constexpr auto begin = zc::launch_chess_puct_begin, reroot = zc::launch_chess_puct_reroot,
                           forget = zc::launch_chess_puct_forget, select = zc::launch_chess_puct_select,
                           backup = zc::launch_chess_puct_backup, end = zc::launch_chess_puct_end;
+    static constexpr auto forget_fresh = zc::launch_chess_puct_forget_fresh;
 };
 
 struct C4Puct {
@@ -1516,6 +1530,7 @@ struct C4Puct {
     static constexpr auto begin = zc::launch_c4_puct_begin, reroot = zc::launch_c4_puct_reroot,
                           forget = zc::launch_c4_puct_forget, select = zc::launch_c4_puct_select,
                           backup = zc::launch_c4_puct_backup, end = zc::launch_c4_puct_end;
+    static constexpr auto forget_fresh = zc::launch_c4_puct_forget_fresh;
 };
 
 // begin / begin_reuse: the same validation and search parameters; the reuse form launches the
@@ -1555,6 +1570,18 @@ int puct_forget(zc_engine *eng, int32_t first, int32_t n, void *hip_stream) {
     if (!n || !G::has_tree(eng)) return ZC_OK;  // no tree yet: nothing is kept
     ZC_HIP(hipSetDevice(eng->cfg.device));
     G::forget(G::params(eng, first, n), (hipStream_t)hip_stream);
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+
+template <class G>
+int puct_forget_fresh(zc_engine *eng, int32_t first, int32_t n, const int32_t *d_slot, void *hip_stream) {
+    if (!eng || (n > 0 && !d_slot)) return fail(ZC_EINVAL, "null argument");
+    if (int r = check_games(eng, first, n)) return r;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    if (!n || !G::has_tree(eng)) return ZC_OK;  // no tree yet: nothing is kept
+    ZC_HIP(hipSetDevice(eng->cfg.device));
+    G::forget_fresh(G::params(eng, first, n), d_slot, (hipStream_t)hip_stream);
     ZC_HIP(hipGetLastError());
     return ZC_OK;
 }
@@ -1628,6 +1655,9 @@ int zc_chess_puct_begin_reuse(zc_engine *eng, int32_t first, int32_t n, const zc
 int zc_chess_puct_forget(zc_engine *eng, int32_t first, int32_t n, void *hip_stream) {
     return puct_forget<ChessPuct>(eng, first, n, hip_stream);
 }
+int zc_chess_puct_forget_fresh(zc_engine *eng, int32_t first, int32_t n, const int32_t *d_slot, void *hip_stream) {
+    return puct_forget_fresh<ChessPuct>(eng, first, n, d_slot, hip_stream);
+}
 int zc_chess_puct_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, zc_chess_state *d_leaves,
                          void *d_planes, int32_t planes_dtype, int32_t *d_counts, void *hip_stream) {
     return puct_select<ChessPuct>(eng, first, n, flush, d_leaves, d_planes, planes_dtype, d_counts, hip_stream);
@@ -1659,6 +1689,9 @@ int zc_c4_puct_begin_reuse(zc_engine *eng, int32_t first, int32_t n, const zc_c4
 }
 int zc_c4_puct_forget(zc_engine *eng, int32_t first, int32_t n, void *hip_stream) {
     return puct_forget<C4Puct>(eng, first, n, hip_stream);
+}
+int zc_c4_puct_forget_fresh(zc_engine *eng, int32_t first, int32_t n, const int32_t *d_slot, void *hip_stream) {
+    return puct_forget_fresh<C4Puct>(eng, first, n, d_slot, hip_stream);
 }
 int zc_c4_puct_select(zc_engine *eng, int32_t first, int32_t n, int32_t flush, zc_c4_state *d_leaves, void *d_planes,
                       int32_t planes_dtype, int32_t *d_counts, void *hip_stream) {

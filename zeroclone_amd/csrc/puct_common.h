@@ -92,6 +92,20 @@ inline void launch_puct_forget(int32_t *ctl, int first_game, int n_games, int do
                        done_word);
 }
 
+// forget, for the games alone whose recorder slot (zc_traj_buffers.d_slot, row gl) holds a game at
+// its first position: a refilled slot's tree belongs to the game that ended.
+__global__ void puct_forget_fresh_kernel(int32_t *ctl, int first_game, int n_games, int done_word,
+                                         const int32_t *slot) {
+    const int gl = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gl < n_games && slot[4 * (size_t)gl] == 1 && slot[4 * (size_t)gl + 1] >= 0)
+        ctl[(size_t)(first_game + gl) * kCtlWords + done_word] = 0;
+}
+inline void launch_puct_forget_fresh(int32_t *ctl, int first_game, int n_games, int done_word, const int32_t *slot,
+                                     hipStream_t s) {
+    hipLaunchKernelGGL(puct_forget_fresh_kernel, dim3((n_games + 63) / 64), dim3(64), 0, s, ctl, first_game, n_games,
+                       done_word, slot);
+}
+
 // select: the walks flush p.flush makes; none in a failed search, none in flush 0 of a search
 // on a kept subtree (a kept root is evaluated already).
 template <class W, class Params>

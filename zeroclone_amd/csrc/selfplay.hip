@@ -841,7 +841,35 @@ __global__ __launch_bounds__(256) void traj_policy_dense4096_kernel(int n_rows, 
     }
 }
 
+// ---------------------------------------------------------------- openings
+// A book of openings in place of the one d_init row: one thread per (slot, word).  A slot whose
+// game has only its first position (slot[0] == 1, game >= 0: started by Trajectories.start or
+// refilled by the record just before) takes row (game / share) % book_rows of the book as its
+// root and as position 0 of its history.  Idle slots and games in progress are not touched, so
+// the call can be repeated.
+__global__ __launch_bounds__(256) void traj_openings_kernel(int n, zc_traj_buffers b, const uint64_t *book,
+                                                            int book_rows, int share, uint64_t *roots) {
+    const int W = b.row_bytes / 8;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long g = t / W;
+    const int w = (int)(t % W);
+    if (g >= n) return;
+    const int32_t *slot = b.d_slot + 4 * (size_t)g;
+    const int game = slot[1];
+    if (game < 0 || slot[0] != 1) return;
+    const uint64_t v = book[(size_t)((game / share) % book_rows) * W + w];
+    roots[(size_t)g * W + w] = v;
+    ((uint64_t *)b.d_hist)[(size_t)g * b.max_len * W + w] = v;
+}
+
 }  // namespace
+
+void launch_traj_openings(int n, const zc_traj_buffers &b, const void *book, int book_rows, int share, void *roots,
+                          hipStream_t s) {
+    const long long threads = (long long)n * (b.row_bytes / 8);
+    hipLaunchKernelGGL(traj_openings_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, n, b,
+                       (const uint64_t *)book, book_rows, share, (uint64_t *)roots);
+}
 
 void launch_traj_policy_append(int n, const zc_traj_buffers &b, const zc_traj_policy_buffers &q, const int32_t *na,
                                const uint16_t *mv, int stride, hipStream_t s) {

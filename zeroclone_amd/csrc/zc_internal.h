@@ -294,6 +294,7 @@ struct C4PuctParams {
 void launch_c4_puct_begin(const C4PuctParams &p, hipStream_t s);
 void launch_c4_puct_reroot(const C4PuctParams &p, hipStream_t s);
 void launch_c4_puct_forget(const C4PuctParams &p, hipStream_t s);
+void launch_c4_puct_forget_fresh(const C4PuctParams &p, const int32_t *slot, hipStream_t s);
 void launch_c4_puct_select(const C4PuctParams &p, hipStream_t s);
 void launch_c4_puct_backup(const C4PuctParams &p, hipStream_t s);
 void launch_c4_puct_end(const C4PuctParams &p, hipStream_t s);
@@ -379,6 +380,7 @@ void launch_chess_hp_expand(const ChessParams &p, hipStream_t s);
 void launch_chess_puct_begin(const ChessParams &p, hipStream_t s);
 void launch_chess_puct_reroot(const ChessParams &p, hipStream_t s);
 void launch_chess_puct_forget(const ChessParams &p, hipStream_t s);
+void launch_chess_puct_forget_fresh(const ChessParams &p, const int32_t *slot, hipStream_t s);
 void launch_chess_puct_select(const ChessParams &p, hipStream_t s);
 void launch_chess_puct_backup(const ChessParams &p, hipStream_t s);
 void launch_chess_puct_end(const ChessParams &p, hipStream_t s);
@@ -426,6 +428,8 @@ enum : int { kTrajPositions = ZC_TRAJ_POSITIONS, kTrajGames = ZC_TRAJ_GAMES, kTr
 void launch_traj_record(int n, const zc_traj_buffers &b, void *states, const int16_t *moves, int32_t *results,
                         const int32_t *flags, const int32_t *rep, hipStream_t s);
 size_t traj_steps_scratch_bytes(int n, int K);
+void launch_traj_openings(int n, const zc_traj_buffers &b, const void *book, int book_rows, int share, void *roots,
+                          hipStream_t s);
 void launch_traj_record_steps(int n, int K, const zc_traj_buffers &b, const void *states, const int16_t *moves,
                               const int32_t *results, const int32_t *reached, void *scratch, hipStream_t s);
 void launch_traj_policy_append(int n, const zc_traj_buffers &b, const zc_traj_policy_buffers &q, const int32_t *na,

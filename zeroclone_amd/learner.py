@@ -18,13 +18,18 @@ device move generator, so on the CPU a chess minibatch carries no legal lists (e
 """
 from __future__ import annotations
 
+import copy
 from dataclasses import dataclass, field
+from typing import TYPE_CHECKING
 
 import numpy as np
 import torch
 
 from . import _native, nets
 from .selfplay import TrajBatch, schedule_hyperparams, simulate_games
+
+if TYPE_CHECKING:   # arena.py imports the pools, and a gate only holds one
+    from .arena import C4Arena, ChessArena
 
 GAMES = {"c4": (_native.ZC_TRAIN_C4, 3, 7, 7, (2, 6, 7)),                               # code, row words, stride,
          "chess": (_native.ZC_TRAIN_CHESS, 9, _native.CHESS_MAX_MOVES, 4096, (17, 8, 8))}  # logits width, planes
@@ -465,14 +470,34 @@ def inference_form(model, device, dtype=torch.float16):
     raise TypeError("set_network takes a ValueNetwork or a PolicyValueNetwork")
 
 
+@dataclass
+class Gate:
+    """The gate of `full_training_run(gate=)`: after a cycle's training the trained network plays
+    `games` games against the network it was trained from in `arena` (a `C4Arena` / `ChessArena`
+    of the model's search, best with openings= so that the games differ) and replaces it in the
+    self-play pool only at a score of at least `threshold` — scripts/evaluate.py:evaluate_pair's
+    win rate with draws as one half.  The arena's sims and c are its own, not the schedule's.
+    history: one (cycle, ArenaResult, promoted) per cycle."""
+    arena: "C4Arena | ChessArena"
+    games: int
+    threshold: float = 0.55
+    history: list = field(default_factory=list)
+
+
 def full_training_run(pool, model, cycles: int, *, epochs: int = 4, batch_size: int = 256, games_cap: int = 2000,
                       sims_cap: int = 800, init_lr: float = 3e-4, lr_decay: float = 0.95, lr_floor: float = 1e-5,
-                      replay: ReplaySet | None = None, game: str | None = None, train_fn=None) -> list[TrainResult]:
+                      replay: ReplaySet | None = None, game: str | None = None, train_fn=None,
+                      gate: Gate | None = None) -> list[TrainResult]:
     """scripts/train.py:full_training_run (:191-244) on a device pool built with `model`'s
     inference form.  Per cycle: `schedule_hyperparams`; the pool's `sims` and `c` (and a PUCT
     search's c_puct) set from it — a schedule beyond the pool's `max_sims` refuses, the trees
     were sized at construction; `simulate_games`; the finished games as a `TrainingSet`;
     `ReplaySet.update`; `train` at the cycle's learning rate; `pool.set_network(model)`.
+    With gate= the hand-back is conditional: the model's state_dict is copied before the cycle's
+    `train`; afterwards a copy of the model holding that state (the incumbent) plays the trained
+    model in `gate.arena` (`set_networks(model, incumbent)`, `play(gate.games)`); at a score of at
+    least `gate.threshold` the pool gets the trained network, else the model takes the copied state
+    back and the pool goes on playing the incumbent; `gate.history` gets the cycle's entry.
     Returns the cycles' `TrainResult`s.  The reference's log-file tee and checkpoint renaming are
     the caller's.  game: "c4" / "chess" (default: by the pool's row size); train_fn: `train`'s
     stand-in (tests)."""
@@ -492,6 +517,20 @@ def full_training_run(pool, model, cycles: int, *, epochs: int = 4, batch_size: 
         simulate_games(pool, hp["games"])
         batch = pool.last_batch
         new = TrainingSet.from_batch(batch, game or ("c4" if batch.rows.shape[1] == 3 else "chess"))
+        if gate is not None:   # on the model's device: what the incumbent is made of
+            snapshot = {k: v.detach().clone() for k, v in model.state_dict().items()}
         results.append(train_fn(model, replay.update(new), epochs=epochs, lr=hp["lr"], batch_size=batch_size))
-        pool.set_network(model)
+        if gate is None:
+            pool.set_network(model)
+            continue
+        incumbent = copy.deepcopy(model)
+        incumbent.load_state_dict(snapshot)
+        gate.arena.set_networks(model, incumbent)
+        res = gate.arena.play(gate.games)
+        promoted = res.score >= gate.threshold
+        if promoted:
+            pool.set_network(model)
+        else:
+            model.load_state_dict(snapshot)
+        gate.history.append((cycle, res, promoted))
     return results

@@ -12,11 +12,12 @@ Trajectories never leave the device while games are played (`Trajectories`,
 zc_traj_record_async): every position is appended to its slot's game in HBM; a finished game
 is labelled exactly as Engine.get_dataset (engine.py:60-89) labels it and copied to a
 device pool, and its slot restarts from the opening (or goes idle once simulate_games'
-quota of games has started).  `take()` returns the pool's games in start order as device
-tensors; `gather_positions` all-gathers every rank's positions (counts first, then a padded
-payload) over torch.distributed — RCCL over xGMI on the GPUs, gloo on CPU — the one
-collective of the scale-out path; `ReplayBuffer` is
-scripts/train.py:_update_replay (:27-50) over device tensors.
+quota of games has started); with `openings=` a pool restarts its slots from a book of openings
+instead, by game number (zc_traj_openings_async, `openings_from_games`).  `take()` returns the
+pool's games in start order as device tensors; `gather_positions` all-gathers every rank's
+positions (counts first, then a padded payload) over torch.distributed — RCCL over xGMI on the
+GPUs, gloo on CPU — the one collective of the scale-out path; `ReplayBuffer`
+is scripts/train.py:_update_replay (:27-50) over device tensors.
 """
 from __future__ import annotations
 
@@ -256,6 +257,15 @@ class Trajectories:
             _native.check(_native.lib().zc_traj_policy_commit_async(
                 self.n, ctypes.byref(self._buf), ctypes.byref(self._pol), ctypes.c_void_p(stream or None)))
 
+    def seed_openings(self, book: torch.Tensor, share: int, roots: torch.Tensor, stream: int = 0):
+        """zc_traj_openings_async: every slot whose game has only its first position takes row
+        (game number // share) % len(book) of `book` ([N, W] int64 on the device) as its row of
+        `roots` and as its history's position 0.  After record() (and its policy commit) of a step
+        and after start(); idle slots and games in progress are not touched."""
+        _native.check(_native.lib().zc_traj_openings_async(
+            self.n, ctypes.byref(self._buf), ctypes.c_void_p(book.data_ptr()), int(book.shape[0]), int(share),
+            ctypes.c_void_p(roots.data_ptr()), ctypes.c_void_p(stream or None)))
+
     def record_policy(self, na: torch.Tensor, root_moves: torch.Tensor | None = None, stream: int = 0):
         """After a step's search, before its play and record(): the root visit counts
         na [n, stride] int32 (d_out_root_na) of the positions searched; chess passes the roots'
@@ -423,6 +433,83 @@ def _check_mfma(value_nets, puct_nets, what="eval_cache / eval_merge need", whos
                              f"torch module cannot be {verb}")
 
 
+_NO_FUSED_BOOK = ("the fused launches refill from the one opening inside the kernel: a pool with a book of openings "
+                  "plays with step()")
+_C4_BOTTOM = sum(1 << (7 * c) for c in range(7))
+_C4_BOARD = sum(0x3F << (7 * c) for c in range(7))
+
+
+def _book(openings, game: str) -> torch.Tensor:
+    """A pool's openings= argument as [N, W] int64 rows (W = 3: Connect4, 9: chess), where it
+    was given; or its refusal.  Connect4 takes a [N, 3] int64 tensor, chess a [N, 72] uint8 tensor
+    or a list of FEN strings."""
+    if game == "chess" and isinstance(openings, (list, tuple)):
+        if not openings or not all(isinstance(f, str) for f in openings):
+            raise ValueError("openings: a list of FEN strings must hold at least one, and nothing else")
+        rows = np.stack([np.frombuffer(_native.chess_from_fen(f).tobytes(), np.uint8) for f in openings])
+        openings = torch.from_numpy(rows.copy())
+    width, dtype = (72, torch.uint8) if game == "chess" else (3, torch.int64)
+    if not torch.is_tensor(openings) or openings.dim() != 2 or openings.shape[1] != width or openings.dtype != dtype:
+        raise ValueError(f"openings must be a [N, {width}] {str(dtype).split('.')[1]} tensor"
+                         + (" or a list of FEN strings" if game == "chess" else ""))
+    if openings.shape[0] < 1:
+        raise ValueError("openings: an empty book")
+    if openings.shape[0] > 0x7FFFFFFF:
+        raise ValueError("openings: more rows than an int32 counts")
+    return openings.contiguous().view(torch.int64) if game == "chess" else openings.contiguous()
+
+
+def check_c4_book(book: torch.Tensor):
+    """Refuses a Connect4 book ([N, 3] int64: stones of the side with turn 0, of the other side,
+    turn) that holds a row no game reaches or none can go on from, naming the first: overlapping
+    stones, sentinel bits (a column's seventh bit, anything above bit 48), a gap under a stone, a
+    turn that is not count(stones[0]) - count(stones[1]) in {0, 1}, four in a row, a full board.
+    Torch operations on the book's device; one read back."""
+    s0, s1, turn = book[:, 0], book[:, 1], book[:, 2]
+    occ = s0 | s1
+    bits = torch.arange(49, device=book.device)
+    count = lambda x: ((x[:, None] >> bits) & 1).sum(1)   # noqa: E731
+
+    def four(b):
+        out = torch.zeros_like(b, dtype=torch.bool)
+        for d in (1, 7, 6, 8):
+            m = b & (b >> d)
+            out |= (m & (m >> (2 * d))) != 0
+        return out
+    n0, n1 = count(s0 & _C4_BOARD), count(s1 & _C4_BOARD)
+    faults = [("overlapping stones", (s0 & s1) != 0),
+              ("sentinel bits set", ((occ & ~_C4_BOARD) != 0)),
+              ("a gap under a stone", (occ & ~_C4_BOTTOM & ~(occ << 1)) != 0),
+              ("turn is not count(stones[0]) - count(stones[1]) in {0, 1}",
+               (turn != n0 - n1) | (turn < 0) | (turn > 1)),
+              ("a side has four in a row", four(s0) | four(s1)),
+              ("a full board", n0 + n1 >= 42)]
+    bad = torch.stack([f for _, f in faults]).cpu()
+    rows = bad.any(0).nonzero()
+    if rows.numel():
+        r = int(rows[0])
+        raise ValueError(f"openings: row {r}: " + next(name for (name, _), b in zip(faults, bad[:, r]) if b))
+
+
+def openings_from_games(batch: TrajBatch, ply: int, limit: int | None = None) -> torch.Tensor:
+    """A book from finished games: the distinct rows at position index `ply` of every game with
+    more than ply + 1 positions (such a position is never a game's last, so never terminal), in
+    torch.unique(dim=0)'s order over the row words — the same games give the same book — cut to
+    the first `limit`.  Connect4: [N, 3] int64; chess: [N, 72] uint8.  On the batch's device."""
+    if ply < 0:
+        raise ValueError("ply must be >= 0")
+    if limit is not None and limit < 0:
+        raise ValueError("limit must be >= 0 or None")
+    g = batch.games
+    first = g[g[:, 4] > ply + 1, 3] + ply
+    rows = batch.rows[first]
+    if rows.shape[0]:
+        rows = torch.unique(rows, dim=0)
+    if limit is not None:
+        rows = rows[:limit]
+    return rows.contiguous().view(torch.uint8) if rows.shape[1] == 9 else rows
+
+
 class _SelfPlayPool:
     """What `C4SelfPlay` and `ChessSelfPlay` share: G games of one GPU, the engine and its game
     streams, the three-way search choice of a step (the game's own search kernel, a value
@@ -441,13 +528,20 @@ class _SelfPlayPool:
     POOL_ROWS: int       # pooled positions reserved per game of games_cap
     FUSED_SEARCH: str    # the search of run() / run_pooled(), for their refusal
     record = True        # Connect4 alone can play unrecorded
+    _openings_share = 1  # games in a row that start from one opening of the book (an arena: 2)
 
     def __init__(self, games: int, sims: int, c: float, batch_size: int, seed: int, rank: int, device,
                  temperature: float, record_policy: bool, init_row: torch.Tensor, max_len: int,
                  games_cap: int | None, pi_slot_cap: int | None, pi_pool_cap: int | None,
                  record: bool = True, max_sims: int | None = None, fused_policy: bool = False,
-                 eval_cache: int = 0, eval_merge: bool = False):
-        """The refusals come before the engine: they need no GPU."""
+                 eval_cache: int = 0, eval_merge: bool = False, book: torch.Tensor | None = None):
+        """The refusals come before the engine: they need no GPU.  book: the game's openings=
+        argument as `_book` returns it."""
+        if book is not None and not record:   # the rule goes by the recorder's game numbers
+            raise ValueError("openings needs the trajectory recorder (record=True): a slot's opening goes by its "
+                             "game number")
+        if book is not None and fused_policy:
+            raise ValueError("openings with fused_policy: " + _NO_FUSED_BOOK)
         if int(eval_cache) < 0:
             raise ValueError(f"eval_cache is a number of entries: 0 (off) or positive (got {eval_cache})")
         self.eval_cache, self.eval_merge, self._caches = int(eval_cache), bool(eval_merge), []
@@ -476,6 +570,7 @@ class _SelfPlayPool:
             self.traj = Trajectories(games, init_row, max_len, cap, cap * self.POOL_ROWS, self.dev,
                                      policy_width=self.POLICY_WIDTH if record_policy else None,
                                      pi_slot_cap=pi_slot_cap, pi_pool_cap=pi_pool_cap)
+        self.book = book.to(self.dev) if book is not None else None
         self.vs = self.value_fn = self.ps = self.net_fn = None
         self.temperature = float(temperature)
         self._run_k = self._ticket = None
@@ -572,7 +667,19 @@ class _SelfPlayPool:
         rec = self._play(s)
         if rec is not None:
             self.traj.record(*rec, stream=s)
+            self._seed_openings(s)
         return self.results
+
+    def _seed_openings(self, s: int):
+        """With a book: the slots that hold a game's first position — after start(), or refilled
+        by the record just enqueued on `s` — take their game's opening, roots and history.  With
+        reuse_tree those slots' kept trees are dropped on the device (zc_*_puct_forget_fresh): an
+        opening may sit one or two plies below the last root of the game that ended, and the
+        search would re-root into a tree of another game, with its repetition terminals."""
+        if self.book is not None:
+            self.traj.seed_openings(self.book, self._openings_share, self.roots, stream=s)
+            if getattr(self, "reuse_tree", False):
+                self.ps.forget_fresh(self.traj.slot, s)
 
     def capture_step(self):
         """One whole step (search with its network, play, record) as a HIP graph; each
@@ -621,6 +728,8 @@ class _SelfPlayPool:
         with the outputs and registered with the engine (`_visits`) before the launch, and the
         recording takes it along."""
         name = "run" if budget is None else "run_pooled"
+        if self.book is not None:
+            raise ValueError(f"{name}(): " + _NO_FUSED_BOOK)
         if self.record_policy and not self.fused_policy:
             raise ValueError(_NO_FUSED_POLICY)
         if self.traj is not None and self.traj.quota != _UNLIMITED:
@@ -711,9 +820,15 @@ class C4SelfPlay(_SelfPlayPool):
                  net=None, puct_net=None, temperature: float = 1.0, puct_seed: int = 1, streams: int = 1,
                  record_policy: bool = False, pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
                  reuse_tree: bool = False, tree_nodes: int | None = None, fused_policy: bool = False,
-                 puct_args: dict | None = None, eval_cache: int = 0, eval_merge: bool = False):
+                 puct_args: dict | None = None, eval_cache: int = 0, eval_merge: bool = False, openings=None):
         """record_policy: every step()'s root visit counts go with the positions into the
         trajectories (TrajBatch.pi / policy_targets(7)), in every search mode.
+        openings: a book of openings, a [N, 3] int64 tensor of positions (`openings_from_games`
+        makes one): game g starts from row g % N instead of the empty board
+        (zc_traj_openings_async after start() and after every step's record).  The book is checked
+        once (`check_c4_book`).  step() and capture_step() only: the fused launches refill inside
+        the kernel from the empty board, so run(), run_pooled(), drain(), fused_policy and
+        record=False refuse.
         eval_cache (net= / puct_net=, MFMA networks): the entries of a device-resident evaluation
         cache (zeroclone_amd/evalcache.py), split evenly over the streams; a leaf whose position
         was evaluated before takes the stored value and logits and the network runs on the
@@ -735,6 +850,9 @@ class C4SelfPlay(_SelfPlayPool):
         `tree_nodes` nodes (default min(2 * sims, 65534)), and a search whose kept nodes leave
         no room for its own starts afresh.  start() and adopt() drop the kept trees."""
         _check_eval_merge(eval_merge, net, puct_net)
+        book = _book(openings, "c4") if openings is not None else None
+        if book is not None:
+            check_c4_book(book)
         if reuse_tree:
             if puct_net is None:
                 raise ValueError("reuse_tree keeps the PUCT search's tree: it needs puct_net")
@@ -746,7 +864,7 @@ class C4SelfPlay(_SelfPlayPool):
                          torch.zeros(24, dtype=torch.uint8), self.MAX_LEN, games_cap, pi_slot_cap, pi_pool_cap,
                          record=record,
                          max_sims=(tree_nodes or min(2 * sims, 65534)) if reuse_tree else None,
-                         fused_policy=fused_policy, eval_cache=eval_cache, eval_merge=eval_merge)
+                         fused_policy=fused_policy, eval_cache=eval_cache, eval_merge=eval_merge, book=book)
         self.reuse_tree = bool(reuse_tree)
         self.record = record
         self.roots = torch.zeros((games, 3), dtype=torch.int64, device=self.dev)
@@ -755,6 +873,7 @@ class C4SelfPlay(_SelfPlayPool):
         self._networks(net, valued.C4ValuedSearch, {}, streams,
                        puct_net, valued.C4PuctSearch,
                        dict(seed=puct_seed, reuse=self.reuse_tree, **(puct_args or {})), streams)
+        self._seed_openings(self._stream(None))
 
     def start(self, quota: int | None = None):
         """Every slot back to the opening; with a quota, slots beyond it idle and finished
@@ -769,6 +888,7 @@ class C4SelfPlay(_SelfPlayPool):
             self.ps.forget()
         if self.traj is not None:
             self.traj.start(quota, games_cap=quota)
+            self._seed_openings(self._stream(None))
 
     def step_search(self, stream: int | None = None) -> torch.Tensor:
         if self.carry_pending:
@@ -914,9 +1034,13 @@ class ChessSelfPlay(_SelfPlayPool):
                  puct_streams: int = 1, streams: int = 1, record_policy: bool = False,
                  pi_slot_cap: int | None = None, pi_pool_cap: int | None = None,
                  reuse_tree: bool = False, tree_nodes: int | None = None, fused_policy: bool = False,
-                 puct_args: dict | None = None, eval_cache: int = 0, eval_merge: bool = False):
+                 puct_args: dict | None = None, eval_cache: int = 0, eval_merge: bool = False, openings=None):
         """record_policy: every step()'s root visit counts go with the positions into the
         trajectories (TrajBatch.pi / policy_targets(4096)), in every search mode.
+        openings: as C4SelfPlay's; a [N, 72] uint8 tensor of zc_chess_state rows or a list of FEN
+        strings.  An opening starts with empty repetition histories, as init_fen= does, and its
+        fifty-move counter and castling rights are the row's own.  A row that
+        zc_chess_terminal_async flags (no legal move, the fifty-move rule reached) is refused.
         eval_cache: as C4SelfPlay's (with the convolutional head an entry holds 8 KB of logits).
         eval_merge: as C4SelfPlay's.
         puct_args: ChessPuctSearch's c_puct / dirichlet_alpha / dirichlet_eps, where its defaults
@@ -937,6 +1061,7 @@ class ChessSelfPlay(_SelfPlayPool):
         _check_eval_merge(eval_merge, net, puct_net)
         if reuse_tree and puct_net is None:
             raise ValueError("reuse_tree keeps the PUCT search's tree: it needs puct_net")
+        book = _book(openings, "chess") if openings is not None else None
         init = _native.chess_from_fen(init_fen) if init_fen else _native.chess_init()
         init = torch.from_numpy(np.frombuffer(init.tobytes(), np.uint8).reshape(1, 72).copy())
         max_len = 2 * hist_cap + 1
@@ -946,7 +1071,7 @@ class ChessSelfPlay(_SelfPlayPool):
         super().__init__(games, sims, c, batch_size, seed, rank, device, temperature, record_policy,
                          init, max_len, games_cap, pi_slot_cap, pi_pool_cap,
                          max_sims=(tree_nodes or min(2 * sims, 65534)) if reuse_tree else None,
-                         fused_policy=fused_policy, eval_cache=eval_cache, eval_merge=eval_merge)
+                         fused_policy=fused_policy, eval_cache=eval_cache, eval_merge=eval_merge, book=book)
         self.reuse_tree = bool(reuse_tree)
         self.eng.chess_reserve()
         self.policy, self.freedom = int(policy), float(freedom)
@@ -970,6 +1095,25 @@ class ChessSelfPlay(_SelfPlayPool):
         if record_policy:
             self.root_moves = torch.zeros((games, _native.CHESS_MAX_MOVES), dtype=torch.int16, device=self.dev)
             self.root_counts = torch.zeros(games, dtype=torch.int32, device=self.dev)
+        if self.book is not None:
+            self._check_book()
+            self._seed_openings(self._stream(None))
+
+    def _check_book(self):
+        """Once per book: zc_chess_terminal_async over its rows, read back."""
+        flags = torch.zeros(self.book.shape[0], dtype=torch.int32, device=self.dev)
+        self.eng.chess_terminal_async(self.book.shape[0], self.book.data_ptr(), flags.data_ptr(), self._stream(None))
+        bad = flags.cpu().nonzero()
+        if bad.numel():
+            r = int(bad[0])
+            f = int(flags[r])
+            why = [name for bit, name in ((_native.ZC_CHESS_WIN, "the side to move is mated"),
+                                          (_native.ZC_CHESS_STALEMATE, "no legal move"),
+                                          (_native.ZC_CHESS_FIFTY, "the fifty-move rule is reached"),
+                                          (_native.ZC_CHESS_OVERFLOW, "more legal moves than a move list holds"))
+                   if f & bit]
+            self.close()
+            raise ValueError(f"openings: row {r} is not a position a game starts from: " + ", ".join(why))
 
     def start(self, quota: int | None = None):
         self.roots.copy_(self.init_row.expand_as(self.roots))
@@ -977,6 +1121,7 @@ class ChessSelfPlay(_SelfPlayPool):
         if self.reuse_tree:
             self.ps.forget()
         self.traj.start(quota, games_cap=quota)
+        self._seed_openings(self._stream(None))
 
     def _search(self, s: int):
         self.eng.chess_search_async(0, self.G, self.roots.data_ptr(), self.sims, self.c, self.bs, self.policy,

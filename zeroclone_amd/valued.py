@@ -527,6 +527,12 @@ class ChessPuctSearch(_PuctSearch):
         games), stream-ordered: their next search starts afresh."""
         self.eng.chess_puct_forget(first_game, self.n if n is None else n, _stream(self.dev))
 
+    def forget_fresh(self, slot: torch.Tensor, stream: int | None = None):
+        """Drop the kept trees of the games whose recorder slot (Trajectories.slot, [n, 4] int32)
+        holds a game at its first position, on the device (stream: default torch's current one):
+        a refilled slot's tree belongs to the game that ended."""
+        self.eng.chess_puct_forget_fresh(0, self.n, slot.data_ptr(), stream if stream is not None else _stream(self.dev))
+
     def _begin(self, first, roots, sims, temperature, s):
         e, args = self.eng, (first, self.n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps, self.seed,
                              self.search_no.data_ptr())
@@ -580,6 +586,12 @@ class C4PuctSearch(_PuctSearch):
         """Drop the kept trees of games [first_game, first_game + n) (default: this search's n
         games), stream-ordered: their next search starts afresh."""
         self.eng.c4_puct_forget(first_game, self.n if n is None else n, _stream(self.dev))
+
+    def forget_fresh(self, slot: torch.Tensor, stream: int | None = None):
+        """Drop the kept trees of the games whose recorder slot (Trajectories.slot, [n, 4] int32)
+        holds a game at its first position, on the device (stream: default torch's current one):
+        a refilled slot's tree belongs to the game that ended."""
+        self.eng.c4_puct_forget_fresh(0, self.n, slot.data_ptr(), stream if stream is not None else _stream(self.dev))
 
     def _begin(self, first, roots, sims, temperature, s):
         e, args = self.eng, (first, self.n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps, self.seed,
