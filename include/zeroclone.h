@@ -606,7 +606,8 @@ int zc_debug_c4_puct_tree(zc_engine *eng, int32_t game, int32_t max_nodes, void 
 
 /* ---- Value-network layers on the matrix cores (models/chess_value/network.py:24-45) -----
  * The residual tower of ValueNetwork with BatchNorm folded into the convolutions, NHWC fp16
- * activations ([n][h][w][c], a pixel's channels contiguous), 128 output channels.
+ * activations ([n][h][w][c], a pixel's channels contiguous), 128 output channels (64: the _w_
+ * family below).
  *   zc_net_conv3x3_async: out = act(conv3x3(in, weight) + bias (+ residual)), padding 1;
  *     weight [9][128][cin] fp16 (tap = ky*3+kx, then output channel, then input channel),
  *     bias [128] f32, residual NULL or [n][h][w][128] fp16, relu 0/1.  Shapes: (h, w) in
@@ -687,6 +688,50 @@ int zc_net_planes_to_nhwc_async(int32_t n, int32_t cin, int32_t hw, int32_t cpad
                                 void *hip_stream);
 int zc_net_value_head_async(int32_t n, int32_t hw, const void *d_act, const float *d_fc_w, float fc_b, double *d_values,
                             void *hip_stream);
+/* ---- The _w_ family: the same layers at either covered width --------------------------
+ * The entry points above with the network's width, `channels`, as their first argument: 128 is
+ * the call above, argument for argument and bit for bit; 64 runs the 64-channel kernels
+ * (csrc/net_conv64.hip); every other width is ZC_EINVAL with a message naming the covered widths,
+ * 64 and 128.  One family with a width argument rather than a second family of names: a caller
+ * that holds a network of either width makes one call, and a third width would add no symbol.
+ * At 64 channels every "128" above reads 64 — weight [9][64][cin], bias [64] (per layer of the
+ * tower: [nconv][64]), activations [n][h*w][64], d_fc_w [64] — and:
+ *   zc_net_conv3x3_pack_w_async: cin in {32, 64};
+ *     packed[(((tap*(cin/32) + j)*4 + mt)*64 + lane)*8 + e] =
+ *     weight[tap][mt*16 + lane%16][j*32 + 8*(lane/16) + e] (one contiguous 1-KB operand fragment of
+ *     v_mfma_f32_16x16x32_f16 per (tap, j, mt)); same size as weight.
+ *   zc_net_conv3x3_packed_w_async: out = rn16(act((acc + bias) + residual)), rounded once; cin in
+ *     {32, 64}, (h, w) in {(8, 8), (6, 7)}; d_in, d_packed, d_bias 16-byte and d_residual, d_out
+ *     8-byte aligned.  The yardstick of the fused tower, which stores the same bits; not tuned.
+ *   zc_net_tower_w_async: d_packed = stem 9*cin0*64 halfs, then 9*64*64 per layer; cin0 = 32,
+ *     nconv odd, (h, w) in {(8, 8), (6, 7)}.  128-pixel tiles, activations in 42 KB of LDS.
+ *   zc_net_tower_policy_w_async: zc_net_tower_policy_ex_async; the 1x1 conv is 64 ->
+ *     policy_channels (32 or 64), d_pw = [policy_channels / 16][2][64][8] fp16 fragments
+ *     (nets.pack_policy_1x1 of a [policy_channels, 64] weight).
+ *   zc_net_tower_counted_w_async, zc_net_tower_policy_counted_w_async: the counted forms.
+ *   zc_net_value_head_w_async: d_act = [n][hw][64] fp16, 16-byte aligned. */
+int zc_net_conv3x3_pack_w_async(int32_t channels, int32_t cin, const void *d_weight, void *d_packed, void *hip_stream);
+int zc_net_conv3x3_packed_w_async(int32_t channels, int32_t n_boards, int32_t h, int32_t w, int32_t cin,
+                                  const void *d_in, const void *d_packed_weight, const float *d_bias,
+                                  const void *d_residual, void *d_out, int32_t relu, void *hip_stream);
+int zc_net_tower_w_async(int32_t channels, int32_t n_boards, int32_t h, int32_t w, int32_t cin0, int32_t nconv,
+                         const void *d_in, const void *d_packed_weights, const float *d_biases, void *d_out,
+                         const float *d_fc_w, float fc_b, double *d_values, void *hip_stream);
+int zc_net_tower_policy_w_async(int32_t channels, int32_t n_boards, int32_t h, int32_t w, int32_t cin0, int32_t nconv,
+                                const void *d_in, const void *d_packed_weights, const float *d_biases,
+                                const float *d_fc_w, float fc_b, double *d_values, const void *d_pw, const float *d_pb,
+                                int32_t policy_channels, int32_t relu, void *d_pout, void *hip_stream);
+int zc_net_tower_counted_w_async(int32_t channels, int32_t n_boards, int32_t h, int32_t w, int32_t cin0, int32_t nconv,
+                                 const void *d_in, const void *d_packed_weights, const float *d_biases, void *d_out,
+                                 const float *d_fc_w, float fc_b, double *d_values, const int32_t *d_count,
+                                 void *hip_stream);
+int zc_net_tower_policy_counted_w_async(int32_t channels, int32_t n_boards, int32_t h, int32_t w, int32_t cin0,
+                                        int32_t nconv, const void *d_in, const void *d_packed_weights,
+                                        const float *d_biases, const float *d_fc_w, float fc_b, double *d_values,
+                                        const void *d_pw, const float *d_pb, int32_t policy_channels, int32_t relu,
+                                        void *d_pout, const int32_t *d_count, void *hip_stream);
+int zc_net_value_head_w_async(int32_t channels, int32_t n, int32_t hw, const void *d_act, const float *d_fc_w,
+                              float fc_b, double *d_values, void *hip_stream);
 
 /* ---- self-play trajectories on the device ---------------------------
  * Replaces the host half of self-play data collection: Engine.play_move's history append

@@ -311,6 +311,35 @@ SIGNATURES = [
                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("zc_net_value_head_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
+    # the _w_ family: the calls above with the width (64 or 128 channels) as their first argument
+    ("zc_net_conv3x3_pack_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p]),
+    ("zc_net_conv3x3_packed_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                     ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                                     ctypes.c_void_p]),
+    ("zc_net_tower_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
+                                            ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_net_tower_policy_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                   ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_net_tower_counted_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("zc_net_tower_policy_counted_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                           ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                           ctypes.c_void_p]),
+    ("zc_net_value_head_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
     ("zc_traj_record_async", ctypes.c_int, [ctypes.c_int32, P(TrajBuffers), ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("zc_traj_openings_async", ctypes.c_int, [ctypes.c_int32, P(TrajBuffers), ctypes.c_void_p, ctypes.c_int32,

@@ -1793,9 +1793,10 @@ int zc_net_conv3x3_packed_async(int32_t n, int32_t h, int32_t w, int32_t cin, co
 // The five tower entry points: the checks, then launch_net_tower.  policy: the forms with a policy
 // head, which need it and the value head whole (d_out: none); the others need d_out or d_values,
 // and d_fc_w with d_values.  ex: the forms that take policy_channels (32 or 64) and relu, and read
-// d_pb 16 bytes at a time.  counted: the forms that take their row count from d_count.
-static int net_tower(bool policy, bool ex, bool counted, int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv,
-                     const void *d_in, const void *d_packed, const float *d_bias, void *d_out, const float *d_fc_w,
+// d_pb 16 bytes at a time.  counted: the forms that take their row count from d_count.  channels:
+// 128 (the entry points above the _w_ family) or 64 (net_conv64.hip), checked by the caller.
+static int net_tower(int32_t channels, bool policy, bool ex, bool counted, int32_t n, int32_t h, int32_t w,
+                     int32_t cin0, int32_t nconv, const void *d_in, const void *d_packed, const float *d_bias, void *d_out, const float *d_fc_w,
                      float fc_b, double *d_values, const void *d_pw, const float *d_pb, int32_t policy_channels,
                      int32_t relu, void *d_pout, const int32_t *d_count, void *hip_stream) {
     bool ok = n >= 0 && !(((uintptr_t)d_packed | (uintptr_t)d_in | (uintptr_t)d_bias) & 15) &&
@@ -1809,6 +1810,15 @@ static int net_tower(bool policy, bool ex, bool counted, int32_t n, int32_t h, i
     if (counted) ok = ok && d_count && !((uintptr_t)d_count & 3);
     if (!ok) return fail(ZC_EINVAL, "bad argument");
     if (!n) return ZC_OK;
+    if (channels == 64) {
+        if (!zc::launch_net64_tower(n, h, w, cin0, nconv, d_in, d_packed, d_bias, d_out, d_values ? d_fc_w : nullptr,
+                                    fc_b, d_values, d_pw, d_pb, d_pout, (hipStream_t)hip_stream, policy_channels, relu,
+                                    d_count))
+            return fail(ZC_EINVAL, "64-channel tower shape (h %d, w %d, cin0 %d, %d convs) not supported", h, w, cin0,
+                        nconv);
+        ZC_HIP(hipGetLastError());
+        return ZC_OK;
+    }
     if (!zc::launch_net_tower(n, h, w, cin0, nconv, d_in, d_packed, d_bias, d_out, d_values ? d_fc_w : nullptr, fc_b,
                               d_values, d_pw, d_pb, d_pout, (hipStream_t)hip_stream, policy_channels, relu, d_count))
         return fail(ZC_EINVAL, "tower shape (h %d, w %d, cin0 %d, %d convs) not supported", h, w, cin0, nconv);
@@ -1819,14 +1829,14 @@ static int net_tower(bool policy, bool ex, bool counted, int32_t n, int32_t h, i
 int zc_net_tower_async(int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv, const void *d_in,
                        const void *d_packed, const float *d_bias, void *d_out, const float *d_fc_w, float fc_b,
                        double *d_values, void *hip_stream) {
-    return net_tower(false, false, false, n, h, w, cin0, nconv, d_in, d_packed, d_bias, d_out, d_fc_w, fc_b, d_values,
+    return net_tower(128, false, false, false, n, h, w, cin0, nconv, d_in, d_packed, d_bias, d_out, d_fc_w, fc_b, d_values,
                      nullptr, nullptr, 32, 1, nullptr, nullptr, hip_stream);
 }
 
 int zc_net_tower_policy_async(int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv, const void *d_in,
                               const void *d_packed, const float *d_bias, const float *d_fc_w, float fc_b,
                               double *d_values, const void *d_pw, const float *d_pb, void *d_pout, void *hip_stream) {
-    return net_tower(true, false, false, n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b, d_values,
+    return net_tower(128, true, false, false, n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b, d_values,
                      d_pw, d_pb, 32, 1, d_pout, nullptr, hip_stream);
 }
 
@@ -1834,14 +1844,14 @@ int zc_net_tower_policy_ex_async(int32_t n, int32_t h, int32_t w, int32_t cin0, 
                                  const void *d_packed, const float *d_bias, const float *d_fc_w, float fc_b,
                                  double *d_values, const void *d_pw, const float *d_pb, int32_t policy_channels,
                                  int32_t relu, void *d_pout, void *hip_stream) {
-    return net_tower(true, true, false, n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b, d_values,
+    return net_tower(128, true, true, false, n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b, d_values,
                      d_pw, d_pb, policy_channels, relu, d_pout, nullptr, hip_stream);
 }
 
 int zc_net_tower_counted_async(int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv, const void *d_in,
                                const void *d_packed, const float *d_bias, void *d_out, const float *d_fc_w, float fc_b,
                                double *d_values, const int32_t *d_count, void *hip_stream) {
-    return net_tower(false, false, true, n, h, w, cin0, nconv, d_in, d_packed, d_bias, d_out, d_fc_w, fc_b, d_values,
+    return net_tower(128, false, false, true, n, h, w, cin0, nconv, d_in, d_packed, d_bias, d_out, d_fc_w, fc_b, d_values,
                      nullptr, nullptr, 32, 1, nullptr, d_count, hip_stream);
 }
 
@@ -1849,7 +1859,7 @@ int zc_net_tower_policy_counted_async(int32_t n, int32_t h, int32_t w, int32_t c
                                       const void *d_packed, const float *d_bias, const float *d_fc_w, float fc_b,
                                       double *d_values, const void *d_pw, const float *d_pb, int32_t policy_channels,
                                       int32_t relu, void *d_pout, const int32_t *d_count, void *hip_stream) {
-    return net_tower(true, true, true, n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b, d_values,
+    return net_tower(128, true, true, true, n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b, d_values,
                      d_pw, d_pb, policy_channels, relu, d_pout, d_count, hip_stream);
 }
 
@@ -1871,6 +1881,93 @@ int zc_net_value_head_async(int32_t n, int32_t hw, const void *d_act, const floa
     if ((uintptr_t)d_act & 15) return fail(ZC_EINVAL, "d_act must be 16-byte aligned (128-channel fp16 NHWC rows)");
     if (!n) return ZC_OK;
     zc::launch_net_value_head(n, hw, d_act, d_fc_w, fc_b, d_values, (hipStream_t)hip_stream);
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+
+// The _w_ family: the entry points above with the network's width as their first argument.  128
+// is the call above, argument for argument; 64 runs net_conv64.hip; every other width is refused.
+static int net_width(int32_t channels) {
+    if (channels == 64 || channels == 128) return ZC_OK;
+    return fail(ZC_EINVAL, "%d channels not supported: the MFMA network kernels cover 64 and 128 channels", channels);
+}
+
+int zc_net_conv3x3_pack_w_async(int32_t channels, int32_t cin, const void *d_weight, void *d_packed,
+                                void *hip_stream) {
+    if (int rc = net_width(channels)) return rc;
+    if (channels == 128) return zc_net_conv3x3_pack_async(cin, d_weight, d_packed, hip_stream);
+    if (!d_weight || !d_packed || ((uintptr_t)d_weight & 15) || ((uintptr_t)d_packed & 15))
+        return fail(ZC_EINVAL, "bad argument");
+    if (!zc::launch_net64_pack_conv_weight(cin, d_weight, d_packed, (hipStream_t)hip_stream))
+        return fail(ZC_EINVAL, "conv3x3 pack: cin %d not supported at 64 channels (32 or 64)", cin);
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+
+int zc_net_conv3x3_packed_w_async(int32_t channels, int32_t n, int32_t h, int32_t w, int32_t cin, const void *d_in,
+                                  const void *d_packed, const float *d_bias, const void *d_residual, void *d_out,
+                                  int32_t relu, void *hip_stream) {
+    if (int rc = net_width(channels)) return rc;
+    if (channels == 128)
+        return zc_net_conv3x3_packed_async(n, h, w, cin, d_in, d_packed, d_bias, d_residual, d_out, relu, hip_stream);
+    // the kernel moves activations 16 and 8 bytes at a time and reads the bias 16 at a time
+    if (n < 0 || (n && (!d_in || !d_packed || !d_bias || !d_out)) ||
+        (((uintptr_t)d_packed | (uintptr_t)d_in | (uintptr_t)d_bias) & 15) ||
+        (((uintptr_t)d_residual | (uintptr_t)d_out) & 7))
+        return fail(ZC_EINVAL, "bad argument");
+    if (!n) return ZC_OK;
+    if (!zc::launch_net64_conv3x3_packed(n, h, w, cin, d_in, d_packed, d_bias, d_residual, d_out, relu ? 1 : 0,
+                                         (hipStream_t)hip_stream))
+        return fail(ZC_EINVAL, "64-channel conv3x3 shape (h %d, w %d, cin %d) not supported", h, w, cin);
+    ZC_HIP(hipGetLastError());
+    return ZC_OK;
+}
+
+int zc_net_tower_w_async(int32_t channels, int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv,
+                         const void *d_in, const void *d_packed, const float *d_bias, void *d_out,
+                         const float *d_fc_w, float fc_b, double *d_values, void *hip_stream) {
+    if (int rc = net_width(channels)) return rc;
+    return net_tower(channels, false, false, false, n, h, w, cin0, nconv, d_in, d_packed, d_bias, d_out, d_fc_w, fc_b,
+                     d_values, nullptr, nullptr, 32, 1, nullptr, nullptr, hip_stream);
+}
+
+int zc_net_tower_policy_w_async(int32_t channels, int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv,
+                                const void *d_in, const void *d_packed, const float *d_bias, const float *d_fc_w,
+                                float fc_b, double *d_values, const void *d_pw, const float *d_pb,
+                                int32_t policy_channels, int32_t relu, void *d_pout, void *hip_stream) {
+    if (int rc = net_width(channels)) return rc;
+    return net_tower(channels, true, true, false, n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b,
+                     d_values, d_pw, d_pb, policy_channels, relu, d_pout, nullptr, hip_stream);
+}
+
+int zc_net_tower_counted_w_async(int32_t channels, int32_t n, int32_t h, int32_t w, int32_t cin0, int32_t nconv,
+                                 const void *d_in, const void *d_packed, const float *d_bias, void *d_out,
+                                 const float *d_fc_w, float fc_b, double *d_values, const int32_t *d_count,
+                                 void *hip_stream) {
+    if (int rc = net_width(channels)) return rc;
+    return net_tower(channels, false, false, true, n, h, w, cin0, nconv, d_in, d_packed, d_bias, d_out, d_fc_w, fc_b,
+                     d_values, nullptr, nullptr, 32, 1, nullptr, d_count, hip_stream);
+}
+
+int zc_net_tower_policy_counted_w_async(int32_t channels, int32_t n, int32_t h, int32_t w, int32_t cin0,
+                                        int32_t nconv, const void *d_in, const void *d_packed, const float *d_bias,
+                                        const float *d_fc_w, float fc_b, double *d_values, const void *d_pw,
+                                        const float *d_pb, int32_t policy_channels, int32_t relu, void *d_pout,
+                                        const int32_t *d_count, void *hip_stream) {
+    if (int rc = net_width(channels)) return rc;
+    return net_tower(channels, true, true, true, n, h, w, cin0, nconv, d_in, d_packed, d_bias, nullptr, d_fc_w, fc_b,
+                     d_values, d_pw, d_pb, policy_channels, relu, d_pout, d_count, hip_stream);
+}
+
+int zc_net_value_head_w_async(int32_t channels, int32_t n, int32_t hw, const void *d_act, const float *d_fc_w,
+                              float fc_b, double *d_values, void *hip_stream) {
+    if (int rc = net_width(channels)) return rc;
+    if (channels == 128) return zc_net_value_head_async(n, hw, d_act, d_fc_w, fc_b, d_values, hip_stream);
+    if (n < 0 || hw < 1 || (n && (!d_act || !d_fc_w || !d_values))) return fail(ZC_EINVAL, "bad argument");
+    // the head reads whole 128-byte pixel rows (64 fp16 channels) in 16-byte pieces
+    if ((uintptr_t)d_act & 15) return fail(ZC_EINVAL, "d_act must be 16-byte aligned (64-channel fp16 NHWC rows)");
+    if (!n) return ZC_OK;
+    zc::launch_net64_value_head(n, hw, d_act, d_fc_w, fc_b, d_values, (hipStream_t)hip_stream);
     ZC_HIP(hipGetLastError());
     return ZC_OK;
 }
@@ -2091,6 +2188,7 @@ int zc_debug_net_switch(const char *name, int32_t value, int32_t *old) {
     int prev = 0;
     if (!zc::net_switch(name, value, &prev))
         return fail(ZC_EINVAL, "zc_debug_net_switch: unknown switch or value (%s = %d)", name ? name : "(null)", value);
+    if (!strcmp(name, "head_raw")) zc::net64_set_head_raw(value);
     if (old) *old = prev;
     return ZC_OK;
 }

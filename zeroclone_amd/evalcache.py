@@ -291,8 +291,8 @@ class _CachedPolicy(_Cached):
     def _check(self, nets, cache):
         for net in nets:
             if not (net.conv_head or net.fused):
-                raise ValueError(f"{type(self).__name__} needs the fused policy head (32 policy planes on 128 "
-                                 "channels)")
+                raise ValueError(f"{type(self).__name__} needs the fused policy head (32 policy planes on 64 or "
+                                 "128 channels)")
         for net in nets:
             if cache.logit_bytes != 2 * net.logits_width:
                 raise ValueError(f"the network's logits are {2 * net.logits_width} bytes a row, the cache's "

@@ -429,8 +429,8 @@ def train(model, ts: TrainingSet, epochs: int = 10, lr: float = 1e-3, batch_size
 
 
 class FoldedPolicyValueNetwork(torch.nn.Module):
-    """Inference form of a `PolicyValueNetwork` of any width on PyTorch-ROCm (the MFMA tower
-    covers 128 channels): eval-mode BatchNorm folded into the convolutions, channels-last;
+    """Inference form of a `PolicyValueNetwork` of any width on PyTorch-ROCm (the MFMA towers
+    cover 64 and 128 channels): eval-mode BatchNorm folded into the convolutions, channels-last;
     returns (values fp64 [n], logits [n, n_logits]) as a PUCT search's network does."""
 
     def __init__(self, net: nets.PolicyValueNetwork):
@@ -455,8 +455,8 @@ class FoldedPolicyValueNetwork(torch.nn.Module):
 
 def inference_form(model, device, dtype=torch.float16):
     """A trained model as a pool's search evaluates it: `nets.for_inference` of a ValueNetwork;
-    `nets.MfmaPolicyValueNetwork` of a PolicyValueNetwork the MFMA tower covers (128 channels, the
-    fused policy heads), else `FoldedPolicyValueNetwork` in `dtype`."""
+    `nets.MfmaPolicyValueNetwork` of a PolicyValueNetwork the MFMA towers cover (64 or 128 channels,
+    the fused policy heads), else `FoldedPolicyValueNetwork` in `dtype`."""
     dev = torch.device(device)
     if isinstance(model, nets.PolicyValueNetwork):
         conv = model.policy[0]

@@ -101,10 +101,13 @@ class FoldedValueNetwork(nn.Module):
         return torch.tanh(self.fc(x))
 
 
+MFMA_WIDTHS = (64, 128)   # csrc/net_conv64.hip, csrc/net_conv.hip
+
+
 def mfma_supported(net: ValueNetwork) -> bool:
-    """Shapes the hand-written MFMA tower covers: 128 channels, <= 32 input planes."""
+    """Shapes the hand-written MFMA towers cover: 64 or 128 channels, <= 32 input planes."""
     conv = net.stem[0]
-    return conv.out_channels == 128 and conv.in_channels <= 32
+    return conv.out_channels in MFMA_WIDTHS and conv.in_channels <= 32
 
 
 def for_inference(net: ValueNetwork, device, dtype=torch.float16, backend: str = "auto"):
@@ -120,9 +123,11 @@ def for_inference(net: ValueNetwork, device, dtype=torch.float16, backend: str =
 
 
 class MfmaValueNetwork:
-    """The folded ValueNetwork on this package's own MFMA kernels (csrc/net_conv.hip):
-    NHWC fp16 activations, implicit-GEMM conv3x3 on v_mfma_f32_32x32x16_f16 (the packed,
-    streamed-weight form: zc_net_conv3x3_packed_async) with the
+    """The folded ValueNetwork on this package's own MFMA kernels (128 channels: csrc/net_conv.hip;
+    64 channels: csrc/net_conv64.hip; `self.channels` is the width, and every launch goes through
+    the C ABI's _w_ family, which takes it):
+    NHWC fp16 activations, implicit-GEMM conv3x3 on the matrix cores (the packed,
+    streamed-weight form: zc_net_conv3x3_packed_w_async) with the
     bias / residual / ReLU epilogue fused, and the pooled tanh head writing fp64 values.
     Call with state_to_tensor planes [n, in_planes, H, W] fp16 (as the stepwise search
     exports them); returns fp64 values [n].  Buffers are cached per batch size, so a call
@@ -134,25 +139,26 @@ class MfmaValueNetwork:
         self.dev = torch.device(device)
         self.in_planes = f.stem.in_channels
         self.cpad = 32
-        if self.in_planes > self.cpad or f.stem.out_channels != 128:
-            raise ValueError("MFMA path: in_planes <= 32 and 128 channels")
-        convs = [(f.stem, self.cpad)] + [(c, 128) for b in f.res for c in (b.c1, b.c2)]
+        self.channels = C = f.stem.out_channels
+        if self.in_planes > self.cpad or C not in MFMA_WIDTHS:
+            raise ValueError("MFMA path: in_planes <= 32 and 64 or 128 channels")
+        convs = [(f.stem, self.cpad)] + [(c, C) for b in f.res for c in (b.c1, b.c2)]
         self.w, self.b = [], []
         for conv, cin in convs:
-            wt = conv.weight.detach().float()                      # [128][ci][3][3]
-            wp = torch.zeros(128, cin, 3, 3)
+            wt = conv.weight.detach().float()                      # [C][ci][3][3]
+            wp = torch.zeros(C, cin, 3, 3)
             wp[:, : wt.shape[1]] = wt
-            self.w.append(wp.permute(2, 3, 0, 1).reshape(9, 128, cin).contiguous().to(self.dev, torch.float16))
+            self.w.append(wp.permute(2, 3, 0, 1).reshape(9, C, cin).contiguous().to(self.dev, torch.float16))
             self.b.append(conv.bias.detach().float().contiguous().to(self.dev))
-        # the streamed-weight kernel's operand order (zc_net_conv3x3_pack_async), packed once
+        # the streamed-weight kernel's operand order (zc_net_conv3x3_pack_w_async), packed once
         from . import _native
         self.wp = []
         for wt in self.w:
             wp = torch.empty_like(wt)
-            _native.check(_native.lib().zc_net_conv3x3_pack_async(wt.shape[2], wt.data_ptr(), wp.data_ptr(),
-                                                                  ctypes_stream(self.dev)))
+            _native.check(_native.lib().zc_net_conv3x3_pack_w_async(C, wt.shape[2], wt.data_ptr(), wp.data_ptr(),
+                                                                    ctypes_stream(self.dev)))
             self.wp.append(wp)
-        # the same packed weights back to back and the biases [nconv][128], for the fused tower
+        # the same packed weights back to back and the biases [nconv][C], for the fused tower
         self.wall = torch.cat([w.reshape(-1) for w in self.wp]).contiguous()
         self.ball = torch.stack(self.b).contiguous()
         torch.cuda.current_stream(self.dev).synchronize()
@@ -172,17 +178,18 @@ class MfmaValueNetwork:
         key = (n, hw)
         if key not in self._bufs:
             mk = lambda c: torch.empty((n, hw, c), dtype=torch.float16, device=self.dev)  # noqa: E731
-            self._bufs[key] = (mk(self.cpad), mk(128), mk(128), mk(128),
+            C = self.channels
+            self._bufs[key] = (mk(self.cpad), mk(C), mk(C), mk(C),
                                torch.empty(n, dtype=torch.float64, device=self.dev))
         return self._bufs[key]
 
     def tower(self, planes, fused: bool = True, head: bool = False, activation: bool = True, count=None):
-        """Stem + residual blocks: the final activation, NHWC fp16 [n, h*w, 128].  fused: one
-        launch for the whole tower (zc_net_tower_async); otherwise one launch per layer
-        (zc_net_conv3x3_packed_async) — bit-identical.  head (fused only): the value head runs
+        """Stem + residual blocks: the final activation, NHWC fp16 [n, h*w, channels].  fused: one
+        launch for the whole tower (zc_net_tower_w_async); otherwise one launch per layer
+        (zc_net_conv3x3_packed_w_async) — bit-identical.  head (fused only): the value head runs
         in the same launch into the returned fp64 values; activation=False skips writing the
         activation (a value-only network needs none).  count (fused only): an int32 tensor on
-        the device holding the number of rows to evaluate (zc_net_tower_counted_async) — n is
+        the device holding the number of rows to evaluate (zc_net_tower_counted_w_async) — n is
         then the capacity, rows [0, min(count, n)) get the bits of the plain call and the
         outputs' rows past them are left as they were."""
         import torch
@@ -197,13 +204,14 @@ class MfmaValueNetwork:
         s = ctypes_stream(self.dev)
         _native.check(L.zc_net_planes_to_nhwc_async(n, c, hw, self.cpad, planes.data_ptr(), x0.data_ptr(), s))
         if fused:
-            args = (n, h, w, self.cpad, len(self.wp), x0.data_ptr(), self.wall.data_ptr(), self.ball.data_ptr(),
+            args = (self.channels, n, h, w, self.cpad, len(self.wp), x0.data_ptr(), self.wall.data_ptr(),
+                    self.ball.data_ptr(),
                     a.data_ptr() if activation or not head else None, self.fcw.data_ptr() if head else None, self.fcb,
                     vals.data_ptr() if head else None)
             if count is None:
-                _native.check(L.zc_net_tower_async(*args, s))
+                _native.check(L.zc_net_tower_w_async(*args, s))
             else:
-                _native.check(L.zc_net_tower_counted_async(*args, _count_ptr(count, self.dev), s))
+                _native.check(L.zc_net_tower_counted_w_async(*args, _count_ptr(count, self.dev), s))
             return a, vals
         if count is not None:
             raise ValueError("count needs the fused tower")
@@ -211,9 +219,10 @@ class MfmaValueNetwork:
             raise ValueError("head=True needs the fused tower")
 
         def conv(i, src, dst, res):
-            _native.check(L.zc_net_conv3x3_packed_async(n, h, w, src.shape[2], src.data_ptr(), self.wp[i].data_ptr(),
-                                                        self.b[i].data_ptr(), res.data_ptr() if res is not None else None,
-                                                        dst.data_ptr(), 1, s))
+            _native.check(L.zc_net_conv3x3_packed_w_async(self.channels, n, h, w, src.shape[2], src.data_ptr(),
+                                                          self.wp[i].data_ptr(), self.b[i].data_ptr(),
+                                                          res.data_ptr() if res is not None else None,
+                                                          dst.data_ptr(), 1, s))
         conv(0, x0, a, None)
         for k in range((len(self.w) - 1) // 2):
             conv(1 + 2 * k, a, t, None)
@@ -222,10 +231,10 @@ class MfmaValueNetwork:
         return a, vals
 
     def tower_policy(self, planes, pw, pb, pout, relu: bool = True, count=None):
-        """The tower, the value head and a policy 1x1 conv 128 -> P (P = 32 or 64; pw:
-        pack_policy_1x1's fragments, pb fp32 [P]) in ONE launch (zc_net_tower_policy_ex_async):
+        """The tower, the value head and a policy 1x1 conv channels -> P (P = 32 or 64; pw:
+        pack_policy_1x1's fragments, pb fp32 [P]) in ONE launch (zc_net_tower_policy_w_async):
         fp64 values [n]; pout [n, h*w, P] fp16 receives conv1x1 + pb, ReLU'd when `relu`.  No
-        tower activation is written.  count: as tower's (zc_net_tower_policy_counted_async)."""
+        tower activation is written.  count: as tower's (zc_net_tower_policy_counted_w_async)."""
         import torch
         from . import _native
         if planes.dim() == 3:   # already the tower's input layout, [n, h*w, cpad] fp16 (8x8 boards)
@@ -248,18 +257,19 @@ class MfmaValueNetwork:
         else:
             planes = planes.contiguous()
             _native.check(L.zc_net_planes_to_nhwc_async(n, c, h * w, self.cpad, planes.data_ptr(), x0.data_ptr(), s))
-        args = (n, h, w, self.cpad, len(self.wp), x0.data_ptr(), self.wall.data_ptr(), self.ball.data_ptr(),
-                self.fcw.data_ptr(), self.fcb, vals.data_ptr(), pw.data_ptr(), pb.data_ptr(), P, 1 if relu else 0,
+        args = (self.channels, n, h, w, self.cpad, len(self.wp), x0.data_ptr(), self.wall.data_ptr(),
+                self.ball.data_ptr(), self.fcw.data_ptr(), self.fcb, vals.data_ptr(), pw.data_ptr(), pb.data_ptr(), P,
+                1 if relu else 0,
                 pout.data_ptr())
         if count is None:
-            _native.check(L.zc_net_tower_policy_ex_async(*args, s))
+            _native.check(L.zc_net_tower_policy_w_async(*args, s))
         else:
-            _native.check(L.zc_net_tower_policy_counted_async(*args, _count_ptr(count, self.dev), s))
+            _native.check(L.zc_net_tower_policy_counted_w_async(*args, _count_ptr(count, self.dev), s))
         return vals
 
     def __call__(self, planes, fused: bool = True, count=None):
         """fp64 values [n]: the tower and the value head in one launch (fused), or the layered
-        tower + zc_net_value_head_async — bit-identical.  count: as tower's."""
+        tower + zc_net_value_head_w_async — bit-identical.  count: as tower's."""
         from . import _native
         if fused:
             return self.tower(planes, head=True, activation=False, count=count)[1]
@@ -267,8 +277,8 @@ class MfmaValueNetwork:
             raise ValueError("count needs the fused tower")
         a, vals = self.tower(planes, fused=False)
         n, hw = a.shape[0], a.shape[1]
-        _native.check(_native.lib().zc_net_value_head_async(n, hw, a.data_ptr(), self.fcw.data_ptr(), self.fcb,
-                                                            vals.data_ptr(), ctypes_stream(self.dev)))
+        _native.check(_native.lib().zc_net_value_head_w_async(self.channels, n, hw, a.data_ptr(), self.fcw.data_ptr(),
+                                                              self.fcb, vals.data_ptr(), ctypes_stream(self.dev)))
         return vals
 
 
@@ -292,10 +302,17 @@ def pack_policy_1x1(weight):
     """A [P, 128] (out, in) 1x1 conv weight, P = 32 or 64, as the tower kernel's
     v_mfma_f32_32x32x16_f16 A fragments, fp16 [P / 32 blocks][8 k-steps][64 lanes][8]: lane l of
     k-step kc of block mb holds weight[32 mb + l % 32, 16 kc + 8 (l // 32) + e]
-    (csrc/net_conv.hip TowerPolicy)."""
+    (csrc/net_conv.hip TowerPolicy).
+
+    A [P, 64] weight (the 64-channel tower's), P = 32 or 64, as v_mfma_f32_16x16x32_f16 A
+    fragments, fp16 [P / 16 M tiles][2 k-steps][64 lanes][8]: lane l of k-step j of M tile mt holds
+    weight[16 mt + l % 16, 32 j + 8 (l // 16) + e] (csrc/net_conv64.hip TowerPolicy64)."""
     co, ci = weight.shape
-    if co not in (32, 64) or ci != 128:
-        raise ValueError("the fused policy conv is 128 -> 32 or 64 channels")
+    if co not in (32, 64) or ci not in MFMA_WIDTHS:
+        raise ValueError("the fused policy conv is 64 or 128 -> 32 or 64 channels")
+    if ci == 64:
+        mt = co // 16
+        return weight.reshape(mt, 16, 2, 4, 8).permute(0, 2, 3, 1, 4).reshape(mt, 2, 64, 8).contiguous()
     mb = co // 32
     return weight.reshape(mb, 32, 8, 2, 8).permute(0, 2, 3, 1, 4).reshape(mb, 8, 64, 8).contiguous()
 
@@ -349,14 +366,14 @@ class PolicyValueNetwork(nn.Module):
 class MfmaPolicyValueNetwork:
     """PolicyValueNetwork for inference, ONE kernel launch up to the policy logits' GEMM: the
     tower, the value head and the policy head's 1x1 conv (BN folded, ReLU) run in the fused
-    tower kernel (zc_net_tower_policy_async; the conv as an MFMA epilogue on the on-chip
-    activation, so the 128-channel activation never reaches HBM); the flatten + Linear to
+    tower kernel (zc_net_tower_policy_w_async, at 64 or 128 channels; the conv as an MFMA epilogue
+    on the on-chip activation, so the tower's activation never reaches HBM); the flatten + Linear to
     the 4096 logits is one fp16 GEMM on PyTorch-ROCm over its [n, h*w*32] output.  Returns
     (fp64 values [n], fp16 logits [n, 4096]).  fused=False: the tower's activation written
     out and the 1x1 conv as a GEMM (the pre-round-4 path, kept for the A/B).
 
     With the convolutional head (PolicyValueNetwork(head="conv"), round 5) the whole network
-    is ONE launch: the 1x1 conv 128 -> 64 epilogue (BN folded, no ReLU) writes [n, 64 from,
+    is ONE launch: the 1x1 conv 64 or 128 -> 64 epilogue (BN folded, no ReLU) writes [n, 64 from,
     64 to] fp16 = the logits in from*64 + to order, and there is no GEMM."""
 
     def __init__(self, net: PolicyValueNetwork, device="cuda"):
@@ -366,8 +383,8 @@ class MfmaPolicyValueNetwork:
         if self.conv_head:
             folded = _fold(net.policy[0], net.policy[1])
             wf = folded.weight.detach().float().reshape(folded.out_channels, -1)   # [h*w, C]
-            if wf.shape != (64, 128):
-                raise ValueError("the fused convolutional head is 128 -> 64 channels (an 8x8 board)")
+            if wf.shape != (64, self.tower.channels):
+                raise ValueError("the fused convolutional head is 64 or 128 -> 64 channels (an 8x8 board)")
             self.fused = True
             self.pw = pack_policy_1x1(wf).to(device, torch.float16)
             self.pb = folded.bias.detach().float().contiguous().to(device)
@@ -379,7 +396,7 @@ class MfmaPolicyValueNetwork:
         wf = folded.weight.detach().float().reshape(P, -1)                      # [P, C]
         self.w1 = wf.t().contiguous().to(device, torch.float16)  # [C, P]
         self.b1 = folded.bias.detach().float().to(device, torch.float16)
-        self.fused = P == 32 and wf.shape[1] == 128
+        self.fused = P == 32 and wf.shape[1] == self.tower.channels
         if self.fused:
             self.pw = pack_policy_1x1(wf).to(device, torch.float16)
             self.pb = folded.bias.detach().float().contiguous().to(device)

@@ -429,8 +429,8 @@ def _check_mfma(value_nets, puct_nets, what="eval_cache / eval_merge need", whos
     from . import nets
     for group, kind in ((value_nets, nets.MfmaValueNetwork), (puct_nets, nets.MfmaPolicyValueNetwork)):
         if not all(n is None or isinstance(n, kind) for n in group):
-            raise ValueError(f"{what} the MFMA form of {whose} (its tower takes the row count from the device): a "
-                             f"torch module cannot be {verb}")
+            raise ValueError(f"{what} the MFMA form of {whose} (64 or 128 channels; its tower takes the row count "
+                             f"from the device): a torch module cannot be {verb}")
 
 
 _NO_FUSED_BOOK = ("the fused launches refill from the one opening inside the kernel: a pool with a book of openings "
