@@ -55,7 +55,8 @@ def _integers(net, g, nl):
     multiples of 2^-6, so that its sum is exact in any order and tanh does not saturate."""
     for m in net.modules():
         if isinstance(m, torch.nn.Conv2d):
-            dens = 0.002 if m.in_channels == 128 and m.kernel_size == (3, 3) else 0.02
+            # the tower's convs: 0.002 at 128 -> 128, 0.004 at 64 -> 64 (the width tests' density)
+            dens = {128: 0.002, 64: 0.004}.get(m.in_channels, 0.02) if m.kernel_size == (3, 3) else 0.02
             keep = torch.rand(m.weight.shape, generator=g) < dens
             m.weight.data = torch.randint(-2, 3, m.weight.shape, generator=g).float() * keep
         elif isinstance(m, torch.nn.BatchNorm2d):
@@ -74,17 +75,22 @@ def _integers(net, g, nl):
     return net
 
 
-def integer_net(in_planes: int, seed: int):
-    """MfmaValueNetwork over an integer ValueNetwork(128 channels, 2 blocks): the MFMA tower."""
+def integer_net(in_planes: int, seed: int, channels: int = 128):
+    """MfmaValueNetwork over an integer ValueNetwork(64 or 128 channels, 2 blocks): the MFMA tower."""
     from zeroclone_amd.nets import MfmaValueNetwork, ValueNetwork
     g = torch.Generator().manual_seed(seed)
-    return MfmaValueNetwork(_integers(ValueNetwork(128, 2, in_planes=in_planes).eval(), g, 0))
+    net = MfmaValueNetwork(_integers(ValueNetwork(channels, 2, in_planes=in_planes).eval(), g, 0))
+    assert net.channels == channels
+    return net
 
 
-def integer_pv_net(in_planes: int, h: int, w: int, n_logits: int, seed: int, head: str = "linear"):
-    """MfmaPolicyValueNetwork over an integer PolicyValueNetwork (128 channels, 2 blocks)."""
+def integer_pv_net(in_planes: int, h: int, w: int, n_logits: int, seed: int, head: str = "linear",
+                   channels: int = 128):
+    """MfmaPolicyValueNetwork over an integer PolicyValueNetwork (64 or 128 channels, 2 blocks)."""
     from zeroclone_amd.nets import MfmaPolicyValueNetwork, PolicyValueNetwork
     g = torch.Generator().manual_seed(seed)
-    net = PolicyValueNetwork(in_planes=in_planes, board=(h, w), n_logits=n_logits, head=head).eval()
+    net = PolicyValueNetwork(channels, in_planes=in_planes, board=(h, w), n_logits=n_logits, head=head).eval()
     net.res = net.res[:2]
-    return MfmaPolicyValueNetwork(_integers(net, g, n_logits))
+    net = MfmaPolicyValueNetwork(_integers(net, g, n_logits))
+    assert net.tower.channels == channels and net.fused
+    return net

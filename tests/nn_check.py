@@ -163,15 +163,87 @@ def ambiguous_share(lo16, hi16) -> float:
 
 
 def value_head_reference(act, fcw, fcb):
-    """The value head's pre-tanh sum for act fp16 [n, hw, 128], fcw fp32 [128], fcb (an fp32
-    value): (d64, slack), with k = hw + 128 + 2 fp32 operations on any element's path (the
+    """The value head's pre-tanh sum for act fp16 [n, hw, C], fcw fp32 [C], fcb (an fp32
+    value): (d64, slack), with k = hw + C + 2 fp32 operations on any element's path (the
     pixel sum, the product, the channel sum, the division by hw, + fcb)."""
     assert act.dtype == torch.float16 and fcw.dtype == torch.float32
     hw = act.shape[1]
     fb = float(np.float32(fcb))
     d = (act.double().sum(dim=1) @ fcw.double()) / hw + fb
     A = (act.double().abs().sum(dim=1) @ fcw.double().abs()) / hw + abs(fb)
-    return d, gamma(hw + 128 + 2) * A
+    return d, gamma(hw + act.shape[2] + 2) * A
+
+
+# ---- synthetic activations for the stand-alone value head, and the wrong heads they must catch ----
+
+HEAD_FCBS = (0.3, 12.5, -12.5)
+
+
+def cancelling_head_inputs(g, n, hw, channels=128):
+    """(act fp16 [n, hw, C], fcw fp32 [C]) from the generator g: C / 2 channel pairs that hold the
+    same activation (per-pair scales 1 .. 6e4, the first two 6e4 and 3e4; 30 % zeros) under
+    opposite Linear weights (the second off by a relative 2^-9 randn), so the C-term sum cancels
+    to O(1) and an fp16 or a badly ordered accumulation shows."""
+    pairs = channels // 2
+    scale = 6.0e4 ** torch.rand(pairs, generator=g, dtype=torch.float64)
+    scale[:2] = torch.tensor([6.0e4, 3.0e4], dtype=torch.float64)
+    half = torch.rand(n, hw, pairs, generator=g, dtype=torch.float64) * scale * (torch.rand(n, hw, pairs, generator=g) >= 0.3)
+    act = torch.stack([half, half], dim=3).reshape(n, hw, channels).half()
+    wpair = torch.randn(pairs, generator=g) * 1e-3
+    fcw = torch.stack([wpair, -wpair * (1 + 2.0 ** -9 * torch.randn(pairs, generator=g))], dim=1).reshape(channels).float()
+    return act, fcw
+
+
+def spread_head_inputs(seed, n, hw, channels=128):
+    """The second, non-cancelling set: every channel its own activation (the pair's scale, 30 %
+    zeros) and its own weight, 0.5 randn / sqrt(C) over the channel's expected pixel mean (0.35
+    scale), so every channel adds O(1 / sqrt(C)) to a sum of std ~0.5.  What the cancelling set
+    cannot see shows here: a term lost from both channels of a pair alike, or the two weights of a
+    pair exchanged (its two channels hold the same activation there)."""
+    g = torch.Generator().manual_seed(seed)
+    scale = (6.0e4 ** torch.rand(channels // 2, generator=g, dtype=torch.float64)).repeat_interleave(2)
+    scale[:4] = torch.tensor([6.0e4, 6.0e4, 3.0e4, 3.0e4], dtype=torch.float64)
+    act = torch.rand(n, hw, channels, generator=g, dtype=torch.float64) * scale * (torch.rand(n, hw, channels, generator=g) >= 0.3)
+    fcw = (0.5 / channels ** 0.5) * torch.randn(channels, generator=g, dtype=torch.float64) / (0.35 * scale)
+    return act.half(), fcw.float()
+
+
+HEAD_MUTANTS = ("fp16_pixel_sums", "fp16_weights", "divide_by_64", "pair_weights_swapped", "one_lane_left_out")
+
+
+def wrong_head(act, fcw, fcb, mutant):
+    """The pre-tanh sum of a subtly wrong value head, in float64 from the head's inputs alone:
+    "fp16_pixel_sums" (each channel's pixel sum accumulated in fp16), "fp16_weights" (fcw rounded
+    to fp16), "divide_by_64" (the mean over 64 pixels whatever hw is: wrong on 6x7 only),
+    "pair_weights_swapped" (channels 2 i and 2 i + 1 take each other's weight), "one_lane_left_out"
+    (channels 8 .. 15 lose one lane's pixels: p = 7 mod 8 of the 64-channel head, where lane l
+    sums channels 8 (l & 7) .. + 7 over pixels l / 8, + 8, ...; p = 3 mod 4 of the 128-channel
+    head, where lane l sums channels 8 (l & 15) .. + 7 over pixels l / 16, + 4, ...)."""
+    assert mutant in HEAD_MUTANTS
+    n, hw, C = act.shape
+    a, w, div = act.double(), fcw.double(), float(hw)
+    fb = float(np.float32(fcb))
+    if mutant == "fp16_pixel_sums":
+        s = torch.zeros(n, C, dtype=torch.float16)
+        for p in range(hw):
+            s = s + act[:, p]
+        return (s.double() @ w) / div + fb
+    if mutant == "fp16_weights":
+        w = fcw.half().double()
+    elif mutant == "divide_by_64":
+        div = 64.0
+    elif mutant == "pair_weights_swapped":
+        w = w.reshape(-1, 2).flip(1).reshape(-1)
+    elif mutant == "one_lane_left_out":
+        a = a.clone()
+        step, first = (8, 7) if C == 64 else (4, 3)
+        a[:, first::step, 8:16] = 0.0
+    return (a.sum(dim=1) @ w) / div + fb
+
+
+def head_rejects(d_wrong, d, slack):
+    """Boards on which a wrong head's sum is NaN or outside the slack of the reference."""
+    return torch.isnan(d_wrong) | ~((d_wrong - d).abs() <= slack)
 
 
 def wide_range_layer(h, w, cin, seed, n=13, cout=128, overflow=False):

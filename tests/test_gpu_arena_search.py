@@ -1,7 +1,9 @@
 """A routed search equals the two single-network searches: each game's move, root visit counts,
 stats and final RNG state are those of the search whose network its key names, bit for bit, in
 each of the four stepwise searches (12 Connect4 games, 6 chess games, batch 8, 20 simulations:
-flushes of 8, 8 and 4 leaves, and the PUCT searches' roots flush of one row a game)."""
+flushes of 8, 8 and 4 leaves, and the PUCT searches' roots flush of one row a game).  The networks
+are callables exact on the planes, integer MFMA networks of 128 channels, of 64, and one of 64
+against one of 128."""
 import random
 
 import numpy as np
@@ -50,17 +52,24 @@ def chess_roots():
     return torch.from_numpy(a.view(np.uint8).reshape(len(CHESS_FENS), 72).copy()).cuda()
 
 
+# the channels of networks A and B: two 64-channel towers, and a 64-channel one against a
+# 128-channel one (the routed callables need the same head and logits width, not the same tower)
+WIDTHS = {"integer_net": (128, 128), "integer_net_64": (64, 64), "integer_net_mixed": (64, 128)}
+
+
 def value_fns(kind, planes):
     if kind == "exact":
         return Exact(11), Exact(23)
-    return valued.NetValue(integer_net(planes, 5)), valued.NetValue(integer_net(planes, 6))
+    ca, cb = WIDTHS[kind]
+    return valued.NetValue(integer_net(planes, 5, ca)), valued.NetValue(integer_net(planes, 6, cb))
 
 
 def policy_fns(kind, planes, h, w, nl, head="linear"):
     if kind == "exact":
         return Exact(11, nl), Exact(23, nl)
-    return (valued.PolicyNet(integer_pv_net(planes, h, w, nl, 5, head)),
-            valued.PolicyNet(integer_pv_net(planes, h, w, nl, 6, head)))
+    ca, cb = WIDTHS[kind]
+    return (valued.PolicyNet(integer_pv_net(planes, h, w, nl, 5, head, ca)),
+            valued.PolicyNet(integer_pv_net(planes, h, w, nl, 6, head, cb)))
 
 
 # search: (class, roots, keys, constructor arguments, the two callables of a kind)
@@ -75,7 +84,7 @@ SEARCHES = {
 }
 
 
-@pytest.mark.parametrize("kind", ["exact", "integer_net"])
+@pytest.mark.parametrize("kind", ["exact", "integer_net", "integer_net_64", "integer_net_mixed"])
 @pytest.mark.parametrize("name", list(SEARCHES))
 def test_routed_search_equals_the_single_network_searches(name, kind):
     cls, roots_fn, key, kw, fns = SEARCHES[name]

@@ -269,9 +269,9 @@ def test_counted_tower_evaluates_the_rows_below_the_count_alone(shape):
     for ref in (a_ref, p_ref):   # the same row at position 0 and at position 36: the same bits
         assert torch.equal(ref[0].view(torch.int16), ref[36].view(torch.int16))
     assert v_ref[0].item() == v_ref[36].item() and pv_ref[0].item() == pv_ref[36].item()
-    for k in (0, 1, 5, 37, 50):
+    for k in (0, 1, 5, 37, 50, -1, -2 ** 31):   # a negative count is 0 (include/zeroclone.h)
         cnt = torch.tensor([k], dtype=torch.int32, device="cuda")
-        kk = min(k, n)
+        kk = max(min(k, n), 0)
         _, a_buf, _, _, v_buf = vnet._buffers(n, hw)
         a_buf.fill_(-1.0)
         v_buf.fill_(-5.0)

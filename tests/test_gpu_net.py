@@ -188,12 +188,26 @@ def test_tower_forms_exact_on_integers(mf, shape, net_sw):
     """Both MFMA forms of the fused tower ("tower_mf": 32x32x16, 16x16x32; "16e": the
     16x16x32 form with the swap epilogue, "tower_epi" 1) on an integer network, 2 residual
     blocks, ragged board counts: equal to float64 exactly."""
+    _tower_forms_exact(mf, shape, net_sw, blocks=2)
+
+
+@pytest.mark.parametrize("mf", ["32", "16", "16e"])
+@pytest.mark.parametrize("shape", [(17, 8, 8), (2, 6, 7)])
+def test_tower_forms_exact_on_integers_without_blocks(mf, shape, net_sw):
+    """The same on a network without residual blocks: the stem alone (nconv = 1), the one layer
+    of a launch that has no next layer's weights to fetch."""
+    _tower_forms_exact(mf, shape, net_sw, blocks=0)
+
+
+def _tower_forms_exact(mf, shape, net_sw, blocks):
     from zeroclone_amd.nets import FoldedValueNetwork, MfmaValueNetwork
     net_sw("tower_mf", int(mf[:2]))
     net_sw("tower_epi", 1 if mf.endswith("e") else 0)
     c, h, w = shape
-    vnet = _integer_net(c, 2, seed=h * 10 + int(mf[:2]))
+    vnet = _integer_net(c, blocks, seed=h * 10 + int(mf[:2]))
     net = MfmaValueNetwork(vnet)
+    assert len(net.w) == len(net.wp) == 1 + 2 * blocks and net.ball.shape == (1 + 2 * blocks, 128)
+    assert net.wall.numel() == 9 * 128 * 32 + 2 * blocks * 9 * 128 * 128   # 0 blocks: the stem's weights alone
     f = FoldedValueNetwork(vnet).double()
     for n in (1, 5, 131):
         x = (torch.rand(n, c, h, w) < 0.3).half()
@@ -255,10 +269,22 @@ def test_value_head_exact_on_integers(mf, shape, net_sw):
     42/64, so the kernel's correctly rounded division by 42 is exact).  With the
     tanh (the product path) the values equal float64 tanh of that sum within tanhf's precision.
     A head without its bias or without its Linear would fail every one of these."""
+    _value_head_exact(mf, shape, net_sw, blocks=2)
+
+
+@pytest.mark.parametrize("mf", ["32", "16"])
+@pytest.mark.parametrize("shape", [(17, 8, 8), (2, 6, 7)])
+def test_value_head_exact_on_integers_without_blocks(mf, shape, net_sw):
+    """The same on a network without residual blocks (nconv = 1): the head reads the stem's
+    output, in the fused launch from the buffer the first layer wrote."""
+    _value_head_exact(mf, shape, net_sw, blocks=0)
+
+
+def _value_head_exact(mf, shape, net_sw, blocks):
     from zeroclone_amd.nets import FoldedValueNetwork, MfmaValueNetwork
     net_sw("tower_mf", int(mf))
     c, h, w = shape
-    vnet = _integer_head(_integer_net(c, 2, seed=h * 7 + int(mf)), h * w, seed=int(mf) + h)
+    vnet = _integer_head(_integer_net(c, blocks, seed=h * 7 + int(mf)), h * w, seed=int(mf) + h)
     xs = [(torch.rand(n, c, h, w) < 0.3).half() for n in (1, 5, 131)]
 
     def pre_tanh(x):

@@ -242,30 +242,29 @@ def test_value_head_on_synthetic_activations(hw, net_sw):
     """zc_net_value_head_async on activations up to 6e4 whose channels come in pairs with
     opposite Linear weights: the 128-term sum cancels to O(1), so an fp16 or a badly ordered
     accumulation shows.  Pre-tanh within the slack of float64; tanh within slack + 1e-6, never
-    past +-1 and exactly +-1 past |d| = 10."""
+    past +-1 and exactly +-1 past |d| = 10.  The same on nn_check.spread_head_inputs, every
+    channel with an activation and a weight of its own, which shows what cancels in a pair
+    (tests/test_net_interval_cpu.py:test_wrong_value_heads_fall_outside_the_slack)."""
     from zeroclone_amd import _native
     L = _native.lib()
     g = torch.Generator().manual_seed(hw)
     for n in (1, 5):
-        scale = 6.0e4 ** torch.rand(64, generator=g, dtype=torch.float64)             # 1 .. 6e4 per channel pair
-        scale[:2] = torch.tensor([6.0e4, 3.0e4], dtype=torch.float64)
-        half = torch.rand(n, hw, 64, generator=g, dtype=torch.float64) * scale * (torch.rand(n, hw, 64, generator=g) >= 0.3)
-        act = torch.stack([half, half], dim=3).reshape(n, hw, 128).half()
-        assert act.max().item() > 5.0e4 and torch.isfinite(act).all()
-        wpair = torch.randn(64, generator=g) * 1e-3
-        fcw = torch.stack([wpair, -wpair * (1 + 2.0 ** -9 * torch.randn(64, generator=g))], dim=1).reshape(128).float()
-        ag, wg = act.cuda(), fcw.cuda()
-        for fcb in (0.3, 12.5, -12.5):
-            d, slack = nc.value_head_reference(act, fcw, fcb)
-            assert slack.max().item() < 0.5 and (d - float(np.float32(fcb))).abs().max().item() < 2.0   # it cancels
-            for raw in (1, 0):
-                net_sw("head_raw", raw)
-                vals = torch.full((n,), 7.0, dtype=torch.float64, device="cuda")
-                _native.check(L.zc_net_value_head_async(n, hw, ag.data_ptr(), wg.data_ptr(), fcb, vals.data_ptr(), None))
-                torch.cuda.synchronize()
-                check_values(vals, act, fcw, fcb, raw, (hw, n, fcb, raw))
-            if abs(fcb) > 10:
-                assert (d.abs() > 10).all()
+        sets = {"cancelling": nc.cancelling_head_inputs(g, n, hw, 128),
+                "spread": nc.spread_head_inputs(1000 * 128 + 10 * hw + n, n, hw, 128)}
+        for name, (act, fcw) in sets.items():
+            assert act.max().item() > 5.0e4 and torch.isfinite(act).all()
+            ag, wg = act.cuda(), fcw.cuda()
+            for fcb in nc.HEAD_FCBS:
+                d, slack = nc.value_head_reference(act, fcw, fcb)
+                assert slack.max().item() < 0.5 and (d - float(np.float32(fcb))).abs().max().item() < 2.0   # it cancels
+                for raw in (1, 0):
+                    net_sw("head_raw", raw)
+                    vals = torch.full((n,), 7.0, dtype=torch.float64, device="cuda")
+                    _native.check(L.zc_net_value_head_async(n, hw, ag.data_ptr(), wg.data_ptr(), fcb, vals.data_ptr(), None))
+                    torch.cuda.synchronize()
+                    check_values(vals, act, fcw, fcb, raw, (hw, n, name, fcb, raw))
+                if abs(fcb) > 10:
+                    assert (d.abs() > 10).all()
 
 
 @pytest.mark.parametrize("board", BOARDS, ids=["8x8", "6x7"])
@@ -490,6 +489,39 @@ def test_counted_launches_with_non_finite_rows(board):
     torch.cuda.synchronize()
     assert same_bits(pout[:7], want_p[:7]) and same_bits(v3[:7], want_pv[:7])
     assert (pout[7:] == -3.0).all() and (v3[7:] == -3.0).all()
+
+
+@pytest.mark.parametrize("count", [0, -1, -2 ** 31])
+@pytest.mark.parametrize("board", BOARDS, ids=["8x8", "6x7"])
+def test_counted_launches_with_no_rows_to_evaluate(board, count, net_sw):
+    """zc_net_tower_counted_async and zc_net_tower_policy_counted_async, capacity 11, in every
+    fused form: "a negative count is 0" (include/zeroclone.h), so with -1 and -2^31 as with 0
+    every row of a sentinel-filled activation, values and pout keeps its sentinel."""
+    from zeroclone_amd.nets import MfmaPolicyValueNetwork
+    c, h, w = board
+    mnet = MfmaPolicyValueNetwork(wide_policy_net(c, h, w, "linear"))
+    tower = mnet.tower
+    xg = planes(NB, c, h, w, seed=21).cuda()
+    cnt = torch.tensor([count], dtype=torch.int32, device="cuda")
+    assert int(cnt.item()) == count
+    pout = torch.empty((NB, h * w, 32), dtype=torch.float16, device="cuda")
+    for mf, epi in FUSED_FORMS:
+        net_sw("tower_mf", mf)
+        net_sw("tower_epi", epi)
+        a, vals = tower.tower(xg, head=True)
+        tower.tower_policy(xg, mnet.pw, mnet.pb, pout)
+        assert a.abs().sum().item() > 0 and pout.abs().sum().item() > 0 and (vals != -3.0).all()   # the plain launches write
+        a.fill_(-3.0)
+        vals.fill_(-3.0)
+        a2, v2 = tower.tower(xg, head=True, count=cnt)
+        torch.cuda.synchronize()
+        assert a2.data_ptr() == a.data_ptr() and v2.data_ptr() == vals.data_ptr()
+        assert (a2 == -3.0).all() and (v2 == -3.0).all(), (board, count, mf, epi)
+        pout.fill_(-3.0)
+        v3 = tower.tower_policy(xg, mnet.pw, mnet.pb, pout, count=cnt)
+        torch.cuda.synchronize()
+        assert (pout == -3.0).all() and (v3 == -3.0).all(), (board, count, mf, epi)
+    net_sw("tower_epi", 0)
 
 
 @pytest.mark.parametrize("what", ["bias", "weight"])

@@ -5,6 +5,7 @@ values and the refusals.  The references are tests/nn_check.py's (float64 on the
 inputs); nothing here is measured on the code under test."""
 import functools
 
+import numpy as np
 import pytest
 import torch
 
@@ -146,18 +147,21 @@ def integer_net(c, blocks, seed):
     return net
 
 
-@pytest.mark.parametrize("blocks", [1, 2, 3])
+@pytest.mark.parametrize("blocks", [0, 1, 2, 3])
 @pytest.mark.parametrize("board", BOARDS, ids=BOARD_IDS)
 def test_tower_exact_on_integers(board, blocks):
     """The fused tower on an integer network equals float64 bit for bit: the MFMA operand and
     accumulator layouts, tap shifts, board edges, the in-place residual and ragged tiles (a tile
     is 2 chess or 3 Connect4 boards; 1 and 3 blocks end in the same buffer, through another
-    number of swaps)."""
+    number of swaps).  0 blocks: the stem alone (nconv = 1), a layer with no next layer's weights
+    to fetch."""
     from zeroclone_amd.nets import FoldedValueNetwork, MfmaValueNetwork
     c, h, w = board
     vnet = integer_net(c, blocks, seed=h * 10 + blocks)
     net = MfmaValueNetwork(vnet)
     assert net.channels == C
+    assert len(net.w) == len(net.wp) == 1 + 2 * blocks and net.ball.shape == (1 + 2 * blocks, C)
+    assert net.wall.numel() == 9 * C * 32 + 2 * blocks * 9 * C * C   # 0 blocks: the stem's weights alone
     f = FoldedValueNetwork(vnet).double()
     for n in (1, 5, 12, 13, 131):
         x = planes(n, c, h, w, seed=100 + n)
@@ -247,6 +251,40 @@ def check_values(got, act, fcw, fcb, raw, what):
         return
     assert ((got - torch.tanh(d)).abs() <= slack + 1e-6).all(), (what, (got - torch.tanh(d)).abs().max().item())
     assert (got.abs() <= 1.0).all(), what
+    big = d.abs() > 10
+    assert torch.equal(got[big], torch.sign(d[big])), what
+
+
+@pytest.mark.parametrize("hw", [64, 42])
+def test_value_head_on_synthetic_activations(hw, net_sw):
+    """zc_net_value_head_w_async at 64 channels on activations up to 6e4 whose channels come in 32
+    pairs with opposite Linear weights (tests/test_gpu_net_range.py's generator at this width):
+    the 64-term sum cancels to O(1), so an fp16 or a badly ordered accumulation shows.  Pre-tanh
+    within the slack of float64 (k = hw + 64 + 2); tanh within slack + 1e-6, never past +-1 and
+    exactly +-1 past |d| = 10.  The same on nn_check.spread_head_inputs, which shows what cancels
+    in a pair: tests/test_net_interval_cpu.py:test_wrong_value_heads_fall_outside_the_slack has
+    the wrong heads each set rejects."""
+    from zeroclone_amd import _native
+    L = _native.lib()
+    g = torch.Generator().manual_seed(hw)
+    for n in (1, 5):
+        sets = {"cancelling": nc.cancelling_head_inputs(g, n, hw, C),
+                "spread": nc.spread_head_inputs(1000 * C + 10 * hw + n, n, hw, C)}
+        for name, (act, fcw) in sets.items():
+            assert act.shape == (n, hw, C) and act.max().item() > 5.0e4 and torch.isfinite(act).all()
+            ag, wg = act.cuda(), fcw.cuda()
+            for fcb in nc.HEAD_FCBS:
+                d, slack = nc.value_head_reference(act, fcw, fcb)
+                assert slack.max().item() < 0.5 and (d - float(np.float32(fcb))).abs().max().item() < 2.0
+                for raw in (1, 0):
+                    net_sw("head_raw", raw)
+                    vals = torch.full((n,), 7.0, dtype=torch.float64, device="cuda")
+                    _native.check(L.zc_net_value_head_w_async(C, n, hw, ag.data_ptr(), wg.data_ptr(), fcb, vals.data_ptr(),
+                                                              None))
+                    torch.cuda.synchronize()
+                    check_values(vals, act, fcw, fcb, raw, (hw, n, name, fcb, raw))
+                if abs(fcb) > 10:
+                    assert (d.abs() > 10).all()
 
 
 @pytest.mark.parametrize("board", BOARDS, ids=BOARD_IDS)
@@ -434,16 +472,17 @@ def test_policy_value_network_tracks_float64(head):
 
 # ---- 5. the counted forms ---------------------------------------------------------------------
 
-@pytest.mark.parametrize("count", [0, 1, 7, 11, 40])
+@pytest.mark.parametrize("count", [0, 1, 7, 11, 40, -1, -2 ** 31])
 @pytest.mark.parametrize("board", BOARDS, ids=BOARD_IDS)
 def test_counted_forms(board, count):
     """zc_net_tower_counted_w_async and zc_net_tower_policy_counted_w_async at 64 channels, capacity
     11: the rows below min(count, 11) have the bits of the plain call; the rows past it of a
-    sentinel-filled activation, values and pout are untouched."""
+    sentinel-filled activation, values and pout are untouched.  A negative count is 0
+    (include/zeroclone.h): every row keeps its sentinel."""
     from zeroclone_amd.nets import MfmaPolicyValueNetwork
     c, h, w = board
     n = 11
-    k = min(count, n)
+    k = max(min(count, n), 0)
     mnet = MfmaPolicyValueNetwork(wide_policy_net(c, h, w, "linear"))
     tower = mnet.tower
     xg = planes(n, c, h, w, seed=21).cuda()
@@ -516,6 +555,133 @@ def test_non_finite_inputs_reach_every_output(board):
     a, vals = mnet.tower(x.cuda(), head=True)
     assert same_bits(clean_rows(a.cpu().reshape(want.shape)), clean_rows(want))
     assert same_bits(clean_rows(vals.cpu()), clean_rows(got_v))
+
+
+@pytest.mark.parametrize("case", [(17, 8, 8, "linear"), (2, 6, 7, "linear"), (17, 8, 8, "conv")], ids=POLICY_IDS)
+def test_non_finite_inputs_reach_pout_and_logits(case):
+    """The same three boards through zc_net_tower_policy_w_async at 64 channels (the conv head from
+    NHWC [n, 64, 32] planes, tower_policy's three-dimensional input): pout is what float64 makes
+    of the activation of tower(head=True), NaN on every pixel the activation holds a NaN; the
+    poisoned boards' values and logits are NaN; the clean boards hold the bits of the clean
+    launch."""
+    from zeroclone_amd.nets import MfmaPolicyValueNetwork
+    c, h, w, head = case
+    net = wide_policy_net(c, h, w, head)
+    mnet = MfmaPolicyValueNetwork(net)
+    assert mnet.fused and mnet.tower.channels == C
+    x, bad = poisoned(c, h, w)
+    as_input = (lambda t: nhwc32(t).reshape(NB, h * w, 32).cuda()) if head == "conv" else (lambda t: t.cuda())
+    assert as_input(bad).dim() == (3 if head == "conv" else 4)
+    v, logits = mnet(as_input(bad))
+    v, logits, pout = v.cpu().clone(), logits.cpu().clone(), mnet._pout[(NB, h * w)].cpu().clone()
+    a, _ = mnet.tower.tower(bad.cuda(), head=True)
+    act = a.cpu().clone()
+    pw, pb = policy_operands(net)
+    assert pw.shape == (32 if head == "linear" else 64, C)
+    lo, hi, s = nc.pointwise_interval(act, pw, pb, relu=head == "linear")
+    assert int(nc.outside(pout, lo, hi, s).sum()) == 0
+    for b in POISON:
+        assert torch.isnan(act[b]).any() and torch.isnan(pout[b]).any() and torch.isnan(v[b]), (case, b)
+        assert torch.isnan(logits[b]).any(), (case, b)
+    v0, logits0 = mnet(as_input(x))
+    assert not torch.isnan(v0).any() and not torch.isnan(logits0).any()
+    assert same_bits(clean_rows(v0.cpu()), clean_rows(v))
+    assert same_bits(clean_rows(mnet._pout[(NB, h * w)].cpu()), clean_rows(pout))
+    assert same_bits(clean_rows(logits0.cpu()), clean_rows(logits))
+
+
+@pytest.mark.parametrize("board", BOARDS, ids=BOARD_IDS)
+def test_counted_launches_with_non_finite_rows(board):
+    """zc_net_tower_counted_w_async and zc_net_tower_policy_counted_w_async at 64 channels, count =
+    7 of 11: the poisoned boards below the count give the plain launch's outputs (NaN kept), and
+    the rows past it — board 7, all NaN, shares its tile with the last counted board (8x8: boards
+    6 and 7; 6x7: boards 6, 7 and 8), board 8 holds a NaN too — keep their sentinel."""
+    from zeroclone_amd.nets import MfmaPolicyValueNetwork
+    c, h, w = board
+    mnet = MfmaPolicyValueNetwork(wide_policy_net(c, h, w, "linear"))
+    tower = mnet.tower
+    _, bad = poisoned(c, h, w)
+    bad[7] = float("nan")
+    xg = bad.cuda()
+    cnt = torch.tensor([7], dtype=torch.int32, device="cuda")
+    a, vals = tower.tower(xg, head=True)
+    want_a, want_v = a.clone(), vals.clone()
+    pout = torch.empty((NB, h * w, 32), dtype=torch.float16, device="cuda")
+    want_pv = tower.tower_policy(xg, mnet.pw, mnet.pb, pout).clone()
+    want_p = pout.clone()
+    assert torch.isnan(want_v[[2, 5]]).all() and torch.isnan(want_p[2]).any() and torch.isnan(want_p[5]).any()
+    assert torch.isfinite(want_v[[0, 1, 3, 4, 6]]).all() and not torch.isnan(want_a[6]).any()
+    a.fill_(-3.0)
+    vals.fill_(-3.0)
+    a2, v2 = tower.tower(xg, head=True, count=cnt)
+    torch.cuda.synchronize()
+    assert same_bits(a2[:7], want_a[:7]) and same_bits(v2[:7], want_v[:7])
+    assert (a2[7:] == -3.0).all() and (v2[7:] == -3.0).all()
+    pout.fill_(-3.0)
+    vals.fill_(-3.0)
+    v3 = tower.tower_policy(xg, mnet.pw, mnet.pb, pout, count=cnt)
+    torch.cuda.synchronize()
+    assert same_bits(pout[:7], want_p[:7]) and same_bits(v3[:7], want_pv[:7])
+    assert (pout[7:] == -3.0).all() and (v3[7:] == -3.0).all()
+
+
+@pytest.mark.parametrize("what", ["bias", "weight"])
+@pytest.mark.parametrize("board", BOARDS, ids=BOARD_IDS)
+def test_nan_parameter_reaches_every_output(board, what):
+    """A NaN folded bias at one channel of block 1's first conv, or one NaN weight (the centre
+    tap: no zero padding meets it), at 64 channels: that output channel is NaN on every pixel
+    (the layered interval check demands it at the first ReLU already), and every board's
+    activation, value, pout and logits hold NaN in the fused tower."""
+    import copy
+    from zeroclone_amd.nets import MfmaPolicyValueNetwork
+    c, h, w = board
+    net = copy.deepcopy(wide_policy_net(c, h, w, "linear"))
+    with torch.no_grad():
+        if what == "bias":
+            net.res[0].seq[1].bias[7] = float("nan")
+        else:
+            net.res[0].seq[0].weight[9, 3, 1, 1] = float("nan")
+    mnet = MfmaPolicyValueNetwork(net)
+    assert mnet.fused and mnet.tower.channels == C
+    ch = 7 if what == "bias" else 9
+    x = planes(5, c, h, w, seed=13)
+
+    def check(i, got, src, res, wt, bias):
+        interval_check((board, what))(i, got, src, res, wt, bias)
+        if i == 1:
+            assert torch.isnan(got[..., ch]).all() and not torch.isnan(got[..., :ch]).any()
+    want = layered(mnet.tower, nhwc32(x).cuda(), check)
+    assert torch.isnan(want).any(dim=(1, 2, 3)).all()
+    a, vals = mnet.tower.tower(x.cuda(), head=True)
+    assert same_bits(a.cpu().reshape(want.shape), want), (board, what)
+    assert torch.isnan(vals).all()
+    v, logits = mnet(x.cuda())
+    assert torch.isnan(v).all() and torch.isnan(mnet._pout[(5, h * w)]).any(dim=(1, 2)).all()
+    assert torch.isnan(logits).any(dim=1).all()
+
+
+def test_pool_with_a_nan_bias_stops_every_game():
+    """A 4-game Connect4 pool at 8 simulations whose 64-channel network — the MFMA tower, value
+    head and policy head of csrc/net_conv64.hip — has a NaN BN bias in block 1: the search of every
+    game ends with ZC_STATUS_INTERNAL (the backup's fence on the NaN value) and check() raises."""
+    from zeroclone_amd import _native
+    from zeroclone_amd.nets import MfmaPolicyValueNetwork, MfmaValueNetwork, PolicyValueNetwork
+    from zeroclone_amd.selfplay import C4SelfPlay
+    torch.manual_seed(0)
+    net = PolicyValueNetwork(C, blocks=2, in_planes=2, board=(6, 7), n_logits=7).eval()
+    with torch.no_grad():
+        net.res[0].seq[1].bias[7] = float("nan")
+    pnet = MfmaPolicyValueNetwork(net)
+    assert isinstance(pnet.tower, MfmaValueNetwork) and pnet.tower.channels == C and pnet.fused
+    pool = C4SelfPlay(4, 8, batch_size=8, seed=3, puct_net=pnet)
+    try:
+        pool.step_search()
+        torch.cuda.synchronize()
+        assert pool.stats[:, 5].cpu().tolist() == [_native.ZC_STATUS_INTERNAL] * 4
+        with pytest.raises(RuntimeError, match="ZC_STATUS_INTERNAL"):
+            pool.check()
+    finally:
+        pool.close()
 
 
 # ---- 7. refusals ------------------------------------------------------------------------------

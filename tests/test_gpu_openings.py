@@ -451,6 +451,55 @@ def test_set_networks_swaps_the_colours(cached):
     arena.close()
 
 
+def test_set_networks_swaps_the_colours_across_widths():
+    """The cached arena handed a 64-channel network against a 128-channel one, then the same two
+    with the names swapped: the first pair plays the plain arena's games of that pair, the second
+    the mirrored result.  After each call both tables are empty (the header and every meta word
+    zero), so the counters of the games that follow are those of tables filled from nothing: the
+    rows a new arena of that pair probes, and new inserts in both."""
+    x64, y128 = integer_net(2, 5, 64), net("c4_value", 6)
+    assert (x64.channels, y128.channels) == (64, 128)
+    kw = dict(eval_cache=ENTRIES, eval_merge=True)
+    arena = c4_arena(net("c4_value", 5), y128, **kw)
+
+    def empty_tables():
+        torch.cuda.synchronize()
+        cache = arena._caches[0]
+        meta = 64 + 4 * _native.EVALCACHE_WAYS * cache.sets
+        return len(cache.tables) == 2 and all(int(t[:meta].count_nonzero()) == 0 for t in cache.tables)
+
+    def used_tables():
+        cache = arena._caches[0]
+        meta = 64 + 4 * _native.EVALCACHE_WAYS * cache.sets
+        return all(int(t[:meta].count_nonzero()) > 0 for t in cache.tables)
+
+    results = []
+    for pair in ((x64, y128), (y128, x64)):
+        arena.set_networks(*pair)
+        assert empty_tables()
+        assert [n.channels for n in arena.routed.nets] == [n.channels for n in pair]
+        before = arena.eval_cache_stats(by_network=True)
+        results.append(arena.play(16, max_steps=2000))
+        assert used_tables()
+        bt = arena.last_batch
+        games = (bt.rows.cpu(), bt.labels.cpu(), bt.moves.cpu(), bt.games.cpu())
+        after = arena.eval_cache_stats(by_network=True)
+        fresh = c4_arena(*pair) if pair[0] is x64 else c4_arena(*pair, **kw)
+        assert fresh.play(16, max_steps=2000) == results[-1]
+        fb = fresh.last_batch
+        same_games(games, (fb.rows.cpu(), fb.labels.cpu(), fb.moves.cpu(), fb.games.cpu()))
+        if pair[0] is not x64:   # the counters against a new cached arena's, which start at zero
+            for x, y, z in zip(before, after, fresh.eval_cache_stats(by_network=True)):
+                assert y["probed"] - x["probed"] == z["probed"] > 0
+        for x, y in zip(before, after):
+            assert y["probed"] > x["probed"] and y["inserts"] > x["inserts"] and y["hits"] > x["hits"]
+        fresh.check()
+        fresh.close()
+    assert results[1] == mirrored(results[0]) and results[1].score == 1.0 - results[0].score
+    arena.check()
+    arena.close()
+
+
 def test_chess_arena_with_a_book():
     a, b = net("chess_value", 5), net("chess_value", 6)
     kw = dict(batch_size=BS, seed=5, hist_cap=HIST_CAP)

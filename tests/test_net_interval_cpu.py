@@ -4,7 +4,9 @@ correct kernel: it must lie wholly inside the accepted interval, and four subtly
 (the conv rounded to fp16 before the residual add, one tap dropped at one pixel, the bias
 added in fp16, ReLU before the residual) must fall outside it for at least 100 elements.
 The generator's inputs must leave fewer than half of the intervals holding two fp16 values
-(a condition on the inputs: an ambiguous element still rejects every value but those two)."""
+(a condition on the inputs: an ambiguous element still rejects every value but those two).
+The same for the value head: five subtly wrong heads against the synthetic activations of the
+GPU tests of the stand-alone head, at both widths."""
 import numpy as np
 import pytest
 import torch
@@ -81,6 +83,59 @@ def test_mutants_fall_outside(layer, mutant, least):
         mask = torch.zeros(s.shape, dtype=torch.bool)
         mask[:, 2, 3, :] = True
         assert int(nc.outside(got, lo, hi, s)[~mask].sum()) == 0 and int(mask.sum()) == 1664
+
+
+def head_cases(channels):
+    """The inputs of the stand-alone value head's GPU tests (test_gpu_net_range.py at 128 channels,
+    test_gpu_net_width.py at 64), drawn as there: (hw, n, cancelling set, spread set)."""
+    for hw in (64, 42):
+        g = torch.Generator().manual_seed(hw)
+        for n in (1, 5):
+            yield hw, n, nc.cancelling_head_inputs(g, n, hw, channels), nc.spread_head_inputs(
+                1000 * channels + 10 * hw + n, n, hw, channels)
+
+
+# which set must reject which wrong head ("divide_by_64" is a wrong head on 6x7 alone)
+CANCELLING_CATCHES = ("fp16_pixel_sums", "fp16_weights", "divide_by_64")
+SPREAD_CATCHES = ("fp16_pixel_sums", "divide_by_64", "pair_weights_swapped", "one_lane_left_out")
+
+
+@pytest.mark.parametrize("channels", [64, 128])
+def test_wrong_value_heads_fall_outside_the_slack(channels):
+    """The synthetic activations of the value head's GPU tests tell a wrong head from a right one:
+    each of nn_check.HEAD_MUTANTS, computed in float64 from the head's inputs alone, is NaN or
+    outside value_head_reference's slack on at least one board of every (hw, n, fcb) case.
+
+    The cancelling set (channel pairs with the same activation under opposite weights) rejects the
+    fp16 pixel sums (NaN: inf - inf), the fp16 weights (1.7 to 17 slacks) and the division by 64 on
+    6x7 (7 to 17 slacks).  It cannot see the two weights of a pair exchanged (its two channels hold
+    the same activation, so the sum is the same) and sees one lane's share of channels 8 .. 15
+    left out in a few cases only (the term leaves both channels of a pair and cancels: 0 to 2.4
+    slacks).  The spread set (every channel its own activation and weight) was added for those
+    two and rejects both in every case, by 40 slacks at the least; with it every named wrong head
+    is caught in every case at both widths.  A right head in fp32 (torch's sums) lies inside
+    the slack on both sets."""
+    assert set(CANCELLING_CATCHES) | set(SPREAD_CATCHES) == set(nc.HEAD_MUTANTS)
+    for hw, n, cancelling, spread in head_cases(channels):
+        for fcb in nc.HEAD_FCBS:
+            for name, (act, fcw), catches in (("cancelling", cancelling, CANCELLING_CATCHES), ("spread", spread, SPREAD_CATCHES)):
+                d, slack = nc.value_head_reference(act, fcw, fcb)
+                assert 5.0e4 < act.max().item() and torch.isfinite(act).all() and slack.max().item() < 0.5
+                assert (d - float(np.float32(fcb))).abs().max().item() < 2.0
+                right = ((act.float().sum(dim=1) * fcw).sum(dim=1) / np.float32(hw) + np.float32(fcb)).double()
+                assert not nc.head_rejects(right, d, slack).any(), (channels, hw, n, fcb, name)
+                for mutant in catches:
+                    if mutant == "divide_by_64" and hw == 64:
+                        continue
+                    wrong = nc.wrong_head(act, fcw, fcb, mutant)
+                    bad = nc.head_rejects(wrong, d, slack)
+                    print(f"{channels} channels hw {hw} n {n} fcb {fcb} {name} {mutant}: {int(bad.sum())} of {n} boards, "
+                          f"{((wrong - d).abs() / slack).max().item():.1f} slacks")
+                    assert bad.any(), (channels, hw, n, fcb, name, mutant)
+            # the blind spot that the spread set closes, stated so that it stays known
+            act, fcw = cancelling
+            d, slack = nc.value_head_reference(act, fcw, fcb)
+            assert not nc.head_rejects(nc.wrong_head(act, fcw, fcb, "pair_weights_swapped"), d, slack).any()
 
 
 def test_overflow_set_demands_the_infinities():
