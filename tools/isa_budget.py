@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Static instruction budget of the Connect4 rollout loop (CPU only: a cross-compile).
 
-    python tools/isa_budget.py [--asm FILE] [--label TEXT]
+    python tools/isa_budget.py [--asm FILE] [--label TEXT] [--kernel KEY] [--instances]
 
 Compiles zeroclone_amd/csrc/c4_search.hip to gfx950 assembly with build.py's flags (ZC_CFLAGS
 honoured; --asm FILE reads an assembly file made that way instead), finds the rollout loops of
-c4_selfplay_kernel<false> by the win test's ds_permute_b32 + v_permlane32_swap — one test in
+c4_selfplay_kernel<false, kModeCarry, true> (the headline's instance: exact rollouts, pooled
+carry, planned flush; --kernel KEY: the instance whose mangled name holds KEY) by the win test's ds_permute_b32 + v_permlane32_swap — one test in
 a loop over blocks inside the loop over leaves, or two when a rollout's first block stands in
 the leaf loop itself and the others in a loop of their own — and prints
 
@@ -26,9 +27,15 @@ the leaf loop itself and the others in a loop of their own — and prints
     per 64 generated words, and the instructions of a view (from the refill's join to the
     lane's word: a ds_bpermute_b32 of the window registers, or a byte read of the draw ring);
   * the flush outside the rollouts (flush_budget below): a level of the prefetching walk, stage
-    1a of the planned flush, the draw table + chase, stages 2-3, backup + publish;
-  * next_free_vgpr and the private segment size of c4_selfplay_kernel<false> and
-    c4_search_kernel<false,false>.
+    1a of the planned flush, the draw table + chase, stages 2-3, backup + publish (every block
+    once, and the executed path's bounds: the longest way through the planned backup, every
+    lane-parallel section and mode test entered, and the shortest, all of them skipped), the serial loop's trip for a dead leaf, and per region the spilled-scalar
+    reloads (v_readlane_b32 sN, vK, imm from a VGPR that only v_writelane_b32 with an
+    immediate lane ever writes: the allocator's SGPR spill registers);
+  * next_free_vgpr and the private segment size of that instance and of the planned lockstep
+    search, c4_search_kernel<false, false, true>;
+  * --instances: registers, spills and scratch of every search instance, and whether each
+    holds the other flush path's code (select_flush's ds_add backup in a planned instance).
 
 profiles/c4_rollout_isa_budget.txt and profiles/c4_flush_isa_budget.txt keep the output for the
 code before and after a change.
@@ -43,8 +50,9 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-KERNEL = "c4_selfplay_kernelILb0EE"
-ALSO = ["c4_search_kernelILb0ELb0EE"]
+KERNEL = "c4_selfplay_kernelILb0ELi3ELb1EE"   # <PHILOX false, kModeCarry, PLANNED true>
+ALSO = ["c4_search_kernelILb0ELb0ELb1EE"]     # <STAMP false, PHILOX false, PLANNED true>
+OLD_NAMES = {KERNEL: "c4_selfplay_kernelILb0EE", ALSO[0]: "c4_search_kernelILb0ELb0EE"}  # before the mode split
 OTHER = ("s_waitcnt", "s_nop", "s_branch", "s_cbranch", "s_setprio", "s_sleep", "s_endpgm", "s_barrier",
          "s_setpc", "s_sendmsg", "s_trap", "s_inst_prefetch", "s_code_end")
 
@@ -203,6 +211,70 @@ def stream_budget(blocks, byname, head, out):
     return {"refill": n, "words": words, "per64": n * 64 / words, "view": nview}
 
 
+def operands(op, s):
+    return [t.strip() for t in s[len(op):].split(",")]
+
+
+def vregs(tok):
+    """The VGPR numbers of an operand: v5 -> [5], v[4:7] -> [4, 5, 6, 7], anything else -> []."""
+    m = re.fullmatch(r"v(\d+)", tok)
+    if m:
+        return [int(m.group(1))]
+    m = re.fullmatch(r"v\[(\d+):(\d+)\]", tok)
+    return list(range(int(m.group(1)), int(m.group(2)) + 1)) if m else []
+
+
+def spill_vgprs(blocks):
+    """The allocator's SGPR spill registers: VGPRs written by v_writelane_b32 with an immediate lane
+    and by nothing else (the code's own lane writes select the lane from an SGPR or M0)."""
+    lanes, other = set(), set()
+    for b in blocks:
+        for op, s in b.ins:
+            ops = operands(op, s)
+            if op == "v_writelane_b32" and len(ops) == 3 and re.fullmatch(r"\d+", ops[2]):
+                lanes.update(vregs(ops[0]))
+            elif op.startswith(("v_swap", "v_permlane32_swap", "v_permlane16_swap")):
+                other.update(v for t in ops for v in vregs(t))
+            elif op.startswith(("v_", "ds_", "global_load", "buffer_load", "scratch_load", "flat_load")):
+                other.update(vregs(ops[0]))
+    return lanes - other
+
+
+def reloads(byname, names, spill):
+    """Spilled scalars read back in these blocks."""
+    n = 0
+    for b in names:
+        for op, s in byname[b].ins:
+            ops = operands(op, s)
+            if (op == "v_readlane_b32" and len(ops) == 3 and re.fullmatch(r"\d+", ops[2])
+                    and set(vregs(ops[1])) & spill):
+                n += 1
+    return n
+
+
+def longest_path(byname, pos, names, src, dst, longest=True):
+    """The costliest (or cheapest) way src .. dst through `names` along forward (layout-order) edges;
+    None: no way."""
+    memo = {}
+
+    def go(n):
+        if n not in memo:
+            best = None
+            for s in byname[n].succ:
+                if s == dst:
+                    cand = []
+                elif s in names and pos[s] > pos[n]:
+                    cand = go(s)
+                else:
+                    continue
+                if cand is not None and (best is None or (cost(byname, cand) > cost(byname, best)) == longest):
+                    best = cand
+            memo[n] = None if best is None else [n] + best
+        return memo[n]
+
+    return go(src)
+
+
 def flush_budget(blocks, byname, Lh, out):
     """The flush outside the rollouts (select_flush_plan, backup, publish), by the same columns.
 
@@ -260,11 +332,80 @@ def flush_budget(blocks, byname, Lh, out):
     print(f"flush {'stages 2-3':<28} {fmt_counts(byname, st23)}  {len(st23)} blocks", file=out)
     print(f"flush {'backup + publish':<28} {fmt_counts(byname, tail)}  {len(tail)} blocks", file=out)
     res.update(chase=chase.n(), stages23=cost(byname, st23), tail=cost(byname, tail))
+    # the executed path of backup + publish lies between the longest way from the leaf loop's exit
+    # round to the flush loop's header (every lane-parallel section entered, X0 rewritten, every
+    # mode's test taken) and the shortest (all of them skipped)
+    # (it starts at the first of the flush loop's own blocks there: rare blocks of the leaf loop
+    # can be laid out after its last common one; the loops of the flush that is not planned are
+    # left out, so in a kernel that holds both flushes this is the planned one's path)
+    own = [n for n in tail if byname[n].loop == F]
+    if own:
+        sys.setrecursionlimit(max(sys.getrecursionlimit(), 4 * len(blocks)))
+        # through the planned backup's prefix sum (row_bcast:31 ends scan_add32) when there is one
+        scan = next((n for n in own if has(byname, [n], "row_bcast:31")), None)
+        for longest, name, key in ((True, "backup + publish, longest", "tail_run"),
+                                   (False, "backup + publish, shortest", "tail_min")):
+            if scan and scan != own[0]:
+                head = longest_path(byname, pos, set(own), own[0], scan, longest)
+                rest = longest_path(byname, pos, set(own), scan, F, longest)
+                run = head + rest if head and rest else None
+            else:
+                run = longest_path(byname, pos, set(own), own[0], F, longest)
+            if run:
+                print(f"flush {name:<28} {fmt_counts(byname, run)}  {len(run)} blocks", file=out)
+                res[key] = cost(byname, run)
+    # a dead leaf (won or full at its start): the serial loop's trip that passes no win test
+    in_leaf = {b.name for b in inF if Lh in loop_chain(byname, b)}
+    tests = {b.name for b in inF if any(op == "ds_permute_b32" for op, _ in b.ins)
+             and any(op.startswith("v_permlane32_swap") for op, _ in b.ins)}
+    calm = {n for n in in_leaf - tests if not any(has(byname, [n], m) for m in STREAM_MARKS)}
+    dead = [p[:-1] for p in all_paths(byname, Lh, Lh, calm)]
+    if dead:
+        p = min(dead, key=lambda p: cost(byname, p))
+        print(f"flush {'dead leaf, serial loop trip':<28} {fmt_counts(byname, p)}  " + " ".join(p), file=out)
+        res["dead_leaf"] = cost(byname, p)
+    else:
+        print(f"flush {'dead leaf, serial loop trip':<28} none: every trip of the leaf loop passes a win test", file=out)
+        res["dead_leaf"] = 0
+    # spilled scalars read back, per region
+    spill = spill_vgprs(blocks)
+    regions = (("walk level loop", sorted(wnames)), ("leaf + block loops", sorted(in_leaf)),
+               ("stages 1a-3", once + [chase.name] + st23), ("backup + publish", tail),
+               ("whole flush loop", [b.name for b in inF]))
+    print(f"spill registers: {' '.join('v%d' % v for v in sorted(spill)) or 'none'}", file=out)
+    res["reloads"] = {}
+    for name, names in regions:
+        res["reloads"][name] = reloads(byname, names, spill)
+        print(f"spilled-scalar reloads, {name:<20} {res['reloads'][name]:3d}", file=out)
     return res
 
 
-def analyse(lines, out):
-    fn, blocks = parse_function(lines, KERNEL)
+def instances(lines, out):
+    """Every search instance: registers, SGPR spills, scratch, and the flush paths its body holds
+    (planned: select_flush_plan's unrolled chase; not planned: the atomic backup's ds_add)."""
+    text = "\n".join(lines)
+    meta = text[text.index("amdhsa.kernels"):]
+    res = {}
+    for m in re.finditer(r"\.amdhsa_kernel (\S*(c4_(?:search|selfplay|walk)_kernelI\w+?E)EvNS\S*)\n(.*?)\.end_amdhsa_kernel",
+                         text, re.S):
+        sym, key, body = m.group(1), m.group(2), m.group(3)
+        vg = int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", body).group(1))
+        ps = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1))
+        md = re.search(r"\.name:\s+" + re.escape(sym) + r"\n.*?\.sgpr_spill_count:\s+(\d+)", meta, re.S)
+        ops = [op for b in parse_function(lines, key + "EvNS")[1] for op, _ in b.ins]
+        res[key] = dict(vgprs=vg, scratch=ps, sgpr_spills=int(md.group(1)) if md else -1, n=len(ops),
+                        chase=ops.count("s_bitset1_b64"), ds_add=sum(op.startswith("ds_add") for op in ops))
+        r = res[key]
+        print(f"{key:<36} vgprs {vg:3d}  scratch {ps:3d}  sgpr spills {r['sgpr_spills']:3d}  instructions {r['n']:5d}"
+              f"  chase s_bitset1 {r['chase']:2d}  backup ds_add {r['ds_add']:2d}", file=out)
+    return res
+
+
+def analyse(lines, out, kernel=None):
+    kernel = asked = kernel or KERNEL
+    if not any(re.match(r"^_Z\S*" + re.escape(kernel), l) for l in lines):  # an assembly from before the mode split
+        kernel = OLD_NAMES.get(kernel, kernel)
+    fn, blocks = parse_function(lines, kernel)
     byname = {b.name: b for b in blocks}
     depth = lambda b: byname[b.loop].header_of if b.loop else 0
     tests = [b for b in blocks if any(op == "ds_permute_b32" for op, _ in b.ins)
@@ -325,8 +466,9 @@ def analyse(lines, out):
         print(f"flush section: markers not found ({type(e).__name__})", file=out)
     print(file=out)
     text = "\n".join(lines)
-    for key in [KERNEL] + ALSO:
-        m = re.search(r"\.amdhsa_kernel (\S*" + re.escape(key) + r"\S*)\n(.*?)\.end_amdhsa_kernel", text, re.S)
+    for key in [asked] + ALSO:
+        m = (re.search(r"\.amdhsa_kernel (\S*" + re.escape(key) + r"\S*)\n(.*?)\.end_amdhsa_kernel", text, re.S) or
+             re.search(r"\.amdhsa_kernel (\S*" + re.escape(OLD_NAMES.get(key, key)) + r"\S*)\n(.*?)\.end_amdhsa_kernel", text, re.S))
         body = m.group(2)
         vg = re.search(r"\.amdhsa_next_free_vgpr (\d+)", body).group(1)
         ps = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)
@@ -339,6 +481,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--asm", help="analyse this assembly file instead of compiling")
     ap.add_argument("--label", help="a heading printed first (e.g. the commit)")
+    ap.add_argument("--kernel", help="part of the mangled name of the self-play instance to analyse")
+    ap.add_argument("--instances", action="store_true", help="also list every search instance")
     a = ap.parse_args()
     if a.asm:
         lines = open(a.asm).read().splitlines()
@@ -349,7 +493,10 @@ def main():
             lines = open(path).read().splitlines()
     if a.label:
         print(f"== {a.label}")
-    analyse(lines, sys.stdout)
+    analyse(lines, sys.stdout, a.kernel)
+    if a.instances:
+        print()
+        instances(lines, sys.stdout)
 
 
 if __name__ == "__main__":

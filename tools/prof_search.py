@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The bench's own workload for rocprofv3 passes: C4SelfPlay at 4096 games x 800 sims x bs 32,
 burned in to steady state (every slot has finished a game and started another, as bench.py
-does), then --steps x G timed moves in one pooled launch (--launch free: --steps moves per game) (c4_selfplay_kernel<false>, the
+does), then --steps x G timed moves in one pooled launch (--launch free: --steps moves per game) (c4_selfplay_kernel<false, kModeCarry, true>, the
 last launch of the trace; tools/summarize_profile.py --moves K reports it per move)."""
 import argparse
 import os

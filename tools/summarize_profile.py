@@ -29,7 +29,8 @@ import hashlib
 import json
 import os
 
-KERNEL = "c4_selfplay_kernel<false>"  # the product kernel (K self-play moves per launch)
+# the product kernel (K self-play moves per launch): exact rollouts, kModeCarry, planned flush
+KERNEL = "c4_selfplay_kernel<false, 3, true>"
 N_CU, N_SIMD, N_XCD = 256, 1024, 8
 
 

@@ -200,9 +200,15 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
         }
       }
       const int jend = min(nb, g + 64);
-      for (int j = g; j < jend; ++j) {
+      // A dead leaf (room < 0: the last mover has four, -1; the board is full, 0) has its value in
+      // its lane already and consumes no word: only the live leaves take a turn of the serial
+      // loop, in ascending lane order — pending order, so the stream is consumed as before.
+      val_v = room_v < 0 ? (room_v + 1) >> 1 : 0;
+      uint64_t live = __ballot(g + (int)lane < nb && room_v >= 0);
+      while (live) {
         RMARK(6);  // regions: 1 leaf setup, 2 view, 3 first segment, 4 absorbed fill, 5 win test, 6 block tail
-        const int jl = j - g;
+        const int jl = (int)ff1(live), j = g + jl;
+        __asm__("s_bitset0_b64 %0, %1" : "+s"(live) : "s"(jl));  // clear the lowest set bit in one SALU
         const uint32_t lm = (uint32_t)__builtin_amdgcn_readlane((int)lm_v, jl);
         // the leaf's boards straight from LDS into VGPRs: one 16-byte read of (p0, p1) at a
         // uniform address (a broadcast), waited for where the win test first uses them.  They
@@ -214,11 +220,10 @@ __device__ void c4_rollouts(Leaf *L, int nb, R &rng, const uint32_t *s_order, Co
         uint64_t S1 = (lm >> 24) & 1u ? ~second_rows : second_rows;
         uint32_t hp = (uint32_t)__builtin_amdgcn_readlane((int)hp_v, jl);  // column heights, carried across blocks
         const uint32_t low0 = (uint32_t)__builtin_amdgcn_readlane((int)ow_v, jl);
-        const int room0 = __builtin_amdgcn_readlane(room_v, jl);
-        int val = (room0 + 1) >> 1;  // -2: has_four(last mover), -1; -1: check_draw, 0
-        int q = 0;  // plies played in this rollout (room0 - room when it ends)
+        const int room0 = __builtin_amdgcn_readlane(room_v, jl);  // >= 0: neither won nor full
+        int val, q;  // the value; plies played in this rollout (room0 - room when it ends)
         RMARK(1);
-        if (room0 >= 0) {  // neither
+        {
             int room = room0;
             int mask = (int)(lm >> 25);
             uint32_t ow = low0;
@@ -577,6 +582,17 @@ __device__ __forceinline__ WalkEnd walk_hbm_prefetch(const Tree &t, ConstDouble 
     const uint32_t lane = lane_id();
     const uint32_t k = lane & 7u, cs = lane >> 3;  // the slot this lane scores / the child it fetches
     const float cf = (float)c;
+    // The level loop's invariants get live ranges of their own, from here to the walk's end: as the
+    // launch's parameters they are live through the whole kernel, the allocator spills them, and
+    // the loop then read them back level by level (v_readlane and its s_nop; tools/isa_budget.py
+    // counts the reloads per region).  The margin only feeds a v_sub: a VGPR.
+    __asm__("" : "+v"(delta));
+    __asm__ volatile("" : "+s"(logtab));
+    {
+        uint64_t cb = (uint64_t)__double_as_longlong(c);
+        __asm__ volatile("" : "+s"(cb));
+        c = __longlong_as_double((long long)cb);
+    }
     (void)cn;  // counts only in the -DZC_DIAG_UCT build
     int node = 0, depth = 0, turn = rturn, nN = done;  // nN = N(node) = Na of its in-edge
     uint64_t b0 = rp0, b1 = rp1;
@@ -996,15 +1012,27 @@ __device__ __forceinline__ SearchLds search_lds(uint8_t *s_dyn, int bs) {
 // flush's rollout words (p.walk_vals / p.walk_words); 2 = replay them instead of running the
 // rollouts — the tree walk, expansion, backup and publish alone on the identical tree.
 // done / nnodes: the simulations already run and the tree's nodes (0 / 1: a new search from
-// the root; else a carried move resumes, its tree as the last flush published it).  stop
-// (carry launches): the pooled ticket counter — once it reaches `budget` the search returns
+// the root; else a carried move resumes, its tree as the last flush published it).  Carry
+// launches: once the pooled ticket counter p.ticket[0] reaches p.budget the search returns
 // at the next flush boundary with done < p.sims (the move is suspended, not abandoned).
-template <bool STAMP, bool PHILOX, int WALK = 0>
+//
+// The launch's mode is compiled in (MODE, PLANNED): a launch runs one combination for its whole
+// life, so each instance holds only what its mode reads — the budget load and the suspend test
+// in the carry instance, the progress load and the priority ladders in the paced one, one of
+// the two flush paths (PLANNED = bs < 64: select_flush_plan and the prefix-sum backup; else
+// select_flush and the atomic backup).  The host picks the instance (launch_c4_*).
+enum : int {
+    kModePlain = 0,   // no pacing, no budget: the lockstep search, the walk diagnostic
+    kModePaced = 1,   // free self-play run: pace balancing on p.progress
+    kModePooled = 2,  // pooled tickets: a move per ticket, searched like kModePlain
+    kModeCarry = 3,   // pooled carry: tickets, and the search suspends once the budget is spent
+};
+template <bool STAMP, bool PHILOX, int WALK, int MODE, bool PLANNED>
 __device__ __forceinline__ void search_move(const SearchParams &p, const SearchLds &L, int gl, int g, const Tree &t,
                                             LRng &rng, uint32_t tag, Counters &cn, int &status, int &done_io,
-                                            int &nnodes_io, const int32_t *stop = nullptr, int32_t budget = 0,
-                                            int *lagp = nullptr, const int32_t *progress = nullptr, int mv = 0) {
-    int lag = lagp ? *lagp : 0;
+                                            int &nnodes_io, int *lagp = nullptr, int mv = 0) {
+    constexpr bool kPaced = MODE == kModePaced, kCarry = MODE == kModeCarry;
+    int lag = kPaced ? *lagp : 0;
     const uint32_t lane = lane_id();
     const uint32_t *const s_order = L.s_order;
     Fresh *const fresh = L.fresh;
@@ -1030,7 +1058,7 @@ __device__ __forceinline__ void search_move(const SearchParams &p, const SearchL
         {
             const zc_c4_state root = p.roots[gl];
             // one lane per draw and lane 63 free as the permutes' discard slot (bs < 64)
-            if (p.bs < 64)
+            if constexpr (PLANNED)
                 select_flush_plan<STAMP>(t, fresh, leaves, s_order, logtab, rng, cn, stamp, nnodes, status,
                                          uni64(root.stones[0]), uni64(root.stones[1]), uni(root.turn), done, nb,
                                          p.c, p.uct_delta, fs);
@@ -1061,9 +1089,11 @@ __device__ __forceinline__ void search_move(const SearchParams &p, const SearchL
             constexpr int kRolloutPrio = 1;
             // `lag` (free runs): how far this game is behind the launch's average pace; its
             // phases run that many levels up, so the arbiter evens the games' paces out
-            set_prio(lag + kRolloutPrio);
+            if constexpr (kPaced) set_prio(lag + kRolloutPrio);
+            else __builtin_amdgcn_s_setprio(kRolloutPrio);
             c4_rollouts(leaves, nb, rng, s_order, cn, STAMP ? &stamp.ph[7] : nullptr);
-            set_prio(lag);
+            if constexpr (kPaced) set_prio(lag);
+            else __builtin_amdgcn_s_setprio(0);
             if (WALK == 1) {
                 wave_mem_order();
                 for (int jj = (int)lane; jj < nb; jj += kBlock) p.walk_vals[wlog + jj] = (int8_t)leaves[jj].val;
@@ -1088,15 +1118,14 @@ __device__ __forceinline__ void search_move(const SearchParams &p, const SearchL
         int32_t na0 = 0, w0 = 0, spent_v = 0;
         // carry launches: the budget's state, read beside the prefix counters (one round trip);
         // free runs: the launch's finished moves (pace balancing)
-        if (stop) spent_v = __hip_atomic_load(stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (progress)
-            spent_v = __hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (kCarry) spent_v = __hip_atomic_load(p.ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (kPaced) spent_v = __hip_atomic_load(p.progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (pre) {
             na0 = t.na(par)[act];
             w0 = t.w(par)[act];
         }
-        const int32_t spent = stop || progress ? uni(spent_v) : 0;
-        if (fs.planned) {
+        const int32_t spent = kCarry || kPaced ? uni(spent_v) : 0;
+        if constexpr (PLANNED) {
             // The planned flush's fresh nodes are the draws 0..D-1 (leaf j <-> node f0 + j for
             // j < D; the leaves D..nb-1 sit on the terminal chain node).  A fresh node's subtree is
             // itself, plus — for a chain node (a Z draw) — every leaf from the next chain node's
@@ -1235,8 +1264,9 @@ __device__ __forceinline__ void search_move(const SearchParams &p, const SearchL
         wave_mem_order();
         stamp.mark(6);
         done += nb;
-        if (stop && done < p.sims && status == 0 && uni(spent) >= budget) break;  // suspend
-        if (progress) {  // behind the average (in simulations): 1; by a move or more: 2
+        if constexpr (kCarry)
+            if (done < p.sims && status == 0 && uni(spent) >= p.budget) break;  // suspend
+        if constexpr (kPaced) {  // behind the average (in simulations): 1; by a move or more: 2
             const int64_t own = ((int64_t)mv * p.sims + done) * p.n_games, avg = (int64_t)spent * p.sims;
             const int64_t mvn = (int64_t)p.sims * p.n_games;  // one move behind
             lag = own >= avg ? 0 : own + mvn <= avg ? 2 : 1;
@@ -1245,7 +1275,7 @@ __device__ __forceinline__ void search_move(const SearchParams &p, const SearchL
     }
     done_io = done;
     nnodes_io = nnodes;
-    if (lagp) *lagp = lag;
+    if constexpr (kPaced) *lagp = lag;
     if (STAMP && lane == 0)
         for (int k_ = 0; k_ < kPhases; ++k_) p.a.phase[kPhases * (size_t)g + k_] += (int64_t)stamp.ph[k_];
 }
@@ -1269,7 +1299,7 @@ __device__ __forceinline__ int best_column(const Tree &t, int &na_col) {
     return (int)((ow >> (3 * best)) & 7u);
 }
 
-template <bool STAMP, bool PHILOX, int WALK>
+template <bool STAMP, bool PHILOX, int WALK, bool PLANNED>
 __device__ __forceinline__ void search_games(const SearchParams &p, uint8_t *s_dyn) {
     const SearchLds L = search_lds(s_dyn, p.bs);
     load_tables(L.s_order);
@@ -1301,7 +1331,8 @@ __device__ __forceinline__ void search_games(const SearchParams &p, uint8_t *s_d
     lrng_open(rng, L.ring, a.ring + (size_t)g * kRingWords, use0, uni64(a.rngpos[2 * (size_t)g + 1]));
     Counters cn;
     int status = 0, done = 0, nnodes = 1;
-    search_move<STAMP, PHILOX, WALK>(p, L, gl, g, t, rng, uni((uint32_t)use0), cn, status, done, nnodes);
+    search_move<STAMP, PHILOX, WALK, kModePlain, PLANNED>(p, L, gl, g, t, rng, uni((uint32_t)use0), cn, status, done,
+                                                          nnodes);
     int na_col;
     const int col = best_column(t, na_col);
     if (lane < 7) p.out_na[(size_t)gl * 7 + lane] = na_col;
@@ -1321,18 +1352,18 @@ __device__ __forceinline__ void search_games(const SearchParams &p, uint8_t *s_d
     lrng_close(rng, a.ring + (size_t)g * kRingWords, use0, a.rngpos + 2 * (size_t)g);
 }
 
-template <bool STAMP, bool PHILOX>
+template <bool STAMP, bool PHILOX, bool PLANNED>
 __global__ __launch_bounds__(kSearchWaves * kBlock, 4) void c4_search_kernel(SearchParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
-    search_games<STAMP, PHILOX, 0>(p, s_dyn);
+    search_games<STAMP, PHILOX, 0, PLANNED>(p, s_dyn);
 }
 
 // Diagnostic: the lockstep search with its rollouts recorded (WALK 1) or replayed (WALK 2):
 // the tree-walk-only kernel whose time and HBM traffic measure the walk (tools/prof_walk.py).
-template <int WALK>
+template <int WALK, bool PLANNED>
 __global__ __launch_bounds__(kSearchWaves * kBlock, 4) void c4_walk_kernel(SearchParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
-    search_games<false, false, WALK>(p, s_dyn);
+    search_games<false, false, WALK, PLANNED>(p, s_dyn);
 }
 
 // Self-play without a global step: each wave plays `p.moves` consecutive moves of its game —
@@ -1351,8 +1382,10 @@ __global__ __launch_bounds__(kSearchWaves * kBlock, 4) void c4_walk_kernel(Searc
 // nodes, Philox tag} in a.carry[g] (the tree, the MT stream and the root stay in HBM).  EVERY
 // self-play launch first resumes a carried move, without a ticket, so the game's moves are
 // the moves an uninterrupted run plays; only carry launches suspend.
-template <bool PHILOX>
+// MODE (search_move): kModePaced = the free run, kModePooled / kModeCarry = the pooled launches.
+template <bool PHILOX, int MODE, bool PLANNED>
 __global__ __launch_bounds__(kSearchWaves * kBlock, 4) void c4_selfplay_kernel(SearchParams p) {
+    constexpr bool kTickets = MODE == kModePooled || MODE == kModeCarry;
     extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
     const SearchLds L = search_lds(s_dyn, p.bs);
     load_tables(L.s_order);
@@ -1379,7 +1412,7 @@ __global__ __launch_bounds__(kSearchWaves * kBlock, 4) void c4_selfplay_kernel(S
     cy = make_uint4(uni(cy.x), uni(cy.y), uni(cy.z), 0u);
     bool resume = cy.x != 0;
     for (; mv < p.moves; ++mv) {
-        if (p.ticket && !resume) {  // pooled run: the next move only while the shared budget lasts
+        if (kTickets && !resume) {  // pooled run: the next move only while the shared budget lasts
             int tk = 0;
             if (lane == 0) tk = atomicAdd(p.ticket, 1);
             if (uni(tk) >= p.budget) break;
@@ -1397,11 +1430,10 @@ __global__ __launch_bounds__(kSearchWaves * kBlock, 4) void c4_selfplay_kernel(S
         const int done0 = done;
         // free runs (every game exactly p.moves moves, the launch waits for the slowest): a game
         // behind the launch's average pace raises its priority, flush by flush (search_move)
-        search_move<false, PHILOX>(p, L, gl, g, t, rng, tag, cn, status, done, nnodes, p.carry ? p.ticket : nullptr,
-                                   p.budget, &lag, p.progress, mv);
-        if (p.progress && lane == 0) atomicAdd(p.progress, 1);
+        search_move<false, PHILOX, 0, MODE, PLANNED>(p, L, gl, g, t, rng, tag, cn, status, done, nnodes, &lag, mv);
+        if (MODE == kModePaced && lane == 0) atomicAdd(p.progress, 1);
         leaves += done - done0;
-        if (done < p.sims) {  // suspended (carry launch, budget spent): the next launch resumes it
+        if (MODE == kModeCarry && done < p.sims) {  // suspended (carry launch, budget spent): the next launch resumes it
             if (lane == 0) a.carry[g] = make_uint4((uint32_t)done, (uint32_t)nnodes, tag, 0u);
             break;
         }
@@ -1431,7 +1463,7 @@ __global__ __launch_bounds__(kSearchWaves * kBlock, 4) void c4_selfplay_kernel(S
         finished += r != ZC_C4_ONGOING;
         wave_mem_order();
     }
-    if (p.ticket && lane == 0) atomicMax(p.ticket + 1, mv);
+    if (kTickets && lane == 0) atomicMax(p.ticket + 1, mv);
     if (p.tstamps && lane == 0) {
         uint64_t *ts = p.tstamps + 4 * (size_t)g;
         ts[0] = t_start;
@@ -1606,49 +1638,70 @@ static int c4_search_wpg(int bs) {
 
 size_t c4_search_lds_bytes(int bs) { return kTabBytes + (size_t)c4_search_wpg(bs) * c4_search_wave_lds(bs); }
 
+// The instance of a launch: its kernel by the launch's arguments (one body per combination the
+// entry points can ask for).
+using SearchKernel = void (*)(SearchParams);
+template <bool STAMP, bool PHILOX>
+static SearchKernel c4_search_instance(int bs) {
+    return bs < 64 ? c4_search_kernel<STAMP, PHILOX, true> : c4_search_kernel<STAMP, PHILOX, false>;
+}
+template <bool PHILOX, int MODE>
+static SearchKernel c4_selfplay_mode(int bs) {
+    return bs < 64 ? c4_selfplay_kernel<PHILOX, MODE, true> : c4_selfplay_kernel<PHILOX, MODE, false>;
+}
+// mode: the free run (pace balancing; p.progress), pooled tickets, pooled carry
+static int c4_selfplay_mode_of(const SearchParams &p) {
+    return !p.ticket ? kModePaced : p.carry ? kModeCarry : kModePooled;
+}
+static SearchKernel c4_selfplay_instance(int bs, int philox, int mode) {
+    if (philox)
+        return mode == kModePaced    ? c4_selfplay_mode<true, kModePaced>(bs)
+               : mode == kModeCarry ? c4_selfplay_mode<true, kModeCarry>(bs)
+                                    : c4_selfplay_mode<true, kModePooled>(bs);
+    return mode == kModePaced    ? c4_selfplay_mode<false, kModePaced>(bs)
+           : mode == kModeCarry ? c4_selfplay_mode<false, kModeCarry>(bs)
+                                : c4_selfplay_mode<false, kModePooled>(bs);
+}
+
 void launch_c4_search(const SearchParams &p, hipStream_t s) {
     const int wpg = c4_search_wpg(p.bs);
     const size_t lds = c4_search_lds_bytes(p.bs);
     const dim3 grid((p.n_games + wpg - 1) / wpg), block(wpg * kBlock);
-    if (p.philox) {
-        if (p.stamp)
-            hipLaunchKernelGGL((c4_search_kernel<true, true>), grid, block, lds, s, p);
-        else
-            hipLaunchKernelGGL((c4_search_kernel<false, true>), grid, block, lds, s, p);
-    } else {
-        if (p.stamp)
-            hipLaunchKernelGGL((c4_search_kernel<true, false>), grid, block, lds, s, p);
-        else
-            hipLaunchKernelGGL((c4_search_kernel<false, false>), grid, block, lds, s, p);
-    }
+    const SearchKernel k = p.philox ? (p.stamp ? c4_search_instance<true, true>(p.bs) : c4_search_instance<false, true>(p.bs))
+                                    : (p.stamp ? c4_search_instance<true, false>(p.bs) : c4_search_instance<false, false>(p.bs));
+    hipLaunchKernelGGL(k, grid, block, lds, s, p);
 }
 
 void launch_c4_walk(const SearchParams &p, int mode, hipStream_t s) {
     const int wpg = c4_search_wpg(p.bs);
     const size_t lds = c4_search_lds_bytes(p.bs);
     const dim3 grid((p.n_games + wpg - 1) / wpg), block(wpg * kBlock);
-    if (mode == 1)
-        hipLaunchKernelGGL((c4_walk_kernel<1>), grid, block, lds, s, p);
-    else
-        hipLaunchKernelGGL((c4_walk_kernel<2>), grid, block, lds, s, p);
+    const SearchKernel k = mode == 1 ? (p.bs < 64 ? c4_walk_kernel<1, true> : c4_walk_kernel<1, false>)
+                                     : (p.bs < 64 ? c4_walk_kernel<2, true> : c4_walk_kernel<2, false>);
+    hipLaunchKernelGGL(k, grid, block, lds, s, p);
 }
 
+// A free run without a progress counter has no instance: every entry point that launches one
+// sets it (zc_c4_selfplay_async).
 void launch_c4_selfplay(const SearchParams &p, hipStream_t s) {
     const int wpg = c4_search_wpg(p.bs);
     const size_t lds = c4_search_lds_bytes(p.bs);
     const dim3 grid((p.n_games + wpg - 1) / wpg), block(wpg * kBlock);
-    if (p.philox)
-        hipLaunchKernelGGL((c4_selfplay_kernel<true>), grid, block, lds, s, p);
-    else
-        hipLaunchKernelGGL((c4_selfplay_kernel<false>), grid, block, lds, s, p);
+    hipLaunchKernelGGL(c4_selfplay_instance(p.bs, p.philox, c4_selfplay_mode_of(p)), grid, block, lds, s, p);
 }
 
+// What a pooled launch keeps resident, whichever of the two pooled instances runs it: the
+// smaller of their occupancies (both are bounded by __launch_bounds__ and the same LDS).
 int c4_selfplay_resident_games(int bs, int philox, int *out) {
     const int wpg = c4_search_wpg(bs);
     int blocks = 0, dev = 0, cus = 0;
-    const void *fn = philox ? (const void *)c4_selfplay_kernel<true> : (const void *)c4_selfplay_kernel<false>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, wpg * kBlock, c4_search_lds_bytes(bs)) != hipSuccess)
-        return -1;
+    for (const int mode : {kModePooled, kModeCarry}) {
+        int b = 0;
+        const void *fn = (const void *)c4_selfplay_instance(bs, philox, mode);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, fn, wpg * kBlock, c4_search_lds_bytes(bs)) != hipSuccess)
+            return -1;
+        blocks = mode == kModePooled || b < blocks ? b : blocks;
+    }
     if (hipGetDevice(&dev) != hipSuccess) return -1;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -1;
     *out = blocks * cus * wpg;
