@@ -116,7 +116,15 @@ int zc_c4_search_async(zc_engine *eng, int32_t first_game, int32_t n_games, cons
  * zc_traj_record_async for that step, which the caller replays in step order.
  * d_stats[i] sums the moves' counters (reserved = games finished).  Results equal `moves`
  * rounds of zc_c4_search_async + zc_c4_play_async; games never wait for each other, so a
- * launch no longer waits once per move for its slowest game. */
+ * launch no longer waits once per move for its slowest game.
+ * A root that is no searchable position (validated on the device before every move, as
+ * zc_c4_search_async does) stops its game there: d_stats[i].status = ZC_STATUS_BAD_STATE, or
+ * ZC_STATUS_NO_MOVES for a valid full board; the game's remaining step rows are ZC_SLOT_SKIP
+ * with move -1, its d_roots row, tree and MT19937 stream are left as they are, a move carried
+ * over for it is dropped, and the other games of the launch are untouched.  The same holds for
+ * the pooled and carry launches below, where the root is examined once the game holds a
+ * ticket (or resumes): a flagged game spends one ticket per launch, and a game that gets
+ * none is not examined (status 0, skip rows only). */
 int zc_c4_selfplay_async(zc_engine *eng, int32_t first_game, int32_t n_games, zc_c4_state *d_roots, int32_t sims,
                          double c, int32_t batch_size, int32_t moves, zc_c4_state *d_out_states,
                          int16_t *d_out_moves, int32_t *d_out_results, zc_game_stats *d_stats, void *hip_stream);
@@ -142,10 +150,22 @@ int zc_c4_selfplay_pooled_async(zc_engine *eng, int32_t first_game, int32_t n_ga
 
 /* zc_c4_selfplay_pooled_async whose in-flight moves CARRY OVER instead of finishing: once the
  * budget is spent (d_ticket[0] reached it), every game's search stops at its next flush boundary
- * (batch_size simulations), and its progress — simulations done, tree nodes, and the tree, the
- * MT19937 stream and the root, which stay in the engine's HBM arena — is kept for the game's
+ * (batch_size simulations), and its progress — simulations done, tree nodes, and the tree and
+ * the MT19937 stream, which stay in the engine's HBM arena — is kept for the game's
  * next self-play launch (this one, zc_c4_selfplay_pooled_async or zc_c4_selfplay_async), which
- * resumes that move first, without a ticket.  The launch's tail — games finishing moves
+ * resumes that move first, without a ticket.  The ROOT is not kept: the resuming launch reads it
+ * again from its own d_roots row.  So a launch that resumes must bring the suspending launch's
+ * buffer with the same game in each row (the same d_roots - first_game, rows untouched in
+ * between) and its sims, c, batch_size and rollout mode and seed.  While moves are carried
+ * over, a self-play launch over any of those games with another value of one of these, a carry
+ * launch with another value over ANY games (the engine keeps one record), and
+ * zc_c4_set_rollout_mode are refused with ZC_EINVAL before anything is enqueued; the message
+ * names the parameter.  Otherwise the move would be finished under other parameters, or the
+ * kept tree grafted onto another game's position, and the guarantee below would break without
+ * a sign.  What the rows HOLD is not checked (that needs the device): a caller that rewrites a
+ * carried game's row gets the kept tree searched on from the new position, unless the new
+ * row is no searchable position — then the game is flagged as described at
+ * zc_c4_selfplay_async and its carried move dropped.  The launch's tail — games finishing moves
  * started just before the budget ran out, on an emptying device — moves into the next launch,
  * where it runs at full occupancy.  Each game's k-th finished move is still exactly the k-th
  * move of zc_c4_selfplay_async (the search is cut only between flushes, and resumed with the
@@ -195,7 +215,9 @@ int zc_c4_pooled_max_games(zc_engine *eng, int32_t batch_size, int32_t *out);
  *     simulation index, game's MT position at the search's start, game, 0x0C4F0A57), key =
  *     seed), so a flush's leaves roll out in parallel.  Expansion draws still come from the
  *     game's MT stream.  Statistical parity with the reference only (same distribution of
- *     playouts, different numbers); specification: tests/c4_philox_ref.py. */
+ *     playouts, different numbers); specification: tests/c4_philox_ref.py.
+ * Refused (ZC_EINVAL) while self-play moves are carried over (zc_c4_selfplay_carry_async): a
+ * suspended search would change its generator mid-move. */
 #define ZC_ROLLOUT_EXACT 0
 #define ZC_ROLLOUT_PHILOX 1
 int zc_c4_set_rollout_mode(zc_engine *eng, int32_t mode, uint64_t seed);
@@ -223,6 +245,10 @@ int zc_c4_play_async(zc_engine *eng, int32_t n_games, zc_c4_state *d_states, con
  * ZC_STATUS_CAPACITY (chess): the child-slot pool ran out, or a walk stood on an expanded,
  * non-terminal node at level 62 (root = level 0): the deepest node a chess tree holds is at
  * level 62, and a search that has to go below it ends without a move. */
+/* Counters of a flagged game (the Connect4 searches and both PUCT searches): a root refused when
+ * the search begins (NO_MOVES, BAD_STATE) reports every counter 0, leaves included: nothing ran.
+ * The plain chess searches still report leaves = sims there.  A search stopped part-way (INTERNAL, or
+ * CAPACITY) reports in `leaves` the simulations it was asked for, not the ones it finished. */
 #define ZC_STATUS_INTERNAL 3
 #define ZC_STATUS_CAPACITY 4
 

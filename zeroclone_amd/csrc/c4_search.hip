@@ -1422,7 +1422,7 @@ __global__ __launch_bounds__(kSearchWaves * kBlock, 4) void c4_selfplay_kernel(S
         uint64_t s0 = uni64(root.stones[0]), s1 = uni64(root.stones[1]);
         int turn = uni(root.turn);
         if (!valid_state(s0, s1, turn) || legal_mask(s0 | s1) == 0) {  // never from play: flagged
-            status = ZC_STATUS_BAD_STATE;
+            status = valid_state(s0, s1, turn) ? ZC_STATUS_NO_MOVES : ZC_STATUS_BAD_STATE;
             break;
         }
         int done = resume ? (int)cy.x : 0, nnodes = resume ? (int)cy.y : 1;
@@ -1493,6 +1493,11 @@ __global__ __launch_bounds__(kSearchWaves * kBlock, 4) void c4_selfplay_kernel(S
         st.rng_words = rng.use();
         st.reserved = finished;
         p.out_stats[gl] = st;
+        // a bad root (the only source of these two codes) under a carried move: the move
+        // belonged to the root that stood there, so it is dropped and the game's next search
+        // starts afresh (the host's guarded range is already lifted)
+        if (resume && (status == ZC_STATUS_BAD_STATE || status == ZC_STATUS_NO_MOVES))
+            a.carry[g] = make_uint4(0u, 0u, 0u, 0u);
     }
     lrng_close(rng, a.ring + (size_t)g * kRingWords, use0, a.rngpos + 2 * (size_t)g);
 }

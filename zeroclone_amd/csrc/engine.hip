@@ -232,6 +232,40 @@ void carry_covered(zc_engine *e, int32_t first, int32_t n) {  // a launch that l
     if (first <= e->carry_lo && first + n >= e->carry_hi) e->carry_lo = e->carry_hi = 0;
 }
 
+const zc_c4_state *roots_base(const zc_c4_state *d_roots, int32_t first) {  // game 0's row, never dereferenced
+    return (const zc_c4_state *)((uintptr_t)d_roots - (uintptr_t)first * sizeof(zc_c4_state));
+}
+
+// A self-play launch while moves are carried over: the kernel resumes {simulations done, nodes,
+// Philox tag} under THIS launch's parameters and re-reads the root from THIS launch's d_roots,
+// so a launch that overlaps the carried games must bring what the suspending launch had (another
+// sims / batch_size / c finishes the move as no uninterrupted search would; other root rows graft
+// the kept tree onto another position).  The rollout mode and seed cannot differ: their setter
+// refuses while moves are carried (zc_c4_set_rollout_mode).  A carry launch is checked even where it
+// does not overlap: the engine keeps one record for the whole range.  Refused before anything is
+// enqueued.
+int check_resume(const zc_engine *e, int32_t first, int32_t n, const zc_c4_state *d_roots, int32_t sims, double c,
+                 int32_t bs, int carry) {
+    if (e->carry_hi <= e->carry_lo || n <= 0) return ZC_OK;
+    if (!carry && !(first < e->carry_hi && first + n > e->carry_lo)) return ZC_OK;
+    const zc_engine::CarrySearch &k = e->carried;
+    const char *const tail = "finish the carried moves with the suspending launch's parameters and root buffer, or "
+                             "drop them with zc_c4_carry_discard";
+    if (sims != k.sims)
+        return fail(ZC_EINVAL, "sims %d differs from the %d of the self-play moves carried over games [%d, %d): %s",
+                    sims, k.sims, e->carry_lo, e->carry_hi, tail);
+    if (bs != k.bs)
+        return fail(ZC_EINVAL, "batch_size %d differs from the %d of the self-play moves carried over games "
+                    "[%d, %d): %s", bs, k.bs, e->carry_lo, e->carry_hi, tail);
+    if (c != k.c)
+        return fail(ZC_EINVAL, "c %.17g differs from the %.17g of the self-play moves carried over games [%d, %d): %s",
+                    c, k.c, e->carry_lo, e->carry_hi, tail);
+    if (roots_base(d_roots, first) != k.roots0)
+        return fail(ZC_EINVAL, "d_roots / first_game: game %d's root row is not the row the suspending launch gave "
+                    "it (moves carried over games [%d, %d)): %s", first, e->carry_lo, e->carry_hi, tail);
+    return ZC_OK;
+}
+
 bool valid_c4(const zc_c4_state &s) {
     const uint64_t full = 0x0000040810204081ull * 0x3Full;
     if ((s.stones[0] & s.stones[1]) || ((s.stones[0] | s.stones[1]) & ~full) || (s.turn & ~1)) return false;
@@ -507,6 +541,7 @@ int zc_c4_selfplay_async(zc_engine *eng, int32_t first, int32_t n, zc_c4_state *
     if (moves < 1) return fail(ZC_EINVAL, "moves must be >= 1 (got %d)", moves);
     if (!n) return ZC_OK;
     std::lock_guard<std::mutex> lk(eng->mu);
+    if (int r = check_resume(eng, first, n, d_roots, sims, c, bs, 0)) return r;
     if (int r = check_visits_cap("zc_c4_selfplay_visits", eng->c4_visits, eng->c4_visits_cap, moves)) return r;
     ZC_HIP(hipSetDevice(eng->cfg.device));
     zc::SearchParams p = make_params(eng, first, n, d_roots, sims, c, bs, nullptr, eng->c4_visits, d_stats);
@@ -537,6 +572,7 @@ int c4_pooled(zc_engine *eng, int32_t first, int32_t n, zc_c4_state *d_roots, in
         return fail(ZC_EINVAL, "budget %lld outside [0, moves_cap x n_games] or >= 2^31", (long long)budget);
     if (!n) return ZC_OK;
     std::lock_guard<std::mutex> lk(eng->mu);
+    if (int r = check_resume(eng, first, n, d_roots, sims, c, bs, carry)) return r;
     if (int r = check_visits_cap("zc_c4_selfplay_visits", eng->c4_visits, eng->c4_visits_cap, moves_cap)) return r;
     ZC_HIP(hipSetDevice(eng->cfg.device));
     // A wave takes its tickets only once resident: with more games than the chip holds at
@@ -569,7 +605,8 @@ int c4_pooled(zc_engine *eng, int32_t first, int32_t n, zc_c4_state *d_roots, in
     } else if (eng->carry_hi <= eng->carry_lo) {
         eng->carry_lo = first;
         eng->carry_hi = first + n;
-    } else {
+        eng->carried = {sims, bs, c, roots_base(d_roots, first)};
+    } else {  // same parameters and root rows (check_resume): the one record holds
         eng->carry_lo = std::min(eng->carry_lo, first);
         eng->carry_hi = std::max(eng->carry_hi, first + n);
     }
@@ -689,6 +726,10 @@ int zc_c4_set_rollout_mode(zc_engine *eng, int32_t mode, uint64_t seed) {
     if (!eng) return fail(ZC_EINVAL, "null argument");
     if (mode != ZC_ROLLOUT_EXACT && mode != ZC_ROLLOUT_PHILOX) return fail(ZC_EINVAL, "unknown rollout mode %d", mode);
     std::lock_guard<std::mutex> lk(eng->mu);
+    if (eng->carry_hi > eng->carry_lo)
+        return fail(ZC_EINVAL, "the rollout mode cannot change while self-play moves are carried over games [%d, %d) "
+                    "(zc_c4_selfplay_carry_async): their searches would change generator mid-move; finish or "
+                    "discard them first", eng->carry_lo, eng->carry_hi);
     eng->rollout_mode = mode;
     eng->rollout_seed = seed;
     return ZC_OK;

@@ -141,7 +141,10 @@ __device__ __forceinline__ void search_done(const Params &p, int32_t *ctl, int g
     st.status = status;
     st.expansions = ctl[W::exp];
     st.depth_sum = ctl[W::depth];
-    st.leaves = ctl[W::reused] ? p.sims - 1 : p.sims;
+    // a root flagged at begin (the only source of these two codes) evaluated no leaf; a search
+    // stopped part-way (INTERNAL, CAPACITY) reports the simulations it was asked for
+    const bool never_ran = status == ZC_STATUS_NO_MOVES || status == ZC_STATUS_BAD_STATE;
+    st.leaves = never_ran ? 0 : ctl[W::reused] ? p.sims - 1 : p.sims;
     p.out_stats[gl] = st;
     ctl[W::done] = status == 0 ? 1 : 0;
 }

@@ -480,6 +480,14 @@ struct zc_engine {
     int rollout_mode = 0;        // ZC_ROLLOUT_EXACT / ZC_ROLLOUT_PHILOX
     uint64_t rollout_seed = 0;
     int carry_lo = 0, carry_hi = 0;  // games that may hold a carried self-play move (engine.hip check_carry)
+    // The suspended searches of [carry_lo, carry_hi), as the carry launch gave them: a launch that
+    // resumes them must bring the same (engine.hip check_resume).  roots0 = the address of game
+    // 0's root row, d_roots - first_game.
+    struct CarrySearch {
+        int32_t sims = 0, bs = 0;
+        double c = 0;
+        const zc_c4_state *roots0 = nullptr;
+    } carried;
     zc::ChessArena ca;  // allocated on the first chess search
     zc::C4PuctArena c4p;  // allocated on the first zc_c4_puct_begin
     // A stepwise search in progress (begin .. end), as its begin call gave it: the entry points'
