@@ -182,16 +182,15 @@ def _integer_net(c, blocks, seed, density=0.002):
     return net
 
 
-@pytest.mark.parametrize("mf", ["32", "16", "16e"])
+@pytest.mark.parametrize("mf", ["32", "16"])
 @pytest.mark.parametrize("shape", [(17, 8, 8), (2, 6, 7)])
 def test_tower_forms_exact_on_integers(mf, shape, net_sw):
-    """Both MFMA forms of the fused tower ("tower_mf": 32x32x16, 16x16x32; "16e": the
-    16x16x32 form with the swap epilogue, "tower_epi" 1) on an integer network, 2 residual
-    blocks, ragged board counts: equal to float64 exactly."""
+    """Both MFMA forms of the fused tower ("tower_mf": 32x32x16, 16x16x32) on an integer
+    network, 2 residual blocks, ragged board counts: equal to float64 exactly."""
     _tower_forms_exact(mf, shape, net_sw, blocks=2)
 
 
-@pytest.mark.parametrize("mf", ["32", "16", "16e"])
+@pytest.mark.parametrize("mf", ["32", "16"])
 @pytest.mark.parametrize("shape", [(17, 8, 8), (2, 6, 7)])
 def test_tower_forms_exact_on_integers_without_blocks(mf, shape, net_sw):
     """The same on a network without residual blocks: the stem alone (nconv = 1), the one layer
@@ -201,10 +200,9 @@ def test_tower_forms_exact_on_integers_without_blocks(mf, shape, net_sw):
 
 def _tower_forms_exact(mf, shape, net_sw, blocks):
     from zeroclone_amd.nets import FoldedValueNetwork, MfmaValueNetwork
-    net_sw("tower_mf", int(mf[:2]))
-    net_sw("tower_epi", 1 if mf.endswith("e") else 0)
+    net_sw("tower_mf", int(mf))
     c, h, w = shape
-    vnet = _integer_net(c, blocks, seed=h * 10 + int(mf[:2]))
+    vnet = _integer_net(c, blocks, seed=h * 10 + int(mf))
     net = MfmaValueNetwork(vnet)
     assert len(net.w) == len(net.wp) == 1 + 2 * blocks and net.ball.shape == (1 + 2 * blocks, 128)
     assert net.wall.numel() == 9 * 128 * 32 + 2 * blocks * 9 * 128 * 128   # 0 blocks: the stem's weights alone
@@ -314,6 +312,44 @@ def _value_head_exact(mf, shape, net_sw, blocks):
         got = net(x.cuda()).clone()
         torch.cuda.synchronize()
         np.testing.assert_allclose(got.cpu().numpy(), np.tanh(pre.numpy()), rtol=0, atol=1e-6)
+
+
+def test_network_switches_refuse_unknown_names_and_head_raw_reaches_both_widths(net_sw):
+    """zc_debug_net_switch knows "tower_mf" and "head_raw" only: a retired name ("tower_epi") and
+    a value outside a switch's set are refused and change nothing.  "head_raw" is one value for
+    both widths: on one 6x7 board with an integer head (as _integer_head: activations 0..4,
+    Linear weights k_c * 42 / 64 with k_c in {0, 1}, a bias that is a multiple of 1/64) the 64-
+    and the 128-channel value head both return the pre-tanh sum sum_c k_c S_c / 64 + bias
+    exactly — past 1, so no tanh — and, with the switch back at 0, its tanh."""
+    from zeroclone_amd import _native
+    L = _native.lib()
+    before = {name: _native.net_switch(name, 0) for name in ("tower_mf", "head_raw")}
+    for name, old in before.items():
+        _native.net_switch(name, old)
+    with pytest.raises(ValueError):
+        _native.net_switch("tower_epi", 0)
+    with pytest.raises(ValueError):
+        _native.net_switch("tower_mf", 7)
+    assert {name: _native.net_switch(name, old) for name, old in before.items()} == before   # nothing moved
+    hw, fcb = 42, -3.0 + 5.0 / 64.0
+    cases = []
+    for ch in (64, 128):
+        g = torch.Generator().manual_seed(ch)
+        act = torch.randint(0, 5, (1, hw, ch), generator=g).half()
+        k = (torch.rand(ch, generator=g) < 0.25).float()
+        pre = (act.double().sum(dim=1) @ k.double()) / 64.0 + fcb
+        assert pre.item() > 1.0
+        cases.append((ch, act.cuda(), (k * hw / 64.0).cuda(), pre))
+    for raw in (1, 0):
+        net_sw("head_raw", raw)
+        for ch, act, fcw, pre in cases:
+            vals = torch.full((1,), 7.0, dtype=torch.float64, device="cuda")
+            _native.check(L.zc_net_value_head_w_async(ch, 1, hw, act.data_ptr(), fcw.data_ptr(), fcb, vals.data_ptr(), None))
+            torch.cuda.synchronize()
+            if raw:
+                assert torch.equal(vals.cpu(), pre), (ch, vals.item(), pre.item())
+            else:
+                np.testing.assert_allclose(vals.cpu().numpy(), np.tanh(pre.numpy()), rtol=0, atol=1e-6)
 
 
 def _integer_pv_net(c, h, w, nl, seed, head="linear"):

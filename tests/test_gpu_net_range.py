@@ -192,7 +192,7 @@ def interval_check(tag):
     return check
 
 
-FUSED_FORMS = [(32, 0), (16, 0), (16, 1), (0, 0)]   # (tower_mf, tower_epi); (0, 0) the default pairing
+FUSED_FORMS = [32, 16, 0]   # tower_mf; 0 the default pairing
 
 
 @pytest.mark.parametrize("board", BOARDS, ids=["8x8", "6x7"])
@@ -213,13 +213,11 @@ def test_wide_range_tower_layer_by_layer_and_fused(board, net_sw):
         assert want.max().item() >= (1e3 if n == 131 else 1.0)
         net_sw("tower_mf", 16)
         assert same_bits(layered(mnet, x0), want), (board, n, "layered, 16x16x32")
-        for mf, epi in FUSED_FORMS:
+        for mf in FUSED_FORMS:
             net_sw("tower_mf", mf)
-            net_sw("tower_epi", epi)
             a, _ = mnet.tower(xs.cuda(), fused=True)
             torch.cuda.synchronize()
-            assert same_bits(a.cpu().reshape(want.shape), want), (board, n, mf, epi)
-        net_sw("tower_epi", 0)
+            assert same_bits(a.cpu().reshape(want.shape), want), (board, n, mf)
 
 
 # ---- the value head ---------------------------------------------------------------------------
@@ -413,18 +411,16 @@ def test_non_finite_inputs_reach_every_output(board, net_sw):
     fcw = mnet.fcw.cpu()
     d, _ = nc.value_head_reference(want.reshape(NB, h * w, 128), fcw, mnet.fcb)
     assert torch.isnan(d[list(POISON)]).all() and torch.isfinite(clean_rows(d)).all()
-    for mf, epi in FUSED_FORMS:
+    for mf in FUSED_FORMS:
         net_sw("tower_mf", mf)
-        net_sw("tower_epi", epi)
         a, vals = mnet.tower(bad.cuda(), head=True)
         got_a, got_v = a.cpu().clone().reshape(want.shape), vals.cpu().clone()
-        assert same_bits(got_a, want), (board, mf, epi)
-        assert torch.equal(torch.isnan(got_v), torch.isnan(d)), (board, mf, epi, got_v.tolist())
+        assert same_bits(got_a, want), (board, mf)
+        assert torch.equal(torch.isnan(got_v), torch.isnan(d)), (board, mf, got_v.tolist())
         assert same_bits(mnet(bad.cuda()).cpu(), got_v) and same_bits(mnet(bad.cuda(), fused=False).cpu(), got_v)
         a, vals = mnet.tower(x.cuda(), head=True)
         assert same_bits(clean_rows(a.cpu().reshape(want.shape)), clean_rows(want))
         assert same_bits(clean_rows(vals.cpu()), clean_rows(got_v))
-    net_sw("tower_epi", 0)
 
 
 @pytest.mark.parametrize("case", [(17, 8, 8, "linear"), (2, 6, 7, "linear"), (17, 8, 8, "conv")],
@@ -505,9 +501,8 @@ def test_counted_launches_with_no_rows_to_evaluate(board, count, net_sw):
     cnt = torch.tensor([count], dtype=torch.int32, device="cuda")
     assert int(cnt.item()) == count
     pout = torch.empty((NB, h * w, 32), dtype=torch.float16, device="cuda")
-    for mf, epi in FUSED_FORMS:
+    for mf in FUSED_FORMS:
         net_sw("tower_mf", mf)
-        net_sw("tower_epi", epi)
         a, vals = tower.tower(xg, head=True)
         tower.tower_policy(xg, mnet.pw, mnet.pb, pout)
         assert a.abs().sum().item() > 0 and pout.abs().sum().item() > 0 and (vals != -3.0).all()   # the plain launches write
@@ -516,12 +511,11 @@ def test_counted_launches_with_no_rows_to_evaluate(board, count, net_sw):
         a2, v2 = tower.tower(xg, head=True, count=cnt)
         torch.cuda.synchronize()
         assert a2.data_ptr() == a.data_ptr() and v2.data_ptr() == vals.data_ptr()
-        assert (a2 == -3.0).all() and (v2 == -3.0).all(), (board, count, mf, epi)
+        assert (a2 == -3.0).all() and (v2 == -3.0).all(), (board, count, mf)
         pout.fill_(-3.0)
         v3 = tower.tower_policy(xg, mnet.pw, mnet.pb, pout, count=cnt)
         torch.cuda.synchronize()
-        assert (pout == -3.0).all() and (v3 == -3.0).all(), (board, count, mf, epi)
-    net_sw("tower_epi", 0)
+        assert (pout == -3.0).all() and (v3 == -3.0).all(), (board, count, mf)
 
 
 @pytest.mark.parametrize("what", ["bias", "weight"])
@@ -551,16 +545,14 @@ def test_nan_parameter_reaches_every_output(board, what, net_sw):
     net_sw("tower_mf", 32)
     want = layered(mnet.tower, nhwc32(x).cuda(), check, staged=True)
     assert torch.isnan(want).any(dim=(1, 2, 3)).all()
-    for mf, epi in FUSED_FORMS:
+    for mf in FUSED_FORMS:
         net_sw("tower_mf", mf)
-        net_sw("tower_epi", epi)
         a, vals = mnet.tower.tower(x.cuda(), head=True)
-        assert same_bits(a.cpu().reshape(want.shape), want), (board, what, mf, epi)
+        assert same_bits(a.cpu().reshape(want.shape), want), (board, what, mf)
         assert torch.isnan(vals).all()
         v, logits = mnet(x.cuda())
         assert torch.isnan(v).all() and torch.isnan(mnet._pout[(5, h * w)]).any(dim=(1, 2)).all()
         assert torch.isnan(logits).any(dim=1).all()
-    net_sw("tower_epi", 0)
 
 
 def test_pool_with_a_nan_bias_stops_every_game():

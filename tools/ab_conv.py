@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""A/B of the conv3x3 implementations (ZC_CONV_IMPL = tile / half; stream2 / stream3 = the packed-weight
-form at 2 / 3 waves per SIMD; argv picks them):
-bit-identical outputs and per-layer time.  Runs each impl in a child process."""
+"""A/B of the conv3x3 entry points (half = the staged form, zc_net_conv3x3_async; stream3 = the
+packed-weight form, zc_net_conv3x3_packed_async; argv picks them): bit-identical outputs and
+per-layer time.  Runs each in a child process."""
 import json
 import os
 import subprocess
@@ -45,13 +45,12 @@ for (h, w, n) in [(8, 8, 32768), (6, 7, 131072), (8, 8, 1000), (6, 7, 777)]:
                         "hash": int((o.view(torch.int16).to(torch.int64) * torch.arange(o.numel(), device="cuda").view(o.shape) % 1000003).sum().item())}
 print(json.dumps(out))
 '''
-IMPLS = sys.argv[1:] or ["tile", "half"]
+IMPLS = sys.argv[1:] or ["half", "stream3"]
 res = {}
 for impl in IMPLS:
-    if impl.startswith("stream"):  # packed weights: stream2 / stream3 = waves per SIMD
-        env = dict(os.environ, ZC_AB_PACKED="1", ZC_CONV_WPE=impl[-1])
-    else:
-        env = dict(os.environ, ZC_CONV_IMPL=impl)
+    if impl not in ("half", "stream3"):
+        sys.exit(f"unknown form {impl!r} (half, stream3)")
+    env = dict(os.environ, ZC_AB_PACKED="1" if impl == "stream3" else "0")
     r = subprocess.run([sys.executable, "-c", CHILD, HERE], env=env, capture_output=True, text=True, timeout=600)
     if r.returncode:
         print(r.stderr[-3000:])

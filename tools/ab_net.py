@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Whole-network A/B of conv variants: the value tower (ValueNetwork(128, 8), MFMA path) on
 the chess C4 batch (32768 boards 8x8, 17 planes) and the Connect4 C2(iii) batch (131072
-boards 6x7, 2 planes).  Each variant "lib[:wpe]" runs in its own process (ZC_LIB, ZC_CONV_WPE),
-in turn over rounds; prints median ms per forward and whether the values are identical.
+boards 6x7, 2 planes).  Each variant library runs in its own process (ZC_LIB), in turn over
+rounds; prints median ms per forward and whether the values are identical.
 
-    python tools/ab_net.py lib_head.so:3 libzeroclone_amd.so:3 libzeroclone_amd.so:4"""
+    python tools/ab_net.py lib_head.so libzeroclone_amd.so"""
 import os
 import statistics
 import subprocess
@@ -38,8 +38,7 @@ def main():
     res = {v: [] for v in variants}
     for rnd in range(int(os.environ.get("AB_ROUNDS", "3"))):
         for v in variants:
-            lib, _, wpe = v.partition(":")
-            env = dict(os.environ, ZC_LIB=os.path.join(ROOT, "zeroclone_amd", lib), ZC_CONV_WPE=wpe or "3")
+            env = dict(os.environ, ZC_LIB=os.path.join(ROOT, "zeroclone_amd", v))
             o = subprocess.run([sys.executable, "-c", CHILD % ROOT], env=env, check=True, capture_output=True,
                                text=True, timeout=300).stdout.strip().splitlines()[-1].split()
             res[v].append(o)

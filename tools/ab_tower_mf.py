@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The fused tower's two MFMA forms, alternating in one process (ZC_TOWER_MF is read per
-launch): the 32x32x16 form (default) and the 16x16x32 form, on the chess C4 batch (32768
+"""The fused tower's two MFMA forms, alternating in one process (the "tower_mf" switch, set
+between launches): the 32x32x16 form and the 16x16x32 form (the default), on the chess C4 batch (32768
 boards 8x8, 17 planes) and the Connect4 C2(iii) batch (131072 boards 6x7, 2 planes).  Prints
 ms per tower, TFLOP/s, and each form's error against a torch fp32 reference of the same folded
 network on the same fp16 input (max abs over the output activation), plus max |MF16 - MF32|."""
@@ -30,12 +30,11 @@ def main():
         net = MfmaValueNetwork(vnet, "cuda")
         g = torch.Generator(device="cuda").manual_seed(1)
         x = (torch.rand(n, planes, h, w, device="cuda", generator=g) < 0.3).half()
-        res = {"32": [], "16": [], "16e": []}
+        res = {"32": [], "16": []}
         outs = {}
         for _ in range(rounds):
-            for mf in ("32", "16", "16e"):
-                _native.net_switch("tower_mf", int(mf[:2]))
-                _native.net_switch("tower_epi", 1 if mf.endswith("e") else 0)
+            for mf in ("32", "16"):
+                _native.net_switch("tower_mf", int(mf))
                 a, _ = net.tower(x)
                 torch.cuda.synchronize()
                 outs[mf] = a.clone()
@@ -53,7 +52,6 @@ def main():
             torch.cuda.synchronize()
             same[mf] = bool(torch.equal(outs[mf], layered))
         _native.net_switch("tower_mf", 0)
-        _native.net_switch("tower_epi", 0)
         # torch fp32 reference on 2048 boards (the folded network, NHWC-compared)
         k = 2048
         f = FoldedValueNetwork(vnet).float().cuda()
@@ -66,9 +64,6 @@ def main():
             "mf32_ms": statistics.median(res["32"]), "mf16_ms": statistics.median(res["16"]),
             "mf32_tflops": round(flop / statistics.median(res["32"]) / 1e9, 1),
             "mf16_tflops": round(flop / statistics.median(res["16"]) / 1e9, 1),
-            "mf16e_ms": statistics.median(res["16e"]),
-            "mf16e_tflops": round(flop / statistics.median(res["16e"]) / 1e9, 1),
-            "mf16e_equals_mf16": bool(torch.equal(outs["16e"], outs["16"])),
             "all_ms": res,
             "fused_equals_layered": same,
             "max_abs_mf16_vs_mf32": float((outs["16"].float() - outs["32"].float()).abs().max()),

@@ -16,7 +16,7 @@ x = torch.randn(n, h, w, cin, device="cuda").half()
 wt = (torch.randn(9, 128, cin, device="cuda") * 0.05).half()
 bias = torch.zeros(128, device="cuda")
 o = torch.empty(n, h, w, 128, device="cuda", dtype=torch.float16)
-packed = os.environ.get("ZC_AB_PACKED") == "1"  # the streamed-weight form (ZC_CONV_WPE picks 2 / 3)
+packed = os.environ.get("ZC_AB_PACKED") == "1"  # the streamed-weight form
 if packed:
     wp = torch.empty_like(wt)
     _native.check(L.zc_net_conv3x3_pack_async(cin, wt.data_ptr(), wp.data_ptr(), None))

@@ -76,7 +76,7 @@ def main():
                                if tr else "mean of the counter passes' warm launches"),
            "trace_ms": [round(x, 4) for x in tr] if tr else None,
            "counter_pass_avg_ms": round(ms_pmc, 4),
-           "kernel": f"tower_kernel<8, 8, 2, 32, 4, 2, 1, {os.environ.get('ZC_TOWER_MF', '16')}> "
+           "kernel": f"tower_kernel<8, 8, 2, 32, 4, 2, {os.environ.get('ZC_TOWER_MF', '16')}> "
                      f"({'16x16x32' if os.environ.get('ZC_TOWER_MF', '16') == '16' else '32x32x16'} MFMA form)",
            "lib_sha256": lib_sha(), "flops_per_launch": FLOPS, "rocprof_avg_ms": round(ms, 4),
            "counter_launches_used": len(durs), "tflops": round(tf, 1),

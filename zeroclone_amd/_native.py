@@ -1237,8 +1237,9 @@ class NativeEngine:
 
 
 def net_switch(name: str, value: int) -> int:
-    """Set one of the network launches' A/B / test switches (zc_debug_net_switch: "tower_mf",
-    "tower_epi", "head_raw"); returns the previous value."""
+    """Set one of the network launches' switches (zc_debug_net_switch: "tower_mf", the MFMA form,
+    0, 16 or 32; "head_raw", 0 or 1, for both widths); returns the previous value.  Any other
+    name or value is refused."""
     old = ctypes.c_int32(0)
     check(lib().zc_debug_net_switch(name.encode(), int(value), ctypes.byref(old)))
     return old.value

@@ -2229,7 +2229,6 @@ int zc_debug_net_switch(const char *name, int32_t value, int32_t *old) {
     int prev = 0;
     if (!zc::net_switch(name, value, &prev))
         return fail(ZC_EINVAL, "zc_debug_net_switch: unknown switch or value (%s = %d)", name ? name : "(null)", value);
-    if (!strcmp(name, "head_raw")) zc::net64_set_head_raw(value);
     if (old) *old = prev;
     return ZC_OK;
 }

@@ -7,9 +7,12 @@
 // with M = 128 output channels, N = the pixels of a tile of boards, K = 9 taps x cin, on
 // v_mfma_f32_32x32x16_f16.  Activations are NHWC fp16 (a pixel's channels contiguous).
 //
-// Two forms (bit-identical results; tools/ab_conv.py): the default half-tile kernel below
-// (128-pixel tiles, 70 KB of LDS, two workgroups per CU) and this one (ZC_CONV_IMPL=tile).
-// One workgroup = 4 waves = one tile of BPW boards (<= 256 pixels; 4 chess boards, 6
+// The staged entry point (zc_net_conv3x3_async) has one kernel per input width, with
+// bit-identical results: the half-tile kernel below for the 128-plane layers (128-pixel
+// tiles, 70 KB of LDS, two workgroups per CU) and this tile kernel for the 32-plane stem,
+// which runs faster on 256-pixel tiles.  The packed entry point and the fused tower stream
+// their weights instead (conv3x3_stream_kernel, tower_kernel).  The tile kernel:
+// one workgroup = 4 waves = one tile of BPW boards (<= 256 pixels; 4 chess boards, 6
 // Connect4 boards).  The tile's input pixels are staged ONCE in LDS (rows padded by 16 B so
 // the 32 lanes reading 32 pixels hit different banks); the 9 shifted views of a tap are
 // just different LDS rows (zero outside the board), so no im2col ever touches HBM.  The
@@ -430,34 +433,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
-
-// ---- the swizzled activation layout (the 16x16x32 form, EPI = 3): unpadded 256-byte rows
-// (128 halfs, sixteen 16-byte chunks) whose chunk c sits at c ^ hsw(row).  hsw depends on
-// row & 7 only (so a zero row, 8 of them, stands for any row of its class) and was chosen
-// (an exhaustive search over the XOR-linear maps) so that every LDS access of the tower is
-// conflict-free on gfx950's banking (MI355X_MICROARCH §LDS):
-//   - the MFMA B operand (ds_read_b128, lane (pixel l & 15, k-chunk l >> 4), rows shifted by
-//     any tap offset): each lane group's 16 chunks land on 16 distinct bank quads;
-//   - the epilogue, in 8-consecutive-channel form (permlane16_swap, as tower_epilogue16_swap):
-//     the residual ds_read_b128 and the ds_write_b128 (8 aligned rows, one chunk) alike;
-//   - the value head's and the output copy's row reads, the input staging's stores.
-// Only the policy 1x1 conv's 32-pixel reads stay 2-way (once per tower).  The padded layout it
-// replaces (144-half rows) left the epilogue's ds_write_b64 4-way and its residual reads 2-way.
-constexpr int kSwzLD = kCout;
-__device__ __forceinline__ int hsw(int row) { return (int)((0xAE9D7340u >> ((row & 7) << 2)) & 15u); }
-__device__ __forceinline__ int swz(int row, int chunk) { return row * kSwzLD + ((chunk ^ hsw(row)) << 3); }
-template <int NT> constexpr size_t tower_lds_swz() { return (size_t)(64 * NT + 8) * kSwzLD * sizeof(_Float16); }
-
 // One layer's MFMA loop in the 16x16x32 form: each wave its 32 output channels (two 16-row
 // M tiles) x the tile's pixels as NN 16-pixel N tiles, k-steps of 32 channels.  Lane l takes
 // pixel l & 15 of each N tile and k-chunk q = l >> 4; the weight fragments come from the same
 // packed stream as tower_mfma's (lane l of M tile m reads the 8 halfs of fragment row
 // 16 m + (l & 15), k 8 q .. 8 q + 7: wa already holds the lane's offset), one tap ahead.
-#ifndef ZC_TOWER_DIAG
-#define ZC_TOWER_DIAG 0  // diagnostic builds (wrong outputs, timing only; tools/tower_diag_libs.sh): 1 = no weight
-                         // reloads, 2 = no B reloads, 4 = every layer reads layer 1's weights, 8 = every weight
-                         // load of a wave reads its first fragment (L1-resident)
-#endif
 template <int H, int W, int NN, int KC, int KCN, int LD, int ZERO, int ZR, int NA>
 __device__ __forceinline__ void tower_mfma16(const _Float16 *lds, int src, const _Float16 *wa, const _Float16 *wn,
                                              h8 (&a)[NA], int l16, const int (&pyx)[NN], int q,
@@ -484,82 +464,12 @@ __device__ __forceinline__ void tower_mfma16(const _Float16 *lds, int src, const
         if (tap + 1 < 9) rows(tap + 1, xbn);
 #pragma unroll
         for (int j = 0; j < J; ++j) {
-            if (ZC_TOWER_DIAG & 2) {
-#pragma unroll
-                for (int n = 0; n < NN; ++n) xn[n] = x[n];
-            } else if (j + 1 < J) {
+            if (j + 1 < J) {
 #pragma unroll
                 for (int n = 0; n < NN; ++n) xn[n] = *(const h8 *)(xb[n] + (j + 1) * 32);
             } else if (tap + 1 < 9) {
 #pragma unroll
                 for (int n = 0; n < NN; ++n) xn[n] = *(const h8 *)(xbn[n]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int n = 0; n < NN; ++n)
-#pragma unroll
-                for (int m = 0; m < 2; ++m)
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[2 * j + m], x[n], acc[m][n], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                if (ZC_TOWER_DIAG & 1) break;
-                if (ZC_TOWER_DIAG & 8) a[2 * j + m] = *(const h8 *)(wa + (size_t)(__builtin_amdgcn_readfirstlane(m * 0)));
-                else if (tap + 1 < 9) a[2 * j + m] = *(const h8 *)(wa + (size_t)((tap + 1) * KC + 2 * j) * 2048 + m * 128);
-                else if (JN == J && wn) a[2 * j + m] = *(const h8 *)(wn + (size_t)(2 * j) * 2048 + m * 128);
-            }
-#pragma unroll
-            for (int n = 0; n < NN; ++n) x[n] = xn[n];
-        }
-        if (tap + 1 < 9) {
-#pragma unroll
-            for (int n = 0; n < NN; ++n) xb[n] = xbn[n];
-        }
-    }
-    if (JN != J && wn && !(ZC_TOWER_DIAG & 1)) {
-#pragma unroll
-        for (int j = 0; j < JN; ++j)
-#pragma unroll
-            for (int m = 0; m < 2; ++m) a[2 * j + m] = *(const h8 *)(wn + (size_t)(2 * j) * 2048 + m * 128);
-    }
-}
-
-// tower_mfma16 on the swizzled layout: the same MFMAs in the same order; lane (pixel l16,
-// k-chunk q) of N tile n reads chunk 4 j + q of its row at (4 j + q) ^ hsw(row) — the row's
-// chunk offset for j = 0 XOR 64 j bytes (hsw of the tap-shifted row does not depend on n).
-template <int H, int W, int NN, int KC, int KCN, int ZERO, int NA>
-__device__ __forceinline__ void tower_mfma16_swz(const _Float16 *lds, int src, const _Float16 *wa, const _Float16 *wn,
-                                                 h8 (&a)[NA], int l16, const int (&pyx)[NN], int q,
-                                                 f4x (&acc)[2][NN]) {
-    constexpr int J = KC / 2, JN = KCN / 2;
-    auto rows = [&](int tap, int (&xo)[NN]) {
-        const int dy = tap / 3 - 1, dx = tap % 3 - 1;
-        const int qh = (q ^ hsw(l16 + dy * W + dx)) << 3;  // the same for every N tile (16 n = 0 mod 8)
-#pragma unroll
-        for (int n = 0; n < NN; ++n) {
-            const int sy = (pyx[n] >> 8) + dy, sx = (pyx[n] & 255) + dx;
-            const bool sv = (unsigned)sy < (unsigned)H && (unsigned)sx < (unsigned)W;
-            const int row = l16 + (n * 16 + dy * W + dx);
-            xo[n] = (sv ? src + row : ZERO + (row & 7)) * kSwzLD + qh;
-        }
-    };
-    int xo[NN];
-    rows(0, xo);
-    h8 x[NN], xn[NN];
-#pragma unroll
-    for (int n = 0; n < NN; ++n) x[n] = *(const h8 *)(lds + xo[n]);
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-        int xon[NN];
-        if (tap + 1 < 9) rows(tap + 1, xon);
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            if (j + 1 < J) {
-#pragma unroll
-                for (int n = 0; n < NN; ++n) xn[n] = *(const h8 *)(lds + (xo[n] ^ ((j + 1) * 32)));
-            } else if (tap + 1 < 9) {
-#pragma unroll
-                for (int n = 0; n < NN; ++n) xn[n] = *(const h8 *)(lds + xon[n]);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -578,7 +488,7 @@ __device__ __forceinline__ void tower_mfma16_swz(const _Float16 *lds, int src, c
         }
         if (tap + 1 < 9) {
 #pragma unroll
-            for (int n = 0; n < NN; ++n) xo[n] = xon[n];
+            for (int n = 0; n < NN; ++n) xb[n] = xbn[n];
         }
     }
     if (JN != J && wn) {
@@ -811,30 +721,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 // operations in the same order as the layer-by-layer packed form: bit-identical outputs
 // (tests/test_gpu_net.py).
 constexpr int kTowerLD = kCout + 8;
-// NT pixel MFMA tiles (32 pixels each) per wave; PG pixel groups of 4 waves per workgroup
-// (the 4 waves of a group split the 128 output channels; the groups split the pixels): buffer
-// rows TP = 32 NT PG.  With PG = 2 the two waves that own the same output channels load the
-// same weight fragments at about the same time, so the second load is served by the CU's
-// vector L1 instead of L2.
+// NT pixel MFMA tiles (32 pixels each) per wave (the 4 waves split the 128 output channels):
+// buffer rows TP = 32 NT.
 // MF = 16 (the 16x16x32 MFMA form, tower_mfma16): rows of 144 halfs (72 dwords: the operand's
 // four 16-byte k-chunks per pixel row land on distinct banks in every ds_read_b128 lane group)
 // and 8 zero rows (the bank class of a row is its index mod 8)
 template <int MF> constexpr int tower_ld() { return MF == 16 ? kCout + 16 : kTowerLD; }
 template <int MF> constexpr int tower_zr() { return MF == 16 ? 8 : 16; }
-template <int NT, int PG = 1> constexpr int tower_zero() { return 32 * NT * PG; }       // first zero row
-template <int NT, int PG = 1, int MF = 32> constexpr int tower_buf1() {                 // buf1's first row
-    return 32 * NT * PG + tower_zr<MF>();
+template <int NT> constexpr int tower_zero() { return 32 * NT; }                         // first zero row
+template <int NT, int MF> constexpr int tower_buf1() { return 32 * NT + tower_zr<MF>(); }  // buf1's first row
+template <int NT, int MF> constexpr size_t tower_lds() {
+    return (size_t)(64 * NT + tower_zr<MF>()) * tower_ld<MF>() * sizeof(_Float16);
 }
-template <int NT, int PG = 1, int MF = 32> constexpr size_t tower_lds() {
-    return (size_t)(64 * NT * PG + tower_zr<MF>()) * tower_ld<MF>() * sizeof(_Float16);
-}
-
+static_assert(tower_lds<4, 16>() == 76032, "264 rows of 144 halfs");
+static_assert(tower_lds<4, 32>() == 73984, "272 rows of 136 halfs");
 
 // One layer's MFMA loop: acc[t] += sum over taps and k of W * X (X from the LDS buffer at
 // row `src`).  a[0..KC) holds the layer's tap-0 fragments on entry; on exit it holds the
 // next layer's (KCN fragments from wn, when wn != nullptr and KCN == KC: in the ring at the
 // last tap; otherwise loaded after the loop).
-template <int H, int W, int NT, int KC, int KCN, int PG = 1>
+template <int H, int W, int NT, int KC, int KCN>
 __device__ __forceinline__ void tower_mfma(const _Float16 *lds, int src, const _Float16 *wa, const _Float16 *wn,
                                            h8 (&a)[8], const int (&prow)[NT], const int (&pyx)[NT], int hh,
                                            f16x (&acc)[NT]) {
@@ -846,7 +752,7 @@ __device__ __forceinline__ void tower_mfma(const _Float16 *lds, int src, const _
             const int sy = (pyx[t] >> 8) + dy, sx = (pyx[t] & 255) + dx;
             const bool sv = (unsigned)sy < (unsigned)H && (unsigned)sx < (unsigned)W;
             const int row = prow[t] + dy * W + dx;
-            xb[t] = lds + (sv ? src + row : tower_zero<NT, PG>() + (row & 15)) * kTowerLD + hh * 8;
+            xb[t] = lds + (sv ? src + row : tower_zero<NT>() + (row & 15)) * kTowerLD + hh * 8;
         }
     };
     const _Float16 *xb[NT];
@@ -892,10 +798,10 @@ __device__ __forceinline__ void tower_mfma(const _Float16 *lds, int src, const _
 // epilogue arithmetic, per lane: 4 channels x one pixel per store)
 template <int NT>
 __device__ __forceinline__ void tower_epilogue(_Float16 *dst, const float4 (&bv)[4], bool res, int npix, int wave,
-                                               int r, int hh, const f16x (&acc)[NT], int pbase = 0) {
+                                               int r, int hh, const f16x (&acc)[NT]) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-        const int P = pbase + t * 32 + r;
+        const int P = t * 32 + r;
         if (P >= npix) continue;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -916,37 +822,12 @@ __device__ __forceinline__ void tower_epilogue(_Float16 *dst, const float4 (&bv)
     }
 }
 
-// tower_epilogue for the 16x16x32 form: lane (pixel l & 15 of N tile n, q = l >> 4) holds
-// channels wave * 32 + 16 m + 4 q .. + 3; the same per-element arithmetic
-template <int NN>
-__device__ __forceinline__ void tower_epilogue16(_Float16 *dst, const float4 (&bv)[2], bool res, int npix, int wave,
-                                                 int l16, int q, const f4x (&acc)[2][NN]) {
-    constexpr int LD = tower_ld<16>();
-#pragma unroll
-    for (int n = 0; n < NN; ++n) {
-        const int P = n * 16 + l16;
-        if (P >= npix) continue;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            h4 *const o = (h4 *)(dst + P * LD + wave * 32 + 16 * m + 4 * q);
-            float v[4] = {acc[m][n][0] + bv[m].x, acc[m][n][1] + bv[m].y, acc[m][n][2] + bv[m].z,
-                          acc[m][n][3] + bv[m].w};
-            if (res) {
-                const h4 rv = *o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += (float)rv[e];
-            }
-            h4 ov;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ov[e] = (_Float16)relu_nan(v[e]);
-            *o = ov;
-        }
-    }
-}
-
-// tower_epilogue16 with the residual layer's reads issued together (one wait for all 16
-// instead of a read-wait-add chain per 4 channels), no per-tile branch when the tile is full
-// and the residual switch resolved per layer (RES): the same per-element arithmetic.
+// The 16x16x32 form's epilogue, tower_epilogue's per-element arithmetic in that form's
+// accumulator layout: lane l holds, for N tile n and M tile m, pixel 16 n + (l & 15) and the
+// four channels wave * 32 + 16 m + 4 (l >> 4) .. + 3 (acc[m][n][0..3], bias slice bv[m]), one
+// 8-byte store each.  A residual layer's (RES) 2 NN reads of dst are issued together, one wait
+// for all of them; CHECK: the tile is not full, so a lane whose pixel is at or past npix reads
+// a valid row in its place and does not store.
 template <int NN, bool RES, bool CHECK>
 __device__ __forceinline__ void tower_epilogue16_batch(_Float16 *dst, const float4 (&bv)[2], int npix, int wave,
                                                        int l16, int q, const f4x (&acc)[2][NN]) {
@@ -979,6 +860,10 @@ __device__ __forceinline__ void tower_epilogue16_batch(_Float16 *dst, const floa
     }
 }
 
+// One layer's epilogue in the 16x16x32 form (lane l: pixel 16 n + l16 of each N tile,
+// channels wave * 32 + 16 m + 4 q .. + 3, l16 = l & 15, q = l >> 4): picks the
+// tower_epilogue16_batch instance for this layer's residual and for a full or partial tile,
+// so neither is tested per store.
 template <int NN>
 __device__ __forceinline__ void tower_epilogue16b(_Float16 *dst, const float4 (&bv)[2], bool res, int npix, int wave,
                                                   int l16, int q, const f4x (&acc)[2][NN]) {
@@ -988,100 +873,6 @@ __device__ __forceinline__ void tower_epilogue16b(_Float16 *dst, const float4 (&
     } else {
         if (res) tower_epilogue16_batch<NN, true, true>(dst, bv, npix, wave, l16, q, acc);
         else tower_epilogue16_batch<NN, false, true>(dst, bv, npix, wave, l16, q, acc);
-    }
-}
-
-// tower_epilogue16 with whole 16-byte stores: the per-element arithmetic in the MFMA layout
-// (residual read per 4 channels, as there), then one v_permlane16_swap per dword hands lane
-// (pixel, q) the 8 consecutive channels wave * 32 + 16 (q & 1) + 8 (q >> 1) .. + 7 of its
-// pixel (rows 0 / 2 keep M tile 0 and take the next row's, rows 1 / 3 the M tile 1 halves):
-// 8 ds_write_b128 per layer and wave instead of 16 ds_write_b64, 2-way instead of 4-way on
-// the 72-dword rows.  Every lane takes part in the swaps; only the store is predicated.
-template <int NN>
-__device__ __forceinline__ void tower_epilogue16_swap(_Float16 *dst, const float4 (&bv)[2], bool res, int npix,
-                                                      int wave, int l16, int q, const f4x (&acc)[2][NN]) {
-    constexpr int LD = tower_ld<16>();
-    const int co8 = wave * 32 + 16 * (q & 1) + 8 * (q >> 1);
-    h4 rv[2][NN];  // the residual, every read issued before the first use
-    if (res) {
-#pragma unroll
-        for (int n = 0; n < NN; ++n)
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-                rv[m][n] = *(const h4 *)(dst + min(n * 16 + l16, npix - 1) * LD + wave * 32 + 16 * m + 4 * q);
-    }
-#pragma unroll
-    for (int n = 0; n < NN; ++n) {
-        const int P = n * 16 + l16;
-        uint32_t pk[2][2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            float v[4] = {acc[m][n][0] + bv[m].x, acc[m][n][1] + bv[m].y, acc[m][n][2] + bv[m].z,
-                          acc[m][n][3] + bv[m].w};
-            if (res) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += (float)rv[m][n][e];
-            }
-            h4 ov;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ov[e] = (_Float16)relu_nan(v[e]);
-            __builtin_memcpy(pk[m], &ov, 8);
-        }
-        const auto s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
-        const auto s1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
-        if (P < npix) *(uint4 *)(dst + P * LD + co8) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
-    }
-}
-
-// The epilogue on the swizzled layout: the fp32 accumulators are first handed over by
-// v_permlane16_swap (4 per N tile) so that lane (pixel l16, q) holds the 8 consecutive
-// channels co8 = wave * 32 + 16 (q & 1) + 8 (q >> 1) .. + 7 of its pixel — one chunk — and the
-// residual read, + bias, + residual, ReLU, fp16 and the store are whole 16-byte chunks
-// (conflict-free, see hsw).  Per element the arithmetic of tower_epilogue16: bit-identical.
-// bv8: this lane's 8 bias values (channels co8 ..).
-template <int NN, bool RES, bool CHECK>
-__device__ __forceinline__ void tower_epilogue16_swz(_Float16 *dst, const float (&bv8)[8], int npix, int wave, int l16,
-                                                     int q, const f4x (&acc)[2][NN]) {
-    const int c8 = wave * 4 + 2 * (q & 1) + (q >> 1);  // the lane's chunk (co8 / 8)
-    h8 rv[NN];
-    if constexpr (RES) {
-#pragma unroll
-        for (int n = 0; n < NN; ++n) {
-            const int P = CHECK ? min(n * 16 + l16, npix - 1) : n * 16 + l16;  // a valid row to read
-            rv[n] = *(const h8 *)(dst + swz(P, c8));
-        }
-    }
-#pragma unroll
-    for (int n = 0; n < NN; ++n) {
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[0][n][e]), __float_as_uint(acc[1][n][e]),
-                                                             false, false);
-            v[e] = __uint_as_float(sw[0]);
-            v[4 + e] = __uint_as_float(sw[1]);
-        }
-        h8 ov;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float y = v[e] + bv8[e];
-            if constexpr (RES) y += (float)rv[n][e];
-            ov[e] = (_Float16)relu_nan(y);
-        }
-        const int P = n * 16 + l16;
-        if (!CHECK || P < npix) *(h8 *)(dst + swz(P, c8)) = ov;
-    }
-}
-
-template <int NN>
-__device__ __forceinline__ void tower_epilogue16s(_Float16 *dst, const float (&bv8)[8], bool res, int npix, int wave,
-                                                  int l16, int q, const f4x (&acc)[2][NN]) {
-    if (npix >= NN * 16) {
-        if (res) tower_epilogue16_swz<NN, true, false>(dst, bv8, npix, wave, l16, q, acc);
-        else tower_epilogue16_swz<NN, false, false>(dst, bv8, npix, wave, l16, q, acc);
-    } else {
-        if (res) tower_epilogue16_swz<NN, true, true>(dst, bv8, npix, wave, l16, q, acc);
-        else tower_epilogue16_swz<NN, false, true>(dst, bv8, npix, wave, l16, q, acc);
     }
 }
 
@@ -1103,26 +894,30 @@ struct TowerPolicy {
 // row count on the device: nboards is then the capacity the grid was sized for, and a workgroup
 // whose first board is at or past min(*count, nboards) returns before it touches LDS; the others
 // run on the clamped count, so rows at or past it are neither read nor written.
-template <int H, int W, int BPH, int CIN0, int NT, int WPE, int PG = 1, int MF = 32, int EPI = 0, typename... CNT>
-__global__ __launch_bounds__(256 * PG) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void tower_kernel(
+template <int H, int W, int BPH, int CIN0, int NT, int WPE, int MF, typename... CNT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void tower_kernel(
     int nboards, int nconv, const _Float16 *__restrict__ in, const _Float16 *__restrict__ wall,
     const float *__restrict__ ball, _Float16 *__restrict__ out, const float *__restrict__ fcw, float fcb,
     double *__restrict__ values, TowerPolicy pol, CNT... cnt) {
     static_assert(sizeof...(CNT) <= 1, "at most one count argument");
     constexpr int HW = H * W;
-    static_assert(BPH * HW <= 32 * NT * PG, "tile too large");
-    static_assert(MF == 32 || (MF == 16 && PG == 1), "the 16x16x32 form has one pixel group");
-    constexpr int TP = 32 * NT * PG;
-    constexpr int NTH = 256 * PG;   // threads
+    static_assert(BPH * HW <= 32 * NT, "tile too large");
+    static_assert(MF == 32 || MF == 16, "the 32x32x16 or the 16x16x32 MFMA form");
+    constexpr int TP = 32 * NT;
+    constexpr int NTH = 256;  // threads
     constexpr int KC0 = CIN0 / 16;
-    constexpr bool SWZ = EPI == 3;  // the swizzled layout (hsw): unpadded rows, chunk c at c ^ hsw(row)
-    static_assert(!SWZ || (MF == 16 && PG == 1), "the swizzled layout is the 16x16x32 form's");
-    constexpr int LD = SWZ ? kSwzLD : tower_ld<MF>(), ZR = tower_zr<MF>(), BUF1 = tower_buf1<NT, PG, MF>();
+    constexpr int LD = tower_ld<MF>(), ZR = tower_zr<MF>(), BUF1 = tower_buf1<NT, MF>();
     constexpr int NP = MF == 16 ? 2 * NT : NT;  // pixel tiles per wave (16 or 32 pixels)
     constexpr size_t kW0 = (size_t)9 * CIN0 * kCout, kW = (size_t)9 * kCout * kCout;  // halfs per layer
     extern __shared__ __attribute__((aligned(16))) _Float16 lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) & 3, pg = tid >> 8;
-    const int pbase = pg * 32 * NT;   // this wave's first pixel of the tile
+    const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) & 3;
+    // tid_hi and pbase are 0: a workgroup is 256 threads.  The compiler learns that bound only in
+    // its backend, so until there these are values to it, and with a literal 0 in their place
+    // the 32x32x16 form's pixel indices, the value head's board loop and the policy conv's
+    // output address fold earlier and the schedule and register allocation of the whole kernel
+    // shift.  They stay as expressions so that retiring the two-pixel-group form changed no
+    // instruction (profiles/retired_net_switches_isa.txt).
+    const int tid_hi = tid >> 8, pbase = tid_hi * 32 * NT;
     const int b0 = blockIdx.x * BPH;
     if constexpr (sizeof...(CNT) == 1) {
         const int32_t *const count = (cnt, ...);
@@ -1156,10 +951,9 @@ __global__ __launch_bounds__(256 * PG) __attribute__((amdgpu_waves_per_eu(WPE, W
             const int i = tid + q * NTH, row = i / C8, c8 = i - row * C8;
             if (row >= TP) break;
             const h8 t = *(const h8 *)(src + min(row, npix - 1) * CIN0 + c8 * 8);
-            *(h8 *)(lds + (SWZ ? swz(BUF1 + row, c8) : (BUF1 + row) * LD + c8 * 8)) = row < npix ? t : zero;
+            *(h8 *)(lds + (BUF1 + row) * LD + c8 * 8) = row < npix ? t : zero;
         }
-        for (int z = tid; z < ZR * LD / 8; z += NTH)
-            *(h8 *)(lds + tower_zero<NT, PG>() * LD + z * 8) = zero;
+        for (int z = tid; z < ZR * LD / 8; z += NTH) *(h8 *)(lds + tower_zero<NT>() * LD + z * 8) = zero;
     }
     int prow[NP], pyx[NP];
 #pragma unroll
@@ -1181,8 +975,8 @@ __global__ __launch_bounds__(256 * PG) __attribute__((amdgpu_waves_per_eu(WPE, W
         // per-lane pixel coordinates re-derived inside the layer (opaque to the compiler), so
         // that the 36 tap addresses are not hoisted out of the layer loop into registers
         const int src = (l & 1) ? 0 : BUF1, dst = (l & 1) ? BUF1 : 0;
-        const _Float16 *const wa = l == 0 ? wl0 : wl0 + kW0 + (size_t)((ZC_TOWER_DIAG & 4) ? 0 : l - 1) * kW;
-        const _Float16 *const wn = l + 1 < nconv ? wl0 + kW0 + (size_t)((ZC_TOWER_DIAG & 4) ? 0 : l) * kW : nullptr;  // layer l+1's
+        const _Float16 *const wa = l == 0 ? wl0 : wl0 + kW0 + (size_t)(l - 1) * kW;
+        const _Float16 *const wn = l + 1 < nconv ? wl0 + kW0 + (size_t)l * kW : nullptr;  // layer l+1's
         if constexpr (MF == 16) {
             int py16[NP];  // (the pixel rows are l16 + 16 t: nothing to carry)
 #pragma unroll
@@ -1195,15 +989,6 @@ __global__ __launch_bounds__(256 * PG) __attribute__((amdgpu_waves_per_eu(WPE, W
             for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int t = 0; t < NP; ++t) acc[m][t] = f4x{0.0f, 0.0f, 0.0f, 0.0f};
-            if constexpr (SWZ) {
-                const float *bp = ball + (size_t)l * kCout + wave * 32 + 16 * (q4 & 1) + 8 * (q4 >> 1);
-                const float4 b0 = *(const float4 *)bp, b1 = *(const float4 *)(bp + 4);
-                const float bv8[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-                tower_mfma16_swz<H, W, NP, KC, 8, tower_zero<NT>()>(lds, src, wa, wn, a, l16, py16, q4, acc);
-                tower_epilogue16s<NP>(lds + dst * LD, bv8, l >= 2 && !(l & 1), npix, wave, l16, q4, acc);
-                __syncthreads();
-                return;
-            }
             float4 bv[2];
 #pragma unroll
             for (int m = 0; m < 2; ++m) bv[m] = *(const float4 *)(ball + (size_t)l * kCout + wave * 32 + 16 * m + 4 * q4);
@@ -1219,12 +1004,7 @@ __global__ __launch_bounds__(256 * PG) __attribute__((amdgpu_waves_per_eu(WPE, W
             __builtin_amdgcn_sched_barrier(0);
             st_mfma += ts1 - ts0;
 #endif
-            if constexpr (EPI == 1)
-                tower_epilogue16_swap<NP>(lds + dst * LD, bv, l >= 2 && !(l & 1), npix, wave, l16, q4, acc);
-            else if constexpr (EPI == 2)
-                tower_epilogue16<NP>(lds + dst * LD, bv, l >= 2 && !(l & 1), npix, wave, l16, q4, acc);
-            else
-                tower_epilogue16b<NP>(lds + dst * LD, bv, l >= 2 && !(l & 1), npix, wave, l16, q4, acc);
+            tower_epilogue16b<NP>(lds + dst * LD, bv, l >= 2 && !(l & 1), npix, wave, l16, q4, acc);
 #if ZC_TOWER_STAMP
             __builtin_amdgcn_sched_barrier(0);
             const uint64_t ts2 = __builtin_amdgcn_s_memtime();
@@ -1252,8 +1032,8 @@ __global__ __launch_bounds__(256 * PG) __attribute__((amdgpu_waves_per_eu(WPE, W
             float4 bv[4];  // this wave's bias slice, in flight during the MFMA loop
 #pragma unroll
             for (int g = 0; g < 4; ++g) bv[g] = *(const float4 *)(ball + (size_t)l * kCout + wave * 32 + 8 * g + 4 * hh);
-            tower_mfma<H, W, NT, KC, 8, PG>(lds, src, wa, wn, a, pr, py, hh, acc);
-            tower_epilogue(lds + dst * LD, bv, l >= 2 && !(l & 1), npix, wave, r, hh, acc, pbase);
+            tower_mfma<H, W, NT, KC, 8>(lds, src, wa, wn, a, pr, py, hh, acc);
+            tower_epilogue(lds + dst * LD, bv, l >= 2 && !(l & 1), npix, wave, pbase + r, hh, acc);
         }
         __syncthreads();
     };
@@ -1272,11 +1052,11 @@ __global__ __launch_bounds__(256 * PG) __attribute__((amdgpu_waves_per_eu(WPE, W
         // the value head on it, one wave per board: value_head_kernel's arithmetic in its
         // order (lane l sums channels 8 (l & 15) .. +8 over pixels l / 16, +4, ...), from LDS
         const int c0 = (lane & 15) * 8;
-        for (int bi = wave + 4 * pg; bi < npix / HW; bi += 4 * PG) {
+        for (int bi = wave + 4 * tid_hi; bi < npix / HW; bi += 4) {
             const _Float16 *act = lds + bi * HW * LD + c0;
             float sum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             for (int p = lane >> 4; p < HW; p += 4) {
-                const h8 v = *(const h8 *)(SWZ ? lds + swz(bi * HW + p, lane & 15) : act + p * LD);
+                const h8 v = *(const h8 *)(act + p * LD);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) sum[e] += (float)v[e];
             }
@@ -1293,10 +1073,9 @@ __global__ __launch_bounds__(256 * PG) __attribute__((amdgpu_waves_per_eu(WPE, W
         }
     }
     if (pol.out) {
-        // the 1x1 conv: wave (pg, wave) takes pixel tiles wave, wave + 4, ... of its group (32
-        // pixels each); per block of 32 output channels 8 MFMAs over the 128 channels, + bias,
-        // ReLU (the linear head's conv) or not (the convolutional head's logits), fp16 ->
-        // [pixel][32 * mblocks]
+        // the 1x1 conv: each wave takes pixel tiles wave, wave + 4, ... (32 pixels each); per
+        // block of 32 output channels 8 MFMAs over the 128 channels, + bias, ReLU (the linear
+        // head's conv) or not (the convolutional head's logits), fp16 -> [pixel][32 * mblocks]
         const int nout = 32 * pol.mblocks;
         for (int mb = 0; mb < pol.mblocks; ++mb) {
             h8 pa[8];
@@ -1313,7 +1092,7 @@ __global__ __launch_bounds__(256 * PG) __attribute__((amdgpu_waves_per_eu(WPE, W
                 for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
 #pragma unroll
                 for (int kc = 0; kc < 8; ++kc) {
-                    const h8 x = *(const h8 *)(lds + (SWZ ? swz(P, 2 * kc + hh) : P * LD + kc * 16 + hh * 8));
+                    const h8 x = *(const h8 *)(lds + P * LD + kc * 16 + hh * 8);
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(pa[kc], x, acc, 0, 0, 0);
                 }
                 if (P < npix) {
@@ -1337,17 +1116,16 @@ __global__ __launch_bounds__(256 * PG) __attribute__((amdgpu_waves_per_eu(WPE, W
         for (int q = 0; q < TP * (kCout / 8) / NTH; ++q) {
             const int i = tid + q * NTH, P = i >> 4, c0 = (i & 15) * 8;
             if (P < npix)
-                *(h8 *)(out + ((size_t)b0 * HW + P) * kCout + c0) =
-                    *(const h8 *)(lds + (SWZ ? swz(P, i & 15) : P * LD + c0));
+                *(h8 *)(out + ((size_t)b0 * HW + P) * kCout + c0) = *(const h8 *)(lds + P * LD + c0);
         }
     }
 }
 
 // A/B and test switches of the network launches.  Read from the environment ONCE, when the
-// library loads (ZC_TOWER_MF, ZC_TOWER_EPI, ZC_HEAD_RAW), and changed afterwards only through
+// library loads (ZC_TOWER_MF, ZC_HEAD_RAW), and changed afterwards only through
 // zc_debug_net_switch — a product process never re-reads the environment per launch.
 struct NetSwitches {
-    int tower_mf, tower_epi, head_raw;
+    int tower_mf, head_raw;
 };
 int env_switch(const char *name, int dflt, int (*parse)(const char *)) {
     const char *e = getenv(name);
@@ -1355,48 +1133,20 @@ int env_switch(const char *name, int dflt, int (*parse)(const char *)) {
 }
 NetSwitches g_net_sw = {
     env_switch("ZC_TOWER_MF", 0, [](const char *e) { return !strcmp(e, "32") ? 32 : !strcmp(e, "16") ? 16 : 0; }),
-    env_switch("ZC_TOWER_EPI", 0, [](const char *e) { return e[0] >= '0' && e[0] <= '3' && !e[1] ? e[0] - '0' : 0; }),
     env_switch("ZC_HEAD_RAW", 0, [](const char *e) { return !strcmp(e, "1") ? 1 : 0; })};
 
-int tower_epi() {  // 1 = the 16x16x32 form's epilogue with 16-byte stores,
-                  // 2 = the per-tile read-wait-add epilogue (before the batched one)
-    return g_net_sw.tower_epi;
-}
-
-template <int H, int W, int BPH, int NT, int WPE, int PG = 1, int MF = 32>
+template <int H, int W, int BPH, int NT, int WPE, int MF>
 void launch_tower(int n, int nconv, const void *in, const void *wall, const float *ball, void *out, const float *fcw,
                   float fcb, double *values, TowerPolicy pol, const int32_t *count, hipStream_t s) {
-    if (count) {  // the counted form: the default epilogue only (the A/B epilogues are the plain launch's)
-        hipLaunchKernelGGL((tower_kernel<H, W, BPH, 32, NT, WPE, PG, MF, 0, const int32_t *>), dim3((n + BPH - 1) / BPH),
-                           dim3(256 * PG), (tower_lds<NT, PG, MF>()), s, n, nconv, (const _Float16 *)in,
-                           (const _Float16 *)wall, ball, (_Float16 *)out, fcw, fcb, values, pol, count);
-        return;
-    }
-    if constexpr (MF == 16) {
-        if (tower_epi() == 1) {
-            hipLaunchKernelGGL((tower_kernel<H, W, BPH, 32, NT, WPE, PG, MF, 1>), dim3((n + BPH - 1) / BPH),
-                               dim3(256 * PG), (tower_lds<NT, PG, MF>()), s, n, nconv, (const _Float16 *)in,
-                               (const _Float16 *)wall, ball, (_Float16 *)out, fcw, fcb, values, pol);
-            return;
-        }
-        if (tower_epi() == 2) {
-            hipLaunchKernelGGL((tower_kernel<H, W, BPH, 32, NT, WPE, PG, MF, 2>), dim3((n + BPH - 1) / BPH),
-                               dim3(256 * PG), (tower_lds<NT, PG, MF>()), s, n, nconv, (const _Float16 *)in,
-                               (const _Float16 *)wall, ball, (_Float16 *)out, fcw, fcb, values, pol);
-            return;
-        }
-        if (tower_epi() == 3) {
-            hipLaunchKernelGGL((tower_kernel<H, W, BPH, 32, NT, WPE, PG, MF, 3>), dim3((n + BPH - 1) / BPH),
-                               dim3(256 * PG), (tower_lds_swz<NT>()), s, n, nconv, (const _Float16 *)in,
-                               (const _Float16 *)wall, ball, (_Float16 *)out, fcw, fcb, values, pol);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((tower_kernel<H, W, BPH, 32, NT, WPE, PG, MF>), dim3((n + BPH - 1) / BPH),
-                           dim3(256 * PG), (tower_lds<NT, PG, MF>()), s, n, nconv, (const _Float16 *)in,
-                           (const _Float16 *)wall, ball, (_Float16 *)out, fcw, fcb, values, pol);
+    const dim3 grid((n + BPH - 1) / BPH), block(256);
+    if (count)  // the counted form
+        hipLaunchKernelGGL((tower_kernel<H, W, BPH, 32, NT, WPE, MF, const int32_t *>), grid, block,
+                           (tower_lds<NT, MF>()), s, n, nconv, (const _Float16 *)in, (const _Float16 *)wall, ball,
+                           (_Float16 *)out, fcw, fcb, values, pol, count);
+    else
+        hipLaunchKernelGGL((tower_kernel<H, W, BPH, 32, NT, WPE, MF>), grid, block, (tower_lds<NT, MF>()), s, n, nconv,
+                           (const _Float16 *)in, (const _Float16 *)wall, ball, (_Float16 *)out, fcw, fcb, values, pol);
 }
-
 
 // [9][kCout][cin] -> the stream form's fragments: packed[((tap * KC + kc) * 4 + mb) * 512 +
 // lane * 8 + e] = w[tap][mb * 32 + lane % 32][kc * 16 + 8 * (lane / 32) + e].
@@ -1458,18 +1208,6 @@ __global__ __launch_bounds__(256) void value_head_kernel(int n, int hw, const _F
     if (lane == 0) values[i] = raw ? (double)(d + fcb) : (double)tanhf(d + fcb);
 }
 
-// head_raw = 1 (tests only): the value head returns its pre-tanh sum, so the pooled Linear
-// can be checked exactly against float64 on integer networks
-int head_raw() { return g_net_sw.head_raw; }
-
-int conv_impl() {  // ZC_CONV_IMPL=tile: 256-pixel tiles for every layer; default: half tiles for 128 planes
-    static const int v = [] {
-        const char *e = getenv("ZC_CONV_IMPL");
-        return e && !strcmp(e, "tile") ? 0 : 1;
-    }();
-    return v;
-}
-
 // The MFMA form (zc_debug_net_switch("tower_mf", ...) between launches, so an A/B can alternate in one process): the fused tower
 // runs the 16x16x32 form (+9 % over 32x32x16 at the power-held clock, outputs bit-identical:
 // profiles/r04_ab_tower_mf.log) unless ZC_TOWER_MF=32; the packed per-layer conv keeps the
@@ -1477,37 +1215,28 @@ int conv_impl() {  // ZC_CONV_IMPL=tile: 256-pixel tiles for every layer; defaul
 int tower_mf() { return g_net_sw.tower_mf == 32 ? 32 : 16; }
 int stream_mf() { return g_net_sw.tower_mf == 16 ? 16 : 32; }
 
-int stream_wpe() {  // ZC_CONV_WPE=2: the packed form at two workgroups per CU (default 3)
-    static const int v = [] {
-        const char *e = getenv("ZC_CONV_WPE");
-        return e && !strcmp(e, "2") ? 2 : 3;
-    }();
-    return v;
-}
-
+// The packed per-layer conv: the 16x16x32 form at two workgroups per CU (its fp32 epilogue tile
+// goes through LDS whole), the 32x32x16 form at three (in two halves)
 template <int H, int W, int BPH, int CIN>
 void launch_stream(int n, const void *in, const void *wp, const float *bias, const void *res, void *out, int relu,
                    hipStream_t s) {
-    const size_t tile = (size_t)(kHalfPix + 16) * (CIN + 8) * sizeof(_Float16);
     if (stream_mf() == 16) {
         const size_t tile16 = (size_t)(kHalfPix + 16) * (CIN + 16) * sizeof(_Float16);
         hipLaunchKernelGGL((conv3x3_stream_kernel<H, W, BPH, CIN, 2, 16>), dim3((n + BPH - 1) / BPH), dim3(256),
                            std::max(tile16, kHalfEpiBytes), s, n, (const _Float16 *)in, (const _Float16 *)wp, bias,
                            (const _Float16 *)res, (_Float16 *)out, relu);
-    } else if (stream_wpe() == 2)
-        hipLaunchKernelGGL((conv3x3_stream_kernel<H, W, BPH, CIN, 2>), dim3((n + BPH - 1) / BPH), dim3(256),
-                           std::max(tile, kHalfEpiBytes), s, n, (const _Float16 *)in, (const _Float16 *)wp, bias,
-                           (const _Float16 *)res, (_Float16 *)out, relu);
-    else
-        hipLaunchKernelGGL((conv3x3_stream_kernel<H, W, BPH, CIN, 3>), dim3((n + BPH - 1) / BPH), dim3(256),
+    } else {
+        const size_t tile = (size_t)(kHalfPix + 16) * (CIN + 8) * sizeof(_Float16);
+        hipLaunchKernelGGL((conv3x3_stream_kernel<H, W, BPH, CIN, 3, 32>), dim3((n + BPH - 1) / BPH), dim3(256),
                            std::max(tile, kHalfEpiBytes / 2), s, n, (const _Float16 *)in, (const _Float16 *)wp, bias,
                            (const _Float16 *)res, (_Float16 *)out, relu);
+    }
 }
 
 template <int H, int W, int BPW, int BPH, int CIN>
 void launch_conv(int n, const void *in, const void *wt, const float *bias, const void *res, void *out, int relu,
                  hipStream_t s) {
-    if (conv_impl() == 1 && CIN >= 64) {  // the 32-plane stem runs faster on 256-pixel tiles
+    if constexpr (CIN >= 64) {  // the 32-plane stem runs faster on 256-pixel tiles
         const size_t lds = std::max((size_t)(kHalfPix + 1 + kCout) * (CIN + 8) * sizeof(_Float16), kHalfEpiBytes);
         hipLaunchKernelGGL((conv3x3_half_kernel<H, W, BPH, CIN>), dim3((n + BPH - 1) / BPH), dim3(256), lds, s, n,
                            (const _Float16 *)in, (const _Float16 *)wt, bias, (const _Float16 *)res, (_Float16 *)out,
@@ -1557,23 +1286,15 @@ bool launch_net_tower(int n, int h, int w, int cin0, int nconv, const void *in, 
                       void *pout, hipStream_t s, int pol_channels, int pol_relu, const int32_t *count) {
     if (cin0 != 32 || nconv < 1 || !(nconv & 1)) return false;
     if (pout && pol_channels != 32 && pol_channels != 64) return false;
-    const TowerPolicy pol{(const _Float16 *)pw, pb, (_Float16 *)pout, head_raw(), pol_channels / 32, pol_relu ? 1 : 0};
+    const TowerPolicy pol{(const _Float16 *)pw, pb, (_Float16 *)pout, net_head_raw(), pol_channels / 32, pol_relu ? 1 : 0};
     // 128-pixel tiles at two workgroups per CU; 64-pixel tiles (one chess board) at 3 or 4
     // workgroups per CU measured 10 % slower (tools/ab_tower.py)
-#ifndef ZC_TOWER_PG
-#define ZC_TOWER_PG 1
-#endif
-#if ZC_TOWER_PG == 2
-    if (h == 8 && w == 8) launch_tower<8, 8, 4, 4, 2, 2>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
-    else if (h == 6 && w == 7) launch_tower<6, 7, 6, 4, 2, 2>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
-#else
     if (tower_mf() == 16) {
-        if (h == 8 && w == 8) launch_tower<8, 8, 2, 4, 2, 1, 16>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
-        else if (h == 6 && w == 7) launch_tower<6, 7, 3, 4, 2, 1, 16>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
+        if (h == 8 && w == 8) launch_tower<8, 8, 2, 4, 2, 16>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
+        else if (h == 6 && w == 7) launch_tower<6, 7, 3, 4, 2, 16>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
         else return false;
-    } else if (h == 8 && w == 8) launch_tower<8, 8, 2, 4, 2>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
-    else if (h == 6 && w == 7) launch_tower<6, 7, 3, 4, 2>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
-#endif
+    } else if (h == 8 && w == 8) launch_tower<8, 8, 2, 4, 2, 32>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
+    else if (h == 6 && w == 7) launch_tower<6, 7, 3, 4, 2, 32>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
     else return false;
     return true;
 }
@@ -1594,12 +1315,16 @@ void launch_net_planes_to_nhwc(int n, int cin, int hw, int cpad, const void *pla
 
 void launch_net_value_head(int n, int hw, const void *act, const float *fcw, float fcb, double *values, hipStream_t s) {
     hipLaunchKernelGGL(value_head_kernel, dim3((unsigned)(((int64_t)n * 64 + 255) / 256)), dim3(256), 0, s, n, hw,
-                       (const _Float16 *)act, fcw, fcb, values, head_raw());
+                       (const _Float16 *)act, fcw, fcb, values, net_head_raw());
 }
 
 }  // namespace zc
 
 namespace zc {
+// head_raw = 1 (tests only): the value heads of both widths return their pre-tanh sum, so the
+// pooled Linear can be checked exactly against float64 on integer networks
+int net_head_raw() { return g_net_sw.head_raw; }
+
 // zc_debug_net_switch (engine.hip): false for an unknown name or value
 bool net_switch(const char *name, int value, int *old) {
     int *slot = nullptr;
@@ -1607,9 +1332,6 @@ bool net_switch(const char *name, int value, int *old) {
     if (name && !strcmp(name, "tower_mf")) {
         slot = &g_net_sw.tower_mf;
         ok = value == 0 || value == 16 || value == 32;
-    } else if (name && !strcmp(name, "tower_epi")) {
-        slot = &g_net_sw.tower_epi;
-        ok = value >= 0 && value <= 3;
     } else if (name && !strcmp(name, "head_raw")) {
         slot = &g_net_sw.head_raw;
         ok = value == 0 || value == 1;

@@ -36,8 +36,6 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #include "zc_internal.h"
@@ -418,13 +416,6 @@ __global__ void pack_conv64_weight_kernel(int cin, const _Float16 *__restrict__ 
     *(h8 *)(packed + (size_t)i * 8) = *(const h8 *)(w + ((size_t)tap * kC + row) * cin + k0);
 }
 
-// The value head's test switch (pre-tanh sums): ZC_HEAD_RAW when the library loads, then
-// zc_debug_net_switch("head_raw", ...), which sets it for both widths.
-int g_head_raw64 = [] {
-    const char *e = getenv("ZC_HEAD_RAW");
-    return e && !strcmp(e, "1") ? 1 : 0;
-}();
-
 template <int H, int W, int BPH>
 void launch_tower64(int n, int nconv, const void *in, const void *wall, const float *ball, void *out, const float *fcw,
                     float fcb, double *values, TowerPolicy64 pol, const int32_t *count, hipStream_t s) {
@@ -462,7 +453,7 @@ bool launch_net64_tower(int n, int h, int w, int cin0, int nconv, const void *in
                         void *pout, hipStream_t s, int pol_channels, int pol_relu, const int32_t *count) {
     if (cin0 != 32 || nconv < 1 || !(nconv & 1)) return false;
     if (pout && pol_channels != 32 && pol_channels != 64) return false;
-    const TowerPolicy64 pol{(const _Float16 *)pw, pb, (_Float16 *)pout, g_head_raw64, pol_channels / 16,
+    const TowerPolicy64 pol{(const _Float16 *)pw, pb, (_Float16 *)pout, net_head_raw(), pol_channels / 16,
                             pol_relu ? 1 : 0};
     if (h == 8 && w == 8) launch_tower64<8, 8, 2>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
     else if (h == 6 && w == 7) launch_tower64<6, 7, 3>(n, nconv, in, wall, ball, out, fcw, fcb, values, pol, count, s);
@@ -481,9 +472,7 @@ bool launch_net64_pack_conv_weight(int cin, const void *w, void *packed, hipStre
 void launch_net64_value_head(int n, int hw, const void *act, const float *fcw, float fcb, double *values,
                              hipStream_t s) {
     hipLaunchKernelGGL(value_head64_kernel, dim3((unsigned)(((int64_t)n * 64 + 255) / 256)), dim3(256), 0, s, n, hw,
-                       (const _Float16 *)act, fcw, fcb, values, g_head_raw64);
+                       (const _Float16 *)act, fcw, fcb, values, net_head_raw());
 }
-
-void net64_set_head_raw(int value) { g_head_raw64 = value ? 1 : 0; }
 
 }  // namespace zc

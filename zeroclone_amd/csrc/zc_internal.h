@@ -406,6 +406,7 @@ bool launch_net_pack_conv_weight(int cin, const void *w, void *packed, hipStream
 void launch_net_planes_to_nhwc(int n, int cin, int hw, int cpad, const void *planes, void *out, hipStream_t s);
 void launch_net_value_head(int n, int hw, const void *act, const float *fcw, float fcb, double *values, hipStream_t s);
 bool net_switch(const char *name, int value, int *old);  // zc_debug_net_switch
+int net_head_raw();  // the "head_raw" switch: the value heads of both widths write their pre-tanh sum
 // the 64-channel width (net_conv64.hip): the same arguments as their 128-channel namesakes
 bool launch_net64_tower(int n, int h, int w, int cin0, int nconv, const void *in, const void *wall, const float *ball,
                         void *out, const float *fcw, float fcb, double *values, const void *pw, const float *pb,
@@ -414,7 +415,6 @@ bool launch_net64_conv3x3_packed(int n, int h, int w, int cin, const void *in, c
                                  const void *res, void *out, int relu, hipStream_t s);
 bool launch_net64_pack_conv_weight(int cin, const void *w, void *packed, hipStream_t s);
 void launch_net64_value_head(int n, int hw, const void *act, const float *fcw, float fcb, double *values, hipStream_t s);
-void net64_set_head_raw(int value);  // zc_debug_net_switch("head_raw", ...) reaches both widths
 
 size_t c4_search_lds_bytes(int bs);
 void launch_c4_ext_begin(const ExtParams &p, hipStream_t s);
