@@ -5,8 +5,11 @@ There is no CPU fallback: if the library or a GPU is missing, constructing an en
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
+import re
 import threading
+import types
 
 import numpy as np
 
@@ -14,20 +17,58 @@ from .build import LIB
 
 P = ctypes.POINTER
 
-ZC_OK = 0
-ZC_EINVAL = -1
-ZC_EHIP = -2
-ZC_ENOMEM = -3
-ZC_ECAPACITY = -4
-ZC_EDEVICE = -5
-ZC_C4_ONGOING = 2
-ZC_STATUS_NO_MOVES = 1
-ROLLOUT_EXACT = 0   # ZC_ROLLOUT_EXACT
-ROLLOUT_PHILOX = 1  # ZC_ROLLOUT_PHILOX
-ZC_STATUS_BAD_STATE = 2
-ZC_F32 = 0
-ZC_F16 = 1
-ZC_F16_NHWC32 = 2   # planes only: fp16 NHWC [n][h*w][32], the MFMA tower's input layout
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "zeroclone.h")
+
+# The header's whole type vocabulary: these scalars, `const char *` (c_char_p), and pointers to
+# anything (c_void_p: it takes byref(), arrays, typed pointers, ints and None alike).
+_SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+            "uint32_t": ctypes.c_uint32, "double": ctypes.c_double, "float": ctypes.c_float, "int": ctypes.c_int}
+
+
+@functools.lru_cache(maxsize=None)
+def _ctype(text: str):
+    """The ctypes type of one return type or parameter, its name, if any, included."""
+    words = re.findall(r"\w+|\*", text)
+    if not words or not re.fullmatch(r"[\w\s*]+", text):
+        raise ValueError(f"cannot read {text.strip()!r}")
+    if "*" in words:
+        return ctypes.c_char_p if words[:3] == ["const", "char", "*"] and words.count("*") == 1 else ctypes.c_void_p
+    if words[0] not in _SCALARS or len(words) > 2:
+        raise ValueError(f"unknown type {text.strip()!r}")
+    return _SCALARS[words[0]]
+
+
+def parse_header(text: str):
+    """(signatures, constants) of a header's text: a (name, restype, argtypes) for every
+    `<ret> zc_name(<params>);` and the value of every `#define ZC_NAME <int>`.  A declaration
+    that is not understood is an error naming it, never a guess: a wrong argtype corrupts a call
+    without a sign."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    constants = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(ZC_\w+)[ \t]+(-?\d+)[ \t]*$", text,
+                                                      re.M)}
+    text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{', " ", text, flags=re.M)
+    signatures = []
+    for stmt in text.split(";"):
+        if not re.search(r"\bzc_\w+\s*\(", stmt):
+            continue
+        decl = " ".join(stmt.split())
+        m = re.fullmatch(r"\s*([\w\s*]+?)\b(zc_\w+)\s*\(([^()]*)\)\s*", stmt)
+        if not m:
+            raise ValueError(f"{HEADER}: cannot split the declaration {decl!r}")
+        try:
+            restype, *argtypes = [_ctype(t) for t in ([m[1]] if m[3].strip() == "void" else [m[1], *m[3].split(",")])]
+        except ValueError as e:
+            raise ValueError(f"{HEADER}: {e} in the declaration {decl!r}") from None
+        signatures.append((m[2], restype, argtypes))
+    return signatures, constants
+
+
+# Every function and every integer constant include/zeroclone.h declares, read from it once per
+# process: SIGNATURES as (name, restype, argtypes), the constants under their header names.
+with open(HEADER) as _f:
+    SIGNATURES, CONSTANTS = parse_header(_f.read())
+globals().update(CONSTANTS)
+ROLLOUT_EXACT, ROLLOUT_PHILOX = CONSTANTS["ZC_ROLLOUT_EXACT"], CONSTANTS["ZC_ROLLOUT_PHILOX"]
 
 
 class C4State(ctypes.Structure):
@@ -77,12 +118,7 @@ class TrainSet(ctypes.Structure):
                 ("d_pi", ctypes.c_void_p)]
 
 
-ZC_TRAIN_C4, ZC_TRAIN_CHESS = 0, 1
-ZC_TRAJ_PI_ENTRIES, ZC_TRAJ_PI_OVERFLOW = 0, 1
-ZC_TRAJ_PI_MAX_COUNT = 65535   # a policy entry's count field: 16 bits
-ZC_TRAJ_POSITIONS, ZC_TRAJ_GAMES, ZC_TRAJ_NEXT, ZC_TRAJ_QUOTA, ZC_TRAJ_FINISHED, ZC_TRAJ_OVERFLOW = range(6)
-ZC_SLOT_IDLE = 3
-ZC_SLOT_SKIP = 4
+ZC_TRAJ_PI_MAX_COUNT = 65535   # a policy entry's count field: 16 bits (not in the header)
 
 C4_STATE_DTYPE = np.dtype([("stones", "<u8", (2,)), ("turn", "<i4"), ("reserved", "<i4")])
 # zc_c4_hp_node: the host-policy walk's end (include/zeroclone.h)
@@ -93,8 +129,8 @@ STATS_DTYPE = np.dtype([("expansions", "<i8"), ("depth_sum", "<i8"), ("leaves", 
                         ("rollout_blocks", "<i8"), ("reserved", "<i8")])
 CHESS_STATE_DTYPE = np.dtype([("board", "u1", (64,)), ("turn", "u1"), ("fifty", "u1"), ("castle", "u1"),
                               ("reserved", "u1", (5,))])
-CHESS_MAX_MOVES = 256
-CHESS_ROLL_CAP = 2048   # ZC_CHESS_ROLL_CAP: moves per side a chess rollout's history holds
+CHESS_MAX_MOVES = CONSTANTS["ZC_CHESS_MAX_MOVES"]
+CHESS_ROLL_CAP = CONSTANTS["ZC_CHESS_ROLL_CAP"]   # moves per side a chess rollout's history holds
 # zc_chess_hp_node: the chess host-policy walk's end (include/zeroclone.h)
 CHESS_HP_NODE_DTYPE = np.dtype([("state", CHESS_STATE_DTYPE), ("node", "<i4"), ("n_untried", "<i4"), ("depth", "<i4"),
                                 ("reserved", "<i4"), ("untried", "<u2", (CHESS_MAX_MOVES,))])
@@ -109,340 +145,17 @@ C4_PNODE_DTYPE = np.dtype([("s0", "<u8"), ("s1", "<u8"), ("order", "<u4"), ("tur
                            ("pad0", "<u4"), ("child", "<u2", (8,)), ("na", "<i4", (8,)), ("pr", "<f4", (8,)),
                            ("w", "<f8", (8,)), ("pad1", "u1", (16,))])
 assert C4_PNODE_DTYPE.itemsize == 192
-ZC_CHESS_WIN, ZC_CHESS_STALEMATE, ZC_CHESS_FIFTY, ZC_CHESS_OVERFLOW = 1, 2, 4, 8
-ZC_POLICY_RANDOM, ZC_POLICY_IMMEDIATE_VALUE = 0, 1
-ZC_STATUS_INTERNAL = 3
-ZC_STATUS_CAPACITY = 4
 assert CHESS_STATE_DTYPE.itemsize == 72
 assert C4_STATE_DTYPE.itemsize == ctypes.sizeof(C4State) == 24
 assert STATS_DTYPE.itemsize == ctypes.sizeof(GameStats) == 64
 STATS_FIELDS = 8
 
-# Every symbol include/zeroclone.h declares: (name, restype, argtypes)
-SIGNATURES = [
-    ("zc_version", ctypes.c_char_p, []),
-    ("zc_last_error", ctypes.c_char_p, []),
-    ("zc_device_count", ctypes.c_int, [P(ctypes.c_int32)]),
-    ("zc_engine_create", ctypes.c_int, [P(EngineConfig), P(ctypes.c_void_p)]),
-    ("zc_engine_destroy", ctypes.c_int, [ctypes.c_void_p]),
-    ("zc_engine_footprint", ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_int64)]),
-    ("zc_rng_seed", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, P(ctypes.c_uint64)]),
-    ("zc_rng_set_state", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, P(ctypes.c_uint32), ctypes.c_int32]),
-    ("zc_rng_get_state", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, P(ctypes.c_uint32), P(ctypes.c_int32)]),
-    ("zc_c4_search", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                    ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p,
-                                    ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_c4_search_games", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_c4_set_rollout_mode", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64]),
-    ("zc_c4_search_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                          ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_c4_play_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_c4_ext_begin", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                       ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_c4_ext_select", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                        ctypes.c_void_p]),
-    ("zc_c4_ext_backup", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                        ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_c4_selfplay_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                            ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_void_p]),
-    ("zc_c4_selfplay_pooled_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                   ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
-                                                   ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_c4_selfplay_carry_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                  ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
-                                                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_c4_carry_discard", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_chess_play_step_async", ctypes.c_int, [ctypes.c_int32, P(ChessPlayBuffers), ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_selfplay_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, P(ChessPlayBuffers),
-                                               ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_selfplay_pooled_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                                      P(ChessPlayBuffers), ctypes.c_int32, ctypes.c_double,
-                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
-                                                      ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_pooled_max_games", ctypes.c_int, [ctypes.c_int32, P(ctypes.c_int32)]),
-    ("zc_c4_pooled_max_games", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, P(ctypes.c_int32)]),
-    ("zc_traj_steps_scratch_bytes", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, P(ctypes.c_int64)]),
-    ("zc_traj_record_steps_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_int64, ctypes.c_void_p]),
-    ("zc_c4_selfplay_visits", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
-    ("zc_chess_selfplay_visits", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
-    ("zc_traj_policy_steps_scratch_bytes", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, P(ctypes.c_int64)]),
-    ("zc_traj_policy_record_steps_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
-    ("zc_c4_hp_walk", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                     ctypes.c_void_p]),
-    ("zc_c4_hp_expand", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                       ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_c4_ext_end", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_c4_rollouts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                      ctypes.c_void_p, P(ctypes.c_int64)]),
-    ("zc_chess_legal_moves_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_children_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_play_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_repetition_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_terminal_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_void_p]),
-    ("zc_chess_planes_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_chess_reserve", ctypes.c_int, [ctypes.c_void_p]),
-    ("zc_chess_search_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                             ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
-                                             ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_void_p]),
-    ("zc_chess_ext_begin", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                          ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
-                                          ctypes.c_double, ctypes.c_void_p]),
-    ("zc_chess_ext_select", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                           ctypes.c_void_p]),
-    ("zc_chess_ext_backup", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                           ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_hp_walk", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                        ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_hp_expand", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_ext_end", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_rollouts_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                               ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_ext_rollouts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_ext_leaf_moves", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_puct_flushes", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32]),
-    ("zc_chess_puct_begin", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                           ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_float,
-                                           ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_chess_puct_select", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                            ctypes.c_void_p]),
-    ("zc_chess_puct_backup", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_chess_puct_backup_ex", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.c_void_p]),
-    ("zc_chess_puct_end", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                         ctypes.c_void_p]),
-    ("zc_chess_puct_begin_reuse", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                 ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_float,
-                                                 ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p]),
-    ("zc_chess_puct_forget", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_chess_puct_forget_fresh", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                  ctypes.c_void_p]),
-    ("zc_c4_puct_begin", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                        ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_float,
-                                        ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_c4_puct_begin_reuse", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                              ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_float,
-                                              ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
-                                              ctypes.c_void_p]),
-    ("zc_c4_puct_forget", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_c4_puct_forget_fresh", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                               ctypes.c_void_p]),
-    ("zc_c4_puct_select", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                         ctypes.c_void_p]),
-    ("zc_c4_puct_backup", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_c4_puct_backup_ex", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                            ctypes.c_void_p]),
-    ("zc_c4_puct_end", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_void_p]),
-    ("zc_debug_c4_puct_tree", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                             ctypes.c_void_p]),
-    ("zc_net_conv3x3_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_net_conv3x3_pack_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_net_conv3x3_packed_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_net_tower_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
-                                          ctypes.c_void_p]),
-    ("zc_net_tower_policy_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                 ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_net_tower_policy_ex_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                    ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                    ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                                                    ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                    ctypes.c_void_p]),
-    ("zc_net_tower_counted_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                  ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_net_tower_policy_counted_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                         ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_net_planes_to_nhwc_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_net_value_head_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
-    # the _w_ family: the calls above with the width (64 or 128 channels) as their first argument
-    ("zc_net_conv3x3_pack_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p]),
-    ("zc_net_conv3x3_packed_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                     ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                                     ctypes.c_void_p]),
-    ("zc_net_tower_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
-                                            ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_net_tower_policy_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
-                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                                   ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_net_tower_counted_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
-                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_net_tower_policy_counted_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                           ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
-                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                           ctypes.c_void_p]),
-    ("zc_net_value_head_w_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_traj_record_async", ctypes.c_int, [ctypes.c_int32, P(TrajBuffers), ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_traj_openings_async", ctypes.c_int, [ctypes.c_int32, P(TrajBuffers), ctypes.c_void_p, ctypes.c_int32,
-                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_traj_policy_append_async", ctypes.c_int, [ctypes.c_int32, P(TrajBuffers), P(TrajPolicyBuffers),
-                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_traj_policy_commit_async", ctypes.c_int, [ctypes.c_int32, P(TrajBuffers), P(TrajPolicyBuffers),
-                                                   ctypes.c_void_p]),
-    ("zc_traj_policy_dense_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_train_batch_async", ctypes.c_int, [P(TrainSet), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_train_loss_scratch_bytes", ctypes.c_int, [ctypes.c_int32, P(ctypes.c_int64)]),
-    ("zc_train_loss_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_arena_route_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_void_p]),
-    ("zc_arena_gather_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_arena_scatter_async", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_evalcache_bytes", ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, P(ctypes.c_int64),
-                                          P(ctypes.c_int64)]),
-    ("zc_evalcache_clear_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_void_p]),
-    ("zc_evalcache_probe_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p]),
-    ("zc_evalcache_commit_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_evalcache_merge_scratch_bytes", ctypes.c_int, [ctypes.c_int32, P(ctypes.c_int64)]),
-    ("zc_evalcache_probe_merged_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                       ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_evalcache_commit_merged_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_void_p]),
-    ("zc_evalcache_probe_routed_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                       ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                       ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_evalcache_commit_routed_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                        ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_void_p]),
-    ("zc_chess_from_fen", ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p]),
-    ("zc_chess_init", ctypes.c_int, [ctypes.c_void_p]),
-    ("zc_c4_from_rows", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, P(C4State)]),
-    ("zc_c4_to_rows", ctypes.c_int, [P(C4State), ctypes.c_char_p]),
-    ("zc_c4_legal_order", ctypes.c_int, [ctypes.c_int32, P(ctypes.c_int32)]),
-    ("zc_gen_reserve", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64]),
-    ("zc_gen_capacity", ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_int32), P(ctypes.c_int64)]),
-    ("zc_gen_begin", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
-                                    ctypes.c_void_p]),
-    ("zc_gen_walk", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_gen_expand", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_gen_backup", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_gen_end", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_debug_uct", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                    ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p]),
-    ("zc_debug_c4_uct_select", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
-                                              ctypes.c_void_p]),
-    ("zc_debug_chess_probe_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p]),
-    ("zc_debug_chess_tree", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_debug_c4_walk_async", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                              ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                              ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_debug_rng_copy", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                         ctypes.c_int32, ctypes.c_void_p]),
-    ("zc_debug_phase_cycles", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, P(ctypes.c_int64)]),
-    ("zc_debug_phase_cycles_games", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, P(ctypes.c_int64)]),
-    ("zc_debug_net_switch", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, P(ctypes.c_int32)]),
-    ("zc_debug_c4_launch_stamps", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
-    ("zc_debug_c4_rollout", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                           ctypes.c_void_p, ctypes.c_void_p]),
-]
-
 _lib = None
 _lock = threading.Lock()
+# The entry points of each game's searches by their name after the prefix (_C4.ext_begin is
+# zc_c4_ext_begin), filled in by lib(): the stepwise wrappers below are written once for both
+# games and take one of these, so a call looks nothing up by name.
+_C4, _CHESS = types.SimpleNamespace(), types.SimpleNamespace()
 
 
 class ZeroCloneError(RuntimeError):
@@ -466,6 +179,9 @@ def lib(build_if_missing: bool = True):
                 fn = getattr(L, name)
                 fn.restype = res
                 fn.argtypes = args
+                for game, fns in (("zc_c4_", _C4), ("zc_chess_", _CHESS)):
+                    if name.startswith(game):
+                        setattr(fns, name[len(game):], fn)
             _lib = L
     return _lib
 
@@ -527,7 +243,7 @@ def pack_chess_move(fr: int, fc: int, tr: int, tc: int, value: float) -> int:
     return (fr * 8 + fc) | ((tr * 8 + tc) << 6) | (int(value) << 12)
 
 
-ARENA_ROUTE_THREADS = 1024   # ZC_ARENA_ROUTE_THREADS: the route kernel's workgroup, and its chunk of keys
+ARENA_ROUTE_THREADS = CONSTANTS["ZC_ARENA_ROUTE_THREADS"]   # the route kernel's workgroup, and its chunk of keys
 
 
 def _arena_rc(name: str, rc: int):
@@ -581,8 +297,11 @@ def arena_scatter(n: int, rows: int, game_rows: int, row_bytes: int, d_perm: int
     _arena_copy("zc_arena_scatter_async", n, rows, game_rows, row_bytes, d_perm, d_src, d_dst, stream)
 
 
-EVALCACHE_WAYS = 8                                     # ZC_EVALCACHE_WAYS
-EVALCACHE_STATS = ("probed", "hits", "inserts", "dropped")   # ZC_EVALCACHE_STAT_*: the four int64 counters
+EVALCACHE_WAYS = CONSTANTS["ZC_EVALCACHE_WAYS"]
+# ZC_EVALCACHE_STAT_* in their order: the merged calls' five int64 counters, the plain calls' first four
+EVALCACHE_MERGED_STATS = tuple(k[len("ZC_EVALCACHE_STAT_"):].lower() for k in sorted(
+    (k for k in CONSTANTS if k.startswith("ZC_EVALCACHE_STAT_")), key=CONSTANTS.get))
+EVALCACHE_STATS = EVALCACHE_MERGED_STATS[:CONSTANTS["ZC_EVALCACHE_STAT_MERGED"]]
 
 
 def evalcache_check_sizes(entries: int, key_bytes: int, logit_bytes: int):
@@ -649,10 +368,6 @@ def evalcache_commit(d_table: int, entries: int, key_bytes: int, logit_bytes: in
                       (d_dense_logits and d_out_logits) or not logit_bytes),
                      (d_table, entries, key_bytes, logit_bytes, n_rows, rows_per_game, game_rows, d_keys, d_miss_rows,
                       d_count, d_dense_values, d_dense_logits, d_out_values, d_out_logits, d_stats, stream))
-
-
-# ZC_EVALCACHE_STAT_* of the merged calls: the five int64 counters
-EVALCACHE_MERGED_STATS = EVALCACHE_STATS + ("merged",)
 
 
 def evalcache_check_merged_sizes(entries: int, key_bytes: int, logit_bytes: int):
@@ -801,6 +516,105 @@ def train_loss(B: int, width: int, stride: int, d_logits: int, logits_f16: bool,
         ctypes.c_void_p(d_v), ctypes.c_void_p(d_z), ctypes.c_void_p(d_legal or None), ctypes.c_void_p(d_n_legal or None),
         ctypes.c_void_p(d_target or None), ctypes.c_void_p(d_scratch), int(scratch_bytes), ctypes.c_void_p(d_loss),
         ctypes.c_void_p(d_grad_v), ctypes.c_void_p(d_grad_logits or None), ctypes.c_void_p(stream or None)))
+
+
+# ---- the stepwise protocol's wrappers, each written once and bound by NativeEngine under both
+# games' names: g is the game's entry points (_C4 or _CHESS), fn one of them.  Device pointers as
+# ints, 0 = NULL.
+def _ext_begin(fn, self, first_game, n, d_roots, sims, c, batch_size, extra, stream):
+    """Both games' ext_begin; extra: what the game's entry point takes after batch_size."""
+    check(fn(self._h, first_game, n, ctypes.c_void_p(d_roots), int(sims), float(c), int(batch_size), *extra,
+             ctypes.c_void_p(stream or None)))
+
+
+def _select(fn, self, first_game, n, flush, d_leaves, d_planes, planes_dtype, d_counts, stream):
+    """Every select, of the value and the PUCT searches; planes_dtype: a ZC_F* code."""
+    check(fn(self._h, first_game, n, int(flush), ctypes.c_void_p(d_leaves or None), ctypes.c_void_p(d_planes or None),
+             planes_dtype, ctypes.c_void_p(d_counts or None), ctypes.c_void_p(stream or None)))
+
+
+def _ext_select(g):
+    def ext_select(self, first_game: int, n: int, flush: int, d_leaves: int = 0, d_planes: int = 0,
+                   planes_f16: bool = True, d_counts: int = 0, stream: int = 0) -> None:
+        _select(g.ext_select, self, first_game, n, flush, d_leaves, d_planes, ZC_F16 if planes_f16 else ZC_F32,
+                d_counts, stream)
+    return ext_select
+
+
+def _ext_backup(g):
+    def ext_backup(self, first_game: int, n: int, flush: int, d_values: int, stream: int = 0) -> None:
+        check(g.ext_backup(self._h, first_game, n, int(flush), ctypes.c_void_p(d_values),
+                           ctypes.c_void_p(stream or None)))
+    return ext_backup
+
+
+def _ext_end(g):
+    def ext_end(self, first_game: int, n: int, d_move: int, d_na: int, d_stats: int, stream: int = 0) -> None:
+        check(g.ext_end(self._h, first_game, n, ctypes.c_void_p(d_move), ctypes.c_void_p(d_na),
+                        ctypes.c_void_p(d_stats), ctypes.c_void_p(stream or None)))
+    return ext_end
+
+
+def _hp_walk(g):
+    def hp_walk(self, game: int, flush: int, leaf: int, d_node: int, stream: int = 0) -> None:
+        check(g.hp_walk(self._h, game, int(flush), int(leaf), ctypes.c_void_p(d_node), ctypes.c_void_p(stream or None)))
+    return hp_walk
+
+
+def _hp_expand(g):
+    def hp_expand(self, game: int, flush: int, leaf: int, index: int, d_leaf: int = 0, stream: int = 0) -> None:
+        """index: into the walk's untried moves, the range the game's entry point checks (7
+        columns, ZC_CHESS_MAX_MOVES moves); -1 at a node without untried moves."""
+        check(g.hp_expand(self._h, game, int(flush), int(leaf), int(index), ctypes.c_void_p(d_leaf or None),
+                          ctypes.c_void_p(stream or None)))
+    return hp_expand
+
+
+def _puct_begin(g):
+    def puct_begin(self, first_game, n, d_roots, sims, c_puct, batch_size, alpha, eps, seed, d_search_no=0, stream=0):
+        check(g.puct_begin(self._h, first_game, n, ctypes.c_void_p(d_roots), int(sims), float(c_puct),
+                           int(batch_size), float(alpha), float(eps), int(seed) & (2**64 - 1),
+                           ctypes.c_void_p(d_search_no or None), ctypes.c_void_p(stream or None)))
+    return puct_begin
+
+
+def _puct_begin_reuse(g):
+    def puct_begin_reuse(self, first_game, n, d_roots, sims, c_puct, batch_size, alpha, eps, seed, d_search_no=0,
+                         d_kept=0, stream=0):
+        """puct_begin that keeps each game's subtree of its new root (zc_*_puct_begin_reuse)."""
+        check(g.puct_begin_reuse(self._h, first_game, n, ctypes.c_void_p(d_roots), int(sims), float(c_puct),
+                                 int(batch_size), float(alpha), float(eps), int(seed) & (2**64 - 1),
+                                 ctypes.c_void_p(d_search_no or None), ctypes.c_void_p(d_kept or None),
+                                 ctypes.c_void_p(stream or None)))
+    return puct_begin_reuse
+
+
+def _puct_forget(g):
+    def puct_forget(self, first_game, n, stream=0):
+        check(g.puct_forget(self._h, first_game, n, ctypes.c_void_p(stream or None)))
+    return puct_forget
+
+
+def _puct_forget_fresh(g):
+    def puct_forget_fresh(self, first_game, n, d_slot, stream=0):
+        check(g.puct_forget_fresh(self._h, first_game, n, ctypes.c_void_p(d_slot), ctypes.c_void_p(stream or None)))
+    return puct_forget_fresh
+
+
+def _puct_backup(g):
+    def puct_backup(self, first_game, n, flush, d_values, d_logits, logits_f16=False, stream=0, rows=0):
+        """rows: values / logits rows per game (0: batch_size; flush 0 also takes 1 — the roots alone)."""
+        check(g.puct_backup_ex(self._h, first_game, n, int(flush), ctypes.c_void_p(d_values),
+                               ctypes.c_void_p(d_logits), ZC_F16 if logits_f16 else ZC_F32, int(rows),
+                               ctypes.c_void_p(stream or None)))
+    return puct_backup
+
+
+def _puct_end(g):
+    def puct_end(self, first_game, n, temperature, d_move, d_na, d_prior, d_stats, stream=0):
+        check(g.puct_end(self._h, first_game, n, float(temperature), ctypes.c_void_p(d_move), ctypes.c_void_p(d_na),
+                         ctypes.c_void_p(d_prior or None), ctypes.c_void_p(d_stats), ctypes.c_void_p(stream or None)))
+    return puct_end
 
 
 class NativeEngine:
@@ -958,33 +772,39 @@ class NativeEngine:
         check(lib().zc_c4_play_async(self._h, n, ctypes.c_void_p(d_states), ctypes.c_void_p(d_moves),
                                      ctypes.c_void_p(d_results), int(bool(reset)), ctypes.c_void_p(stream or None)))
 
-    # ---- stepwise search (caller-supplied values); device pointers as ints, 0 = NULL
+    # ---- stepwise value search (caller-supplied values), with the host-policy walk and expansion
     def c4_ext_begin(self, first_game: int, n: int, d_roots: int, sims: int, c: float, batch_size: int,
                      stream: int = 0) -> None:
-        check(lib().zc_c4_ext_begin(self._h, first_game, n, ctypes.c_void_p(d_roots), int(sims), float(c),
-                                    int(batch_size), ctypes.c_void_p(stream or None)))
+        _ext_begin(_C4.ext_begin, self, first_game, n, d_roots, sims, c, batch_size, (), stream)
 
-    def c4_ext_select(self, first_game: int, n: int, flush: int, d_leaves: int = 0, d_planes: int = 0,
-                      planes_f16: bool = True, d_counts: int = 0, stream: int = 0) -> None:
-        check(lib().zc_c4_ext_select(self._h, first_game, n, int(flush), ctypes.c_void_p(d_leaves or None),
-                                     ctypes.c_void_p(d_planes or None), ZC_F16 if planes_f16 else ZC_F32,
-                                     ctypes.c_void_p(d_counts or None), ctypes.c_void_p(stream or None)))
+    def chess_ext_begin(self, first_game: int, n: int, d_roots: int, sims: int, c: float, batch_size: int,
+                        policy: int = 0, freedom: float = 0.0, stream: int = 0):
+        _ext_begin(_CHESS.ext_begin, self, first_game, n, d_roots, sims, c, batch_size, (int(policy), float(freedom)),
+                   stream)
 
-    def c4_ext_backup(self, first_game: int, n: int, flush: int, d_values: int, stream: int = 0) -> None:
-        check(lib().zc_c4_ext_backup(self._h, first_game, n, int(flush), ctypes.c_void_p(d_values),
-                                     ctypes.c_void_p(stream or None)))
+    c4_ext_select, chess_ext_select = _ext_select(_C4), _ext_select(_CHESS)
+    c4_ext_backup, chess_ext_backup = _ext_backup(_C4), _ext_backup(_CHESS)
+    c4_ext_end, chess_ext_end = _ext_end(_C4), _ext_end(_CHESS)
+    c4_hp_walk, chess_hp_walk = _hp_walk(_C4), _hp_walk(_CHESS)
+    c4_hp_expand, chess_hp_expand = _hp_expand(_C4), _hp_expand(_CHESS)
 
-    def c4_hp_walk(self, game: int, flush: int, leaf: int, d_node: int, stream: int = 0) -> None:
-        check(lib().zc_c4_hp_walk(self._h, game, int(flush), int(leaf), ctypes.c_void_p(d_node),
-                                  ctypes.c_void_p(stream or None)))
+    # ---- stepwise PUCT search
+    c4_puct_begin, chess_puct_begin = _puct_begin(_C4), _puct_begin(_CHESS)
+    c4_puct_begin_reuse, chess_puct_begin_reuse = _puct_begin_reuse(_C4), _puct_begin_reuse(_CHESS)
+    c4_puct_forget, chess_puct_forget = _puct_forget(_C4), _puct_forget(_CHESS)
+    c4_puct_forget_fresh, chess_puct_forget_fresh = _puct_forget_fresh(_C4), _puct_forget_fresh(_CHESS)
+    c4_puct_backup, chess_puct_backup = _puct_backup(_C4), _puct_backup(_CHESS)
+    c4_puct_end, chess_puct_end = _puct_end(_C4), _puct_end(_CHESS)
 
-    def c4_hp_expand(self, game: int, flush: int, leaf: int, index: int, d_leaf: int = 0, stream: int = 0) -> None:
-        check(lib().zc_c4_hp_expand(self._h, game, int(flush), int(leaf), int(index), ctypes.c_void_p(d_leaf or None),
-                                    ctypes.c_void_p(stream or None)))
+    def c4_puct_select(self, first_game, n, flush, d_leaves=0, d_planes=0, planes_f16=True, d_counts=0, stream=0):
+        _select(_C4.puct_select, self, first_game, n, flush, d_leaves, d_planes, ZC_F16 if planes_f16 else ZC_F32,
+                d_counts, stream)
 
-    def c4_ext_end(self, first_game: int, n: int, d_move: int, d_na: int, d_stats: int, stream: int = 0) -> None:
-        check(lib().zc_c4_ext_end(self._h, first_game, n, ctypes.c_void_p(d_move), ctypes.c_void_p(d_na),
-                                  ctypes.c_void_p(d_stats), ctypes.c_void_p(stream or None)))
+    def chess_puct_select(self, first_game, n, flush, d_leaves=0, d_planes=0, planes_f16=True, d_counts=0, stream=0,
+                          planes_nhwc=False):
+        """planes_nhwc: fp16 planes in the tower's input layout [n*bs][64][32] (ZC_F16_NHWC32)."""
+        _select(_CHESS.puct_select, self, first_game, n, flush, d_leaves, d_planes,
+                ZC_F16_NHWC32 if planes_nhwc else ZC_F16 if planes_f16 else ZC_F32, d_counts, stream)
 
     # ---- chess rules (device pointers; stream 0 = null stream)
     def chess_legal_moves_async(self, n: int, d_states: int, d_moves: int, d_counts: int, stream: int = 0):
@@ -1039,33 +859,6 @@ class NativeEngine:
                                           ctypes.c_void_p(d_na), ctypes.c_void_p(d_stats),
                                           ctypes.c_void_p(stream or None)))
 
-    def chess_ext_begin(self, first_game: int, n: int, d_roots: int, sims: int, c: float, batch_size: int,
-                        policy: int = 0, freedom: float = 0.0, stream: int = 0):
-        check(lib().zc_chess_ext_begin(self._h, first_game, n, ctypes.c_void_p(d_roots), int(sims), float(c),
-                                       int(batch_size), int(policy), float(freedom), ctypes.c_void_p(stream or None)))
-
-    def chess_ext_select(self, first_game: int, n: int, flush: int, d_leaves: int = 0, d_planes: int = 0,
-                         planes_f16: bool = True, d_counts: int = 0, stream: int = 0):
-        check(lib().zc_chess_ext_select(self._h, first_game, n, int(flush), ctypes.c_void_p(d_leaves or None),
-                                        ctypes.c_void_p(d_planes or None), ZC_F16 if planes_f16 else ZC_F32,
-                                        ctypes.c_void_p(d_counts or None), ctypes.c_void_p(stream or None)))
-
-    def chess_ext_backup(self, first_game: int, n: int, flush: int, d_values: int, stream: int = 0):
-        check(lib().zc_chess_ext_backup(self._h, first_game, n, int(flush), ctypes.c_void_p(d_values),
-                                        ctypes.c_void_p(stream or None)))
-
-    def chess_hp_walk(self, game: int, flush: int, leaf: int, d_node: int, stream: int = 0) -> None:
-        check(lib().zc_chess_hp_walk(self._h, game, int(flush), int(leaf), ctypes.c_void_p(d_node),
-                                     ctypes.c_void_p(stream or None)))
-
-    def chess_hp_expand(self, game: int, flush: int, leaf: int, index: int, d_leaf: int = 0, stream: int = 0) -> None:
-        check(lib().zc_chess_hp_expand(self._h, game, int(flush), int(leaf), int(index),
-                                       ctypes.c_void_p(d_leaf or None), ctypes.c_void_p(stream or None)))
-
-    def chess_ext_end(self, first_game: int, n: int, d_move: int, d_na: int, d_stats: int, stream: int = 0):
-        check(lib().zc_chess_ext_end(self._h, first_game, n, ctypes.c_void_p(d_move), ctypes.c_void_p(d_na),
-                                     ctypes.c_void_p(d_stats), ctypes.c_void_p(stream or None)))
-
     # ---- the walk diagnostic (device pointers; tools/prof_walk.py)
     def c4_walk_async(self, first_game: int, n: int, d_roots: int, sims: int, c: float, batch_size: int, mode: int,
                       d_vals: int, d_words: int, d_move: int, d_na: int, d_stats: int, stream: int = 0):
@@ -1088,92 +881,13 @@ class NativeEngine:
 
     def chess_ext_rollouts(self, first_game: int, n: int, flush: int, d_hist: int, d_hist_len: int, hist_cap: int,
                            d_values: int, d_status: int = 0, stream: int = 0):
-        check(lib().zc_chess_ext_rollouts(self._h, first_game, n, int(flush), ctypes.c_void_p(d_hist),
-                                          ctypes.c_void_p(d_hist_len), int(hist_cap), ctypes.c_void_p(d_values),
-                                          ctypes.c_void_p(d_status or None), ctypes.c_void_p(stream or None)))
+        check(_CHESS.ext_rollouts(self._h, first_game, n, int(flush), ctypes.c_void_p(d_hist),
+                                  ctypes.c_void_p(d_hist_len), int(hist_cap), ctypes.c_void_p(d_values),
+                                  ctypes.c_void_p(d_status or None), ctypes.c_void_p(stream or None)))
 
     def chess_ext_leaf_moves(self, first_game: int, n: int, flush: int, d_moves: int, d_depth: int, stream: int = 0):
-        check(lib().zc_chess_ext_leaf_moves(self._h, first_game, n, int(flush), ctypes.c_void_p(d_moves),
-                                            ctypes.c_void_p(d_depth), ctypes.c_void_p(stream or None)))
-
-    # ---- chess PUCT search (device pointers)
-    def chess_puct_begin(self, first_game, n, d_roots, sims, c_puct, batch_size, alpha, eps, seed, d_search_no=0,
-                        stream=0):
-        check(lib().zc_chess_puct_begin(self._h, first_game, n, ctypes.c_void_p(d_roots), int(sims), float(c_puct),
-                                        int(batch_size), float(alpha), float(eps), int(seed) & (2**64 - 1),
-                                        ctypes.c_void_p(d_search_no or None), ctypes.c_void_p(stream or None)))
-
-    def chess_puct_begin_reuse(self, first_game, n, d_roots, sims, c_puct, batch_size, alpha, eps, seed,
-                               d_search_no=0, d_kept=0, stream=0):
-        """chess_puct_begin that keeps each game's subtree of its new root (zc_chess_puct_begin_reuse)."""
-        check(lib().zc_chess_puct_begin_reuse(self._h, first_game, n, ctypes.c_void_p(d_roots), int(sims),
-                                              float(c_puct), int(batch_size), float(alpha), float(eps),
-                                              int(seed) & (2**64 - 1), ctypes.c_void_p(d_search_no or None),
-                                              ctypes.c_void_p(d_kept or None), ctypes.c_void_p(stream or None)))
-
-    def chess_puct_forget(self, first_game, n, stream=0):
-        check(lib().zc_chess_puct_forget(self._h, first_game, n, ctypes.c_void_p(stream or None)))
-
-    def chess_puct_forget_fresh(self, first_game, n, d_slot, stream=0):
-        check(lib().zc_chess_puct_forget_fresh(self._h, first_game, n, ctypes.c_void_p(d_slot),
-                                               ctypes.c_void_p(stream or None)))
-
-    def chess_puct_select(self, first_game, n, flush, d_leaves=0, d_planes=0, planes_f16=True, d_counts=0, stream=0,
-                          planes_nhwc=False):
-        """planes_nhwc: fp16 planes in the tower's input layout [n*bs][64][32] (ZC_F16_NHWC32)."""
-        code = ZC_F16_NHWC32 if planes_nhwc else ZC_F16 if planes_f16 else ZC_F32
-        check(lib().zc_chess_puct_select(self._h, first_game, n, int(flush), ctypes.c_void_p(d_leaves or None),
-                                         ctypes.c_void_p(d_planes or None), code,
-                                         ctypes.c_void_p(d_counts or None), ctypes.c_void_p(stream or None)))
-
-    def chess_puct_backup(self, first_game, n, flush, d_values, d_logits, logits_f16=False, stream=0, rows=0):
-        """rows: values / logits rows per game (0: batch_size; flush 0 also takes 1 — the roots alone)."""
-        check(lib().zc_chess_puct_backup_ex(self._h, first_game, n, int(flush), ctypes.c_void_p(d_values),
-                                            ctypes.c_void_p(d_logits), ZC_F16 if logits_f16 else ZC_F32, int(rows),
-                                            ctypes.c_void_p(stream or None)))
-
-    def chess_puct_end(self, first_game, n, temperature, d_move, d_na, d_prior, d_stats, stream=0):
-        check(lib().zc_chess_puct_end(self._h, first_game, n, float(temperature), ctypes.c_void_p(d_move),
-                                      ctypes.c_void_p(d_na), ctypes.c_void_p(d_prior or None),
-                                      ctypes.c_void_p(d_stats), ctypes.c_void_p(stream or None)))
-
-    # ---- Connect4 PUCT search (device pointers as ints)
-    def c4_puct_begin(self, first_game, n, d_roots, sims, c_puct, batch_size, alpha, eps, seed, d_search_no=0,
-                        stream=0):
-        check(lib().zc_c4_puct_begin(self._h, first_game, n, ctypes.c_void_p(d_roots), int(sims), float(c_puct),
-                                     int(batch_size), float(alpha), float(eps), int(seed) & (2**64 - 1),
-                                     ctypes.c_void_p(d_search_no or None), ctypes.c_void_p(stream or None)))
-
-    def c4_puct_begin_reuse(self, first_game, n, d_roots, sims, c_puct, batch_size, alpha, eps, seed, d_search_no=0,
-                            d_kept=0, stream=0):
-        """c4_puct_begin that keeps each game's subtree of its new root (zc_c4_puct_begin_reuse)."""
-        check(lib().zc_c4_puct_begin_reuse(self._h, first_game, n, ctypes.c_void_p(d_roots), int(sims), float(c_puct),
-                                           int(batch_size), float(alpha), float(eps), int(seed) & (2**64 - 1),
-                                           ctypes.c_void_p(d_search_no or None), ctypes.c_void_p(d_kept or None),
-                                           ctypes.c_void_p(stream or None)))
-
-    def c4_puct_forget(self, first_game, n, stream=0):
-        check(lib().zc_c4_puct_forget(self._h, first_game, n, ctypes.c_void_p(stream or None)))
-
-    def c4_puct_forget_fresh(self, first_game, n, d_slot, stream=0):
-        check(lib().zc_c4_puct_forget_fresh(self._h, first_game, n, ctypes.c_void_p(d_slot),
-                                            ctypes.c_void_p(stream or None)))
-
-    def c4_puct_select(self, first_game, n, flush, d_leaves=0, d_planes=0, planes_f16=True, d_counts=0, stream=0):
-        check(lib().zc_c4_puct_select(self._h, first_game, n, int(flush), ctypes.c_void_p(d_leaves or None),
-                                      ctypes.c_void_p(d_planes or None), ZC_F16 if planes_f16 else ZC_F32,
-                                      ctypes.c_void_p(d_counts or None), ctypes.c_void_p(stream or None)))
-
-    def c4_puct_backup(self, first_game, n, flush, d_values, d_logits, logits_f16=False, stream=0, rows=0):
-        """rows: as chess_puct_backup."""
-        check(lib().zc_c4_puct_backup_ex(self._h, first_game, n, int(flush), ctypes.c_void_p(d_values),
-                                         ctypes.c_void_p(d_logits), ZC_F16 if logits_f16 else ZC_F32, int(rows),
-                                         ctypes.c_void_p(stream or None)))
-
-    def c4_puct_end(self, first_game, n, temperature, d_move, d_na, d_prior, d_stats, stream=0):
-        check(lib().zc_c4_puct_end(self._h, first_game, n, float(temperature), ctypes.c_void_p(d_move),
-                                   ctypes.c_void_p(d_na), ctypes.c_void_p(d_prior or None),
-                                   ctypes.c_void_p(d_stats), ctypes.c_void_p(stream or None)))
+        check(_CHESS.ext_leaf_moves(self._h, first_game, n, int(flush), ctypes.c_void_p(d_moves),
+                                    ctypes.c_void_p(d_depth), ctypes.c_void_p(stream or None)))
 
     def debug_c4_puct_tree(self, game: int, max_nodes: int = 1 << 16) -> np.ndarray:
         """Game `game`'s Connect4 PUCT tree (test hook): node records (C4_PNODE_DTYPE)."""

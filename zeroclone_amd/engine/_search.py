@@ -231,109 +231,102 @@ def c4_moves(eng, ids, roots, sims, c, bs, value, backend):
     return [(int(m), 0) for m in mv.cpu().numpy()]
 
 
-def c4_host_policy_moves(eng, ids, roots, sims, c, bs, value, policy, backend):
-    """The §8(b) fallback: mcts.get_move with an arbitrary policy callable.  Per game, per
-    simulation: zc_c4_hp_walk selects (mcts.cpp:47-63) on the device tree, the policy picks
-    among the untried moves on the host exactly as mcts.cpp:67-70 calls it (the untried moves
-    as a list in the node's order; the action's list.index), zc_c4_hp_expand expands; each
-    flush's leaves go to value.batch (mcts.cpp:116) and zc_c4_ext_backup.  Python's `random`
-    is used only by the policy and the value themselves, in the reference's order."""
+def _host_policy_moves(g, eng, ids, roots, sims, c, bs, value, policy, backend):
+    """The §8(b) fallback: mcts.get_move with an arbitrary policy callable, on the game g
+    describes (the two callers below).  Per game, per simulation: hp_walk selects
+    (mcts.cpp:47-63) on the device tree, the policy picks among the untried moves on the host
+    exactly as mcts.cpp:67-70 calls it (the untried moves as a list in the node's order; the
+    action's list.index), hp_expand expands; each flush's leaves go to value.batch
+    (mcts.cpp:116) and ext_backup.  Python's `random` is used only by the policy and the value
+    themselves, in the reference's order."""
     import torch
-    from .games.connect4 import c4_backend as zb
     dev = torch.device("cuda", eng.device)
     stream = torch.cuda.current_stream(dev)
     s = stream.cuda_stream
-    node = torch.zeros(_native.C4_HP_NODE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    leaf = torch.zeros(3, dtype=torch.int64, device=dev)
+    begin, walk, expand, backup, end = (getattr(eng, f"{g.game}_{step}")
+                                        for step in ("ext_begin", "hp_walk", "hp_expand", "ext_backup", "ext_end"))
+    node = torch.zeros(g.node.itemsize, dtype=torch.uint8, device=dev)
+    leaf = torch.zeros(g.leaf[0], dtype=g.leaf[1], device=dev)
     vals = torch.zeros(bs, dtype=torch.float64, device=dev)
-    mv = torch.zeros(1, dtype=torch.int32, device=dev)
-    na = torch.zeros((1, 7), dtype=torch.int32, device=dev)
+    mv = torch.zeros(1, dtype=g.move, device=dev)
+    na = torch.zeros((1, g.na), dtype=torch.int32, device=dev)
     st = torch.zeros((1, _native.STATS_FIELDS), dtype=torch.int64, device=dev)
     out = []
     for gi, root in zip(ids, roots):
-        r = torch.from_numpy(np.asarray([root], _native.C4_STATE_DTYPE).view(np.int64).reshape(1, 3).copy()).to(dev)
-        eng.c4_ext_begin(int(gi), 1, r.data_ptr(), sims, c, bs, s)
-        for f in range((sims + bs - 1) // bs):
-            nb = min(bs, sims - f * bs)
-            states = []
-            for j in range(nb):
-                eng.c4_hp_walk(int(gi), f, j, node.data_ptr(), s)
-                nd = node.cpu().numpy().view(_native.C4_HP_NODE_DTYPE)[0]
-                if int(nd["node"]) < 0:
-                    raise ValueError("invalid root for the search (bad state or no legal move)")
-                k = -1
-                n_un = int(nd["n_untried"])
-                if n_un:
-                    moves = [(int(col), 0) for col in nd["untried"][:n_un]]
-                    k = moves.index(policy(moves))
-                eng.c4_hp_expand(int(gi), f, j, k, leaf.data_ptr(), s)
-                row = leaf.cpu().numpy().view(np.uint64)
-                states.append(zb.from_zc(int(row[0]), int(row[1]), int(row[2]) & 1))
-            v = [float(x) for x in value.batch(states, backend=backend)]
-            vals[:nb].copy_(torch.tensor(v, dtype=torch.float64))
-            eng.c4_ext_backup(int(gi), 1, f, vals.data_ptr(), s)
-        eng.c4_ext_end(int(gi), 1, mv.data_ptr(), na.data_ptr(), st.data_ptr(), s)
-        stream.synchronize()
-        if int(st[0, 5].item()):
-            raise RuntimeError(f"host-policy search failed (status {int(st[0, 5].item())})")
-        out.append((int(mv[0].item()), 0))
-    return out
-
-
-def chess_host_policy_moves(eng, ids, states, sims, c, bs, value, policy, backend):
-    """The §8(b) fallback for chess: as c4_host_policy_moves, on the chess tree
-    (zc_chess_hp_walk / zc_chess_hp_expand inside a zc_chess_ext_* search).  The policy gets
-    the untried moves as the reference's move objects ((fr, fc, tr, tc), capture value), in
-    the node's untried order; a game with no legal move gives None."""
-    import torch
-    from .games.chess import chess_backend as cb
-    dev = torch.device("cuda", eng.device)
-    stream = torch.cuda.current_stream(dev)
-    s = stream.cuda_stream
-    node = torch.zeros(_native.CHESS_HP_NODE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    leaf = torch.zeros(72, dtype=torch.uint8, device=dev)
-    vals = torch.zeros(bs, dtype=torch.float64, device=dev)
-    mv = torch.zeros(1, dtype=torch.int16, device=dev)
-    na = torch.zeros((1, _native.CHESS_MAX_MOVES), dtype=torch.int32, device=dev)
-    st = torch.zeros((1, _native.STATS_FIELDS), dtype=torch.int64, device=dev)
-    out = []
-    for gi, state in zip(ids, states):
-        root = torch.from_numpy(chess_roots([state]).view(np.uint8).reshape(1, 72).copy()).to(dev)
-        eng.chess_ext_begin(int(gi), 1, root.data_ptr(), sims, c, bs, _native.ZC_POLICY_RANDOM, 0.0, s)
+        gi = int(gi)
+        r = torch.from_numpy(g.root_row(root)).to(dev)
+        begin(gi, 1, r.data_ptr(), sims, c, bs, *g.begin_extra, s)
         live = True
         for f in range((sims + bs - 1) // bs):
             nb = min(bs, sims - f * bs)
-            leaves = []
+            rows = []
             for j in range(nb):
-                eng.chess_hp_walk(int(gi), f, j, node.data_ptr(), s)
-                nd = node.cpu().numpy().view(_native.CHESS_HP_NODE_DTYPE)[0]
-                if int(nd["node"]) < 0:
+                walk(gi, f, j, node.data_ptr(), s)
+                nd = node.cpu().numpy().view(g.node)[0]
+                if int(nd["node"]) < 0:   # the root was refused
+                    if g.refused:
+                        raise ValueError(g.refused)
                     live = False
                     break
                 k = -1
                 n_un = int(nd["n_untried"])
                 if n_un:
-                    moves = [_native.unpack_chess_move(m) for m in nd["untried"][:n_un]]
+                    moves = [g.move_of(m) for m in nd["untried"][:n_un]]
                     k = moves.index(policy(moves))
-                eng.chess_hp_expand(int(gi), f, j, k, leaf.data_ptr(), s)
-                leaves.append(leaf.cpu().numpy().copy())
+                expand(gi, f, j, k, leaf.data_ptr(), s)
+                rows.append(leaf.cpu().numpy().copy())
             if not live:
                 break
-            leaves = chess_leaf_states(eng, int(gi), 1, f, bs, np.stack(leaves), [nb], [state])[0]
-            v = [float(x) for x in value.batch(leaves, backend=backend)]
+            v = [float(x) for x in value.batch(g.leaf_states(gi, f, np.stack(rows), root), backend=backend)]
             vals[:nb].copy_(torch.tensor(v, dtype=torch.float64))
-            eng.chess_ext_backup(int(gi), 1, f, vals.data_ptr(), s)
-        eng.chess_ext_end(int(gi), 1, mv.data_ptr(), na.data_ptr(), st.data_ptr(), s)
+            backup(gi, 1, f, vals.data_ptr(), s)
+        end(gi, 1, mv.data_ptr(), na.data_ptr(), st.data_ptr(), s)
         stream.synchronize()
         status = int(st[0, 5].item())
-        if status == _native.ZC_STATUS_NO_MOVES:
+        if status and status == g.no_moves:
             out.append(None)
-            continue
-        if status:
-            raise RuntimeError(f"host-policy chess search failed (status {status})")
-        m = int(mv[0].item()) & 0xFFFF
-        out.append(None if m == 0xFFFF else _native.unpack_chess_move(m))
+        elif status:
+            raise RuntimeError(f"{g.what} failed (status {status})")
+        else:
+            out.append(g.result(int(mv[0].item())))
     return out
+
+
+def c4_host_policy_moves(eng, ids, roots, sims, c, bs, value, policy, backend):
+    """The host-policy search on Connect4 (zc_c4_hp_walk / zc_c4_hp_expand inside a zc_c4_ext_*
+    search); moves are (column, 0).  A root that is no searchable position raises ValueError
+    at its first walk."""
+    import torch
+    from types import SimpleNamespace
+    from .games.connect4 import c4_backend as zb
+    return _host_policy_moves(SimpleNamespace(
+        game="c4", node=_native.C4_HP_NODE_DTYPE, leaf=(3, torch.int64), move=torch.int32, na=7, begin_extra=(),
+        root_row=lambda root: np.asarray([root], _native.C4_STATE_DTYPE).view(np.int64).reshape(1, 3).copy(),
+        move_of=lambda col: (int(col), 0),
+        leaf_states=lambda gi, f, rows, root: [zb.from_zc(int(r[0]), int(r[1]), int(r[2]) & 1)
+                                               for r in rows.view(np.uint64)],
+        result=lambda m: (m, 0), what="host-policy search", no_moves=None,
+        refused="invalid root for the search (bad state or no legal move)",
+    ), eng, ids, roots, sims, c, bs, value, policy, backend)
+
+
+def chess_host_policy_moves(eng, ids, states, sims, c, bs, value, policy, backend):
+    """The host-policy search on the chess tree (zc_chess_hp_walk / zc_chess_hp_expand inside a
+    zc_chess_ext_* search).  The policy gets the untried moves as the reference's move objects
+    ((fr, fc, tr, tc), capture value), in the node's untried order, and a flush's leaves carry
+    their move histories (chess_leaf_states).  A refused root stops the search, whose status then
+    says why: a game with no legal move gives None."""
+    import torch
+    from types import SimpleNamespace
+    return _host_policy_moves(SimpleNamespace(
+        game="chess", node=_native.CHESS_HP_NODE_DTYPE, leaf=(72, torch.uint8), move=torch.int16,
+        na=_native.CHESS_MAX_MOVES, begin_extra=(_native.ZC_POLICY_RANDOM, 0.0),
+        root_row=lambda state: chess_roots([state]).view(np.uint8).reshape(1, 72).copy(),
+        move_of=_native.unpack_chess_move,
+        leaf_states=lambda gi, f, rows, state: chess_leaf_states(eng, gi, 1, f, bs, rows, [len(rows)], [state])[0],
+        result=lambda m: None if m & 0xFFFF == 0xFFFF else _native.unpack_chess_move(m & 0xFFFF),
+        what="host-policy chess search", no_moves=_native.ZC_STATUS_NO_MOVES, refused=None,
+    ), eng, ids, states, sims, c, bs, value, policy, backend)
 
 
 def generic_moves(eng, state, sims, c, bs, value, policy, backend):

@@ -150,10 +150,13 @@ class _StepSearch:
 
         begin -> [select(f) -> evaluate -> backup(f)] * flushes -> end    (_split_flushes)
 
-    A search class gives the row shapes below and _begin(first, roots, sims, par, stream),
+    A search kind (_ValueSearch, _PuctSearch) gives _begin(first, roots, sims, par, stream),
     _select (as _split_flushes calls it), _evaluate_backup(sims) (the rule for _split_flushes),
-    _end(first, par, stream) and _flushes(sims); par is the move's own parameter, a value
-    search's c or a PUCT search's temperature."""
+    _end(first, par, stream) and _flushes(sims), written against the engine's wrappers of its
+    STEPS; par is the move's own parameter, a value search's c or a PUCT search's temperature.
+    A game's class gives GAME, which selects those wrappers, and the row shapes below."""
+    GAME = ""                        # "c4" / "chess": the engine's <GAME>_<step> wrappers
+    STEPS = ()                       # the kind's steps: self._<step> = eng.<GAME>_<step>, looked up once
     STATE = ""                       # the C struct of a root / leaf row
     LEAF = ((0,), torch.uint8)       # a leaf row's shape and dtype (the roots' too)
     PLANES = (0, 0, 0)               # one leaf's planes
@@ -169,6 +172,8 @@ class _StepSearch:
         if planes_dtype not in (torch.float16, torch.float32):
             raise ValueError("planes_dtype must be float16 or float32")
         self.eng, self.n, self.bs = eng, n_games, batch_size
+        for step in self.STEPS:
+            setattr(self, "_" + step, getattr(eng, f"{self.GAME}_{step}"))
         self.dev = dev = torch.device("cuda", eng.device)
         L, (row, row_dtype) = n_games * batch_size, self.LEAF
         self.leaves = torch.zeros((L, *row), dtype=row_dtype, device=dev) if leaves else None
@@ -216,9 +221,23 @@ class _StepSearch:
 class _ValueSearch(_StepSearch):
     """value_fn: one callable, or a list of k callables — then the games are split into k
     contiguous parts searched on k streams (_split_flushes).  The results are the same."""
+    STEPS = ("ext_begin", "ext_select", "ext_backup", "ext_end")
+    _begin_extra = ()   # what the game's ext_begin takes after batch_size
 
     def _flushes(self, sims: int) -> int:
         return (sims + self.bs - 1) // self.bs
+
+    def _begin(self, first, roots, sims, c, s):
+        self._ext_begin(first, self.n, roots.data_ptr(), sims, c, self.bs, *self._begin_extra, s)
+
+    def _select(self, first, m, f, lv, pv, cv, s):
+        self._ext_select(first, m, f, _ptr(lv), _ptr(pv), pv is None or pv.dtype == torch.float16, cv.data_ptr(), s)
+
+    def _evaluate_backup(self, sims):
+        return _value_backup(sims, self.bs, self._ext_backup)
+
+    def _end(self, first, c, s):
+        self._ext_end(first, self.n, self.move.data_ptr(), self.na.data_ptr(), self.stats.data_ptr(), s)
 
     def enqueue(self, roots: torch.Tensor, sims: int, c: float, value_fn, first_game: int = 0):
         """Enqueue one whole move on torch's current stream (no host synchronisation unless
@@ -240,6 +259,9 @@ class _PuctSearch(_StepSearch):
     contiguous parts searched on k streams (_split_flushes): one part's select, backup and
     policy GEMM overlap another part's tower.  The results are the same."""
     PRIOR = True
+    STEPS = ("puct_begin", "puct_begin_reuse", "puct_forget", "puct_forget_fresh", "puct_select", "puct_backup",
+             "puct_end")
+    _select_extra = {}   # what the game's puct_select takes besides
 
     def _alloc_puct(self, eng, n_games, batch_size, c_puct, alpha, eps, seed, planes_dtype, leaves):
         self._alloc(eng, n_games, batch_size, planes_dtype, leaves)
@@ -248,8 +270,47 @@ class _PuctSearch(_StepSearch):
         # temperature sample; each search adds 1 on the device (graph replays included)
         self.search_no = torch.zeros(n_games, dtype=torch.int32, device=self.dev)
 
+    def _alloc_reuse(self, reuse: bool):
+        """reuse and kept; with reuse, the re-root's scratch too exists before any graph capture."""
+        self.reuse, self.kept = bool(reuse), None
+        if self.reuse:
+            self.kept = torch.zeros(self.n, dtype=torch.int32, device=self.dev)
+            z = torch.zeros((1, *self.LEAF[0]), dtype=self.LEAF[1], device=self.dev)
+            self._puct_begin_reuse(0, 0, z.data_ptr(), 2, self.c, self.bs, self.alpha, self.eps, self.seed)
+            self.forget()   # trees of an earlier search object on this engine are not this one's
+
+    def forget(self, first_game: int = 0, n: int | None = None):
+        """Drop the kept trees of games [first_game, first_game + n) (default: this search's n
+        games), stream-ordered: their next search starts afresh."""
+        self._puct_forget(first_game, self.n if n is None else n, _stream(self.dev))
+
+    def forget_fresh(self, slot: torch.Tensor, stream: int | None = None):
+        """Drop the kept trees of the games whose recorder slot (Trajectories.slot, [n, 4] int32)
+        holds a game at its first position, on the device (stream: default torch's current one):
+        a refilled slot's tree belongs to the game that ended."""
+        self._puct_forget_fresh(0, self.n, slot.data_ptr(), stream if stream is not None else _stream(self.dev))
+
     def _flushes(self, sims: int) -> int:
         return _native.check(_native.lib().zc_chess_puct_flushes(int(sims), int(self.bs)))
+
+    def _begin(self, first, roots, sims, temperature, s):
+        args = (first, self.n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps, self.seed,
+                self.search_no.data_ptr())
+        if self.reuse:
+            self._puct_begin_reuse(*args, self.kept.data_ptr(), stream=s)
+        else:
+            self._puct_begin(*args, stream=s)
+
+    def _select(self, first, m, f, lv, pv, cv, s):
+        self._puct_select(first, m, f, _ptr(lv), pv.data_ptr(), pv.dtype == torch.float16, cv.data_ptr(), s,
+                          **self._select_extra)
+
+    def _evaluate_backup(self, sims):
+        return _puct_backup(self.bs, self._puct_backup)
+
+    def _end(self, first, temperature, s):
+        self._puct_end(first, self.n, temperature, self.move.data_ptr(), self.na.data_ptr(), self.prior.data_ptr(),
+                       self.stats.data_ptr(), s)
 
     def enqueue(self, roots: torch.Tensor, sims: int, net_fn, temperature: float = 0.0, first_game: int = 0):
         return self._enqueue(roots, sims, net_fn, first_game, temperature)
@@ -262,24 +323,12 @@ class _PuctSearch(_StepSearch):
 
 
 class C4ValuedSearch(_ValueSearch):
+    GAME = "c4"
     STATE, LEAF, PLANES, MOVE, NA = "zc_c4_state", ((3,), torch.int64), (2, 6, 7), torch.int32, 7
 
     def __init__(self, eng: "_native.NativeEngine", n_games: int, batch_size: int = 32,
                  planes_dtype: torch.dtype = torch.float16, leaves: bool = True, planes: bool = True):
         self._alloc(eng, n_games, batch_size, planes_dtype, leaves, planes)
-
-    def _begin(self, first, roots, sims, c, s):
-        self.eng.c4_ext_begin(first, self.n, roots.data_ptr(), sims, c, self.bs, s)
-
-    def _select(self, first, m, f, lv, pv, cv, s):
-        self.eng.c4_ext_select(first, m, f, _ptr(lv), _ptr(pv), pv is None or pv.dtype == torch.float16,
-                               cv.data_ptr(), s)
-
-    def _evaluate_backup(self, sims):
-        return _value_backup(sims, self.bs, self.eng.c4_ext_backup)
-
-    def _end(self, first, c, s):
-        self.eng.c4_ext_end(first, self.n, self.move.data_ptr(), self.na.data_ptr(), self.stats.data_ptr(), s)
 
 
 class NetValue:
@@ -461,6 +510,8 @@ class ChessValuedSearch(_ValueSearch):
     """Stepwise chess search (zc_chess_ext_*): the configs/chess_value.yaml path — a value
     network evaluates every flush's leaves (planes [n*bs, 17, 8, 8]) between the select and
     backup kernels.  Same protocol and value_fn contract as C4ValuedSearch."""
+    GAME = "chess"
+    _begin_extra = property(lambda self: (self.policy, self.freedom))
     STATE, LEAF, PLANES, MOVE, NA = ("zc_chess_state", ((72,), torch.uint8), (17, 8, 8), torch.int16,
                                      _native.CHESS_MAX_MOVES)
 
@@ -470,19 +521,6 @@ class ChessValuedSearch(_ValueSearch):
         self._alloc(eng, n_games, batch_size, planes_dtype, leaves, planes)
         self.policy, self.freedom = policy, freedom
         eng.chess_reserve()   # the tree arena exists before any graph capture
-
-    def _begin(self, first, roots, sims, c, s):
-        self.eng.chess_ext_begin(first, self.n, roots.data_ptr(), sims, c, self.bs, self.policy, self.freedom, s)
-
-    def _select(self, first, m, f, lv, pv, cv, s):
-        self.eng.chess_ext_select(first, m, f, _ptr(lv), _ptr(pv), pv is None or pv.dtype == torch.float16,
-                                  cv.data_ptr(), s)
-
-    def _evaluate_backup(self, sims):
-        return _value_backup(sims, self.bs, self.eng.chess_ext_backup)
-
-    def _end(self, first, c, s):
-        self.eng.chess_ext_end(first, self.n, self.move.data_ptr(), self.na.data_ptr(), self.stats.data_ptr(), s)
 
 
 class ChessPuctSearch(_PuctSearch):
@@ -497,6 +535,7 @@ class ChessPuctSearch(_PuctSearch):
     then adds sims - 1 visits below the kept ones; `kept` [n] int32 = nodes kept (0: a fresh
     tree).  The engine needs max_sims above sims for anything to be kept; forget() drops the
     trees, and so does any other chess search of the game."""
+    GAME = "chess"
     STATE, LEAF, PLANES, MOVE, NA = ChessValuedSearch.STATE, ChessValuedSearch.LEAF, (17, 8, 8), torch.int16, \
         _native.CHESS_MAX_MOVES
 
@@ -510,47 +549,12 @@ class ChessPuctSearch(_PuctSearch):
         if planes_nhwc and planes_dtype != torch.float16:
             raise ValueError("planes_nhwc needs fp16 planes")
         self.planes_nhwc = planes_nhwc
+        self._select_extra = {"planes_nhwc": planes_nhwc}
         if planes_nhwc:
             self.PLANES = (64, 32)
         self._alloc_puct(eng, n_games, batch_size, c_puct, dirichlet_alpha, dirichlet_eps, seed, planes_dtype, leaves)
         eng.chess_reserve()   # the tree arena exists before any graph capture
-        self.reuse = bool(reuse)
-        self.kept = None
-        if self.reuse:   # and so does the re-root's scratch
-            self.kept = torch.zeros(n_games, dtype=torch.int32, device=self.dev)
-            z = torch.zeros((1, 72), dtype=torch.uint8, device=self.dev)
-            eng.chess_puct_begin_reuse(0, 0, z.data_ptr(), 2, c_puct, batch_size, dirichlet_alpha, dirichlet_eps, seed)
-            self.forget()   # trees of an earlier search object on this engine are not this one's
-
-    def forget(self, first_game: int = 0, n: int | None = None):
-        """Drop the kept trees of games [first_game, first_game + n) (default: this search's n
-        games), stream-ordered: their next search starts afresh."""
-        self.eng.chess_puct_forget(first_game, self.n if n is None else n, _stream(self.dev))
-
-    def forget_fresh(self, slot: torch.Tensor, stream: int | None = None):
-        """Drop the kept trees of the games whose recorder slot (Trajectories.slot, [n, 4] int32)
-        holds a game at its first position, on the device (stream: default torch's current one):
-        a refilled slot's tree belongs to the game that ended."""
-        self.eng.chess_puct_forget_fresh(0, self.n, slot.data_ptr(), stream if stream is not None else _stream(self.dev))
-
-    def _begin(self, first, roots, sims, temperature, s):
-        e, args = self.eng, (first, self.n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps, self.seed,
-                             self.search_no.data_ptr())
-        if self.reuse:
-            e.chess_puct_begin_reuse(*args, self.kept.data_ptr(), stream=s)
-        else:
-            e.chess_puct_begin(*args, stream=s)
-
-    def _select(self, first, m, f, lv, pv, cv, s):
-        self.eng.chess_puct_select(first, m, f, _ptr(lv), pv.data_ptr(), pv.dtype == torch.float16, cv.data_ptr(), s,
-                                   planes_nhwc=self.planes_nhwc)
-
-    def _evaluate_backup(self, sims):
-        return _puct_backup(self.bs, self.eng.chess_puct_backup)
-
-    def _end(self, first, temperature, s):
-        self.eng.chess_puct_end(first, self.n, temperature, self.move.data_ptr(), self.na.data_ptr(),
-                                self.prior.data_ptr(), self.stats.data_ptr(), s)
+        self._alloc_reuse(reuse)
 
 
 class C4PuctSearch(_PuctSearch):
@@ -566,47 +570,14 @@ class C4PuctSearch(_PuctSearch):
     previous search holds it one or two plies below its root (zc_c4_puct_begin_reuse), and then
     adds sims - 1 visits below the kept ones; `kept` [n] int32 = nodes kept (0: a fresh tree).
     The engine needs max_sims above sims for anything to be kept; forget() drops the trees."""
+    GAME = "c4"
     STATE, LEAF, PLANES, MOVE, NA = C4ValuedSearch.STATE, C4ValuedSearch.LEAF, (2, 6, 7), torch.int32, 7
 
     def __init__(self, eng: "_native.NativeEngine", n_games: int, batch_size: int = 32, c_puct: float = 1.5,
                  dirichlet_alpha: float = 0.3, dirichlet_eps: float = 0.25, seed: int = 0,
                  planes_dtype: torch.dtype = torch.float16, leaves: bool = True, reuse: bool = False):
         self._alloc_puct(eng, n_games, batch_size, c_puct, dirichlet_alpha, dirichlet_eps, seed, planes_dtype, leaves)
-        self.reuse = bool(reuse)
         # the tree arena exists before any graph capture
         z = torch.zeros((1, 3), dtype=torch.int64, device=self.dev)
-        eng.c4_puct_begin(0, 0, z.data_ptr(), 2, c_puct, batch_size, dirichlet_alpha, dirichlet_eps, seed)
-        self.kept = None
-        if self.reuse:   # and so does the re-root's scratch
-            self.kept = torch.zeros(n_games, dtype=torch.int32, device=self.dev)
-            eng.c4_puct_begin_reuse(0, 0, z.data_ptr(), 2, c_puct, batch_size, dirichlet_alpha, dirichlet_eps, seed)
-            self.forget()   # trees of an earlier search object on this engine are not this one's
-
-    def forget(self, first_game: int = 0, n: int | None = None):
-        """Drop the kept trees of games [first_game, first_game + n) (default: this search's n
-        games), stream-ordered: their next search starts afresh."""
-        self.eng.c4_puct_forget(first_game, self.n if n is None else n, _stream(self.dev))
-
-    def forget_fresh(self, slot: torch.Tensor, stream: int | None = None):
-        """Drop the kept trees of the games whose recorder slot (Trajectories.slot, [n, 4] int32)
-        holds a game at its first position, on the device (stream: default torch's current one):
-        a refilled slot's tree belongs to the game that ended."""
-        self.eng.c4_puct_forget_fresh(0, self.n, slot.data_ptr(), stream if stream is not None else _stream(self.dev))
-
-    def _begin(self, first, roots, sims, temperature, s):
-        e, args = self.eng, (first, self.n, roots.data_ptr(), sims, self.c, self.bs, self.alpha, self.eps, self.seed,
-                             self.search_no.data_ptr())
-        if self.reuse:
-            e.c4_puct_begin_reuse(*args, self.kept.data_ptr(), stream=s)
-        else:
-            e.c4_puct_begin(*args, stream=s)
-
-    def _select(self, first, m, f, lv, pv, cv, s):
-        self.eng.c4_puct_select(first, m, f, _ptr(lv), pv.data_ptr(), pv.dtype == torch.float16, cv.data_ptr(), s)
-
-    def _evaluate_backup(self, sims):
-        return _puct_backup(self.bs, self.eng.c4_puct_backup)
-
-    def _end(self, first, temperature, s):
-        self.eng.c4_puct_end(first, self.n, temperature, self.move.data_ptr(), self.na.data_ptr(),
-                             self.prior.data_ptr(), self.stats.data_ptr(), s)
+        self._puct_begin(0, 0, z.data_ptr(), 2, c_puct, batch_size, dirichlet_alpha, dirichlet_eps, seed)
+        self._alloc_reuse(reuse)
